@@ -146,7 +146,13 @@ def parse():
     ap.add_argument("--dry-collectives", action="store_true",
                     help="N > 1: run ONLY the gather path (sharding.gather_results and FixedGather, incl. a forced overflow step) on tiny "
                          "tensors -- no database, no kernels -- and print one JSON line: tells a collective failure from a kernel failure")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's pairs: the fields of vsx_plan_fetch) as DIR/<name>.npy "
+                         "in float32 / float64, at most 64 MB (a fixed, seeded sample of the pairs beyond that): two builds compared output for output")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def main():
@@ -334,6 +340,7 @@ def main():
     t0 = time.perf_counter()
     res = plan.fetch()
     t_fetch = time.perf_counter() - t0
+    dumped = dump_outputs(a.dump_outputs, res) if a.dump_outputs else None
 
     total_cells = job_cells * a.steps
     value = total_cells / elapsed / 1e9
@@ -428,6 +435,8 @@ def main():
         out["roofline"]["traffic_note"] = pmc_note
     if gather_check is not None:
         out["gather_check"] = gather_check
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if rccl is not None:
         rccl["per_rank_ms_per_step"] = per_rank_ms
         rccl["gather"] = a.gather
@@ -614,6 +623,28 @@ def dry_collectives(dist, sharding, device, rank, world):
     checks["fixed_gather_mixed_votes_one_rank_overflows"] = all(int(v[0]) == 1 and int(v[1]) == int(views[0][1]) >= 0 and int(v[2]) == 2 for v in views)
     checks["fixed_gather_degraded_at_step"] = int(views[0][1])
     return checks
+
+
+DUMP_MAX_BYTES = 60_000_000          # array data of --dump-outputs: with the .npy headers, under the 64 MB the option promises
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: the last timed step's results (AlignmentResults of plan.fetch) as one .npy per field.  The integer fields are
+    exact in float32; a CIGAR string becomes its length and its CRC-32 (float64, exact).  pair.npy holds each row's index in the step's
+    pair list: all pairs while they fit DUMP_MAX_BYTES, beyond that a fixed seeded sample (the same pairs for the same arguments)."""
+    import zlib
+    n = len(res)
+    cap = DUMP_MAX_BYTES // (6 * 4 + 2 * 8)            # bytes per pair: six float32 fields, two float64
+    idx = np.arange(n) if n <= cap else np.sort(np.random.default_rng(2026).choice(n, cap, replace=False))
+    cig = [res.cigar[i].encode() for i in idx.tolist()]
+    arrays = {k: getattr(res, k)[idx].astype(np.float32) for k in ("score", "aligned", "matches", "mismatches", "gaps")}
+    arrays["cigar_len"] = np.array([len(c) for c in cig], np.float32)
+    arrays["cigar_crc32"] = np.array([zlib.crc32(c) for c in cig], np.float64)
+    arrays["pair"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return {"dir": path, "pairs": n, "pairs_dumped": len(idx), "files": sorted(k + ".npy" for k in arrays)}
 
 
 def end_to_end(a, al, Q, T, qidx, tidx, cells, res):

@@ -4,7 +4,8 @@
 no /root/reference).  The fixtures pin both oracle/nw_oracle.c and the HIP path.
 
   python oracle/gen_golden.py            # writes tests/golden/search16_golden.json,
-                                         #        tests/golden/ref_api_examples.json, lma_golden.json, dust_golden.json
+                                         #        tests/golden/ref_api_examples.json, lma_golden.json, dust_golden.json,
+                                         #        msa_golden.json
   python oracle/gen_golden.py --fuzz N   # additionally: N random pairs oracle-vs-reference (no file)
 """
 import argparse
@@ -257,9 +258,46 @@ def gen_dust(path, n=400):
     print(f"wrote {path}: {len(seqs)} sequences, {sum(1 for e in exp if any(c.islower() for c in e))} with a masked interval")
 
 
+def msa_inputs(seed):
+    """families of mutated copies, one IUPAC-mutated copy and one exact duplicate (its uc line carries '=' instead of a CIGAR)"""
+    rng = random.Random(seed)
+    seqs = []
+    for f in range(6):
+        anc = rnd_seq(rng, rng.randint(120, 180))
+        for _ in range(rng.randint(1, 8)):
+            seqs.append(mutate(rng, anc, rng.choice([0.02, 0.07])))
+    seqs.append(mutate(rng, seqs[0], 0.03, "ACGTNRY"))
+    seqs.append(seqs[1])
+    rng.shuffle(seqs)
+    return seqs
+
+
+def gen_msa(path, seeds=(3, 8)):
+    """the star MSA of the clusters (core/msa.cpp) through the reference CLI: --cluster_fast --uc --msaout --consout --profile"""
+    import subprocess
+    import tempfile
+    from oracle import refcli
+    assert refcli.available(), "oracle/_ref/vsearch_ref missing: make -C oracle ref_full"
+    cases = {}
+    for seed in seeds:
+        seqs = msa_inputs(seed)
+        with tempfile.TemporaryDirectory(prefix="vsxmsa_") as tmp:
+            fa = os.path.join(tmp, "m.fa")
+            refcli.write_fasta(fa, [f"s{i:03d}" for i in range(len(seqs))], seqs)
+            subprocess.run([refcli.REF_BIN, "--cluster_fast", fa, "--id", "0.85", "--qmask", "none", "--threads", "1", "--quiet",
+                            "--uc", tmp + "/m.uc", "--msaout", tmp + "/m.msa", "--consout", tmp + "/m.cons", "--profile", tmp + "/m.prof"],
+                           check=True)
+            cases[str(seed)] = {"in": seqs, **{k: open(os.path.join(tmp, "m." + k)).read().splitlines() for k in ("uc", "msa", "cons", "prof")}}
+    doc = {"generator": "oracle/gen_golden.py gen_msa (reference CLI --cluster_fast --id 0.85 --qmask none --threads 1 "
+                        "--uc --msaout --consout --profile; sequences named s000, s001, ... in input order)", "cases": cases}
+    with open(path, "w") as f:
+        json.dump(doc, f, separators=(",", ":"))
+    print(f"wrote {path}: seeds {list(seeds)}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="write just this fixture: dust")
+    ap.add_argument("--only", default="", help="write just this fixture: dust or msa")
     ap.add_argument("--fuzz", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--no-write", action="store_true")
@@ -268,12 +306,16 @@ def main():
     if a.only == "dust":
         gen_dust(os.path.join(GOLD, "dust_golden.json"))
         return
+    if a.only == "msa":
+        gen_msa(os.path.join(GOLD, "msa_golden.json"))
+        return
     if not a.no_write:
         os.makedirs(GOLD, exist_ok=True)
         gen_search16(os.path.join(GOLD, "search16_golden.json"))
         gen_api_examples(os.path.join(GOLD, "ref_api_examples.json"))
         gen_lma(os.path.join(GOLD, "lma_golden.json"))
         gen_dust(os.path.join(GOLD, "dust_golden.json"))
+        gen_msa(os.path.join(GOLD, "msa_golden.json"))
     if a.fuzz:
         sys.exit(1 if fuzz(a.fuzz, a.seed) else 0)
 

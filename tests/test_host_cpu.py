@@ -647,3 +647,36 @@ def test_fixed_gather_overlap_accounting_and_degrade():
         fg.collect(fg.post(rec, runs), immediate=True)
         assert fg.stats()["collects"] == 4
 
+
+def test_bench_dump_outputs_fields_budget_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every field of the fetched results as float32 / float64 .npy, exact; past the byte budget a seeded
+    sample of the pairs -- the same rows on every call -- that keeps the files within it"""
+    import zlib
+    import bench
+    rng = np.random.default_rng(3)
+    n = 5000
+    cig = ["%dM%dI%dM" % (a, b, c) for a, b, c in rng.integers(1, 300, (n, 3))]
+
+    class Results:                              # the fields of vsearch_amd.aligner.AlignmentResults that the dump reads
+        score = rng.integers(-32768, 32767, n).astype(np.int16)
+        aligned, matches, mismatches, gaps = (rng.integers(0, 65535, n).astype(np.uint16) for _ in range(4))
+        cigar = cig
+
+        def __len__(self):
+            return n
+    res = Results()
+    info = bench.dump_outputs(str(tmp_path / "all"), res)
+    assert info["pairs"] == info["pairs_dumped"] == n
+    load = lambda d, k: np.load(str(tmp_path / d / (k + ".npy")))
+    for k in ("score", "aligned", "matches", "mismatches", "gaps"):
+        assert load("all", k).dtype == np.float32 and np.array_equal(load("all", k), getattr(res, k))
+    assert np.array_equal(load("all", "cigar_len"), [len(c) for c in cig])
+    assert load("all", "cigar_crc32").dtype == np.float64 and np.array_equal(load("all", "cigar_crc32"), [zlib.crc32(c.encode()) for c in cig])
+    assert np.array_equal(load("all", "pair"), np.arange(n))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40 * 1000)
+    a, b = bench.dump_outputs(str(tmp_path / "a"), res), bench.dump_outputs(str(tmp_path / "b"), res)
+    assert a["pairs_dumped"] == b["pairs_dumped"] == 1000
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) - 128 for f in a["files"]) <= 40 * 1000
+    pick = load("a", "pair").astype(np.int64)
+    assert np.array_equal(pick, load("b", "pair")) and np.all(np.diff(pick) > 0)
+    assert np.array_equal(load("a", "score"), res.score[pick]) and np.array_equal(load("a", "cigar_len"), [len(cig[i]) for i in pick])
