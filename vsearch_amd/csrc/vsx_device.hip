@@ -61,6 +61,7 @@ DEV u32 a_pk_minu(u32 a, u32 b) { u32 r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r)
 DEV u32 a_pk_mad(u32 a, u32 b, u32 c) { u32 r; asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c)); return r; }
 DEV u32 a_bfi(u32 mask, u32 a, u32 b) { u32 r; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(mask), "v"(a), "v"(b)); return r; }
 DEV u32 a_bfi_v(u32 mask, u32 a, u32 b) { u32 r; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(a), "v"(b)); return r; }
+DEV u32 a_bfi_vs(u32 mask, u32 a, u32 b) { u32 r; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(a), "s"(b)); return r; }
 DEV u32 a_lshr1(u32 a) { u32 r; asm("v_lshrrev_b32 %0, 1, %1" : "=v"(r) : "v"(a)); return r; }
 DEV u32 a_pk_ashr15(u32 a) { u32 r; asm("v_pk_ashrrev_i16 %0, 15, %1 op_sel_hi:[0,1]" : "=v"(r) : "v"(a)); return r; }
 // direction funnel: shift the accumulator right by one, drop the sign bits of d into bits 15 / 31
@@ -414,9 +415,22 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
       prefetch(0);
 
       // feed block `blk` = columns 16 blk .. 16 blk + 15 (lane l describes column 16 blk + l), built from the prefetched symbols;
-      // prefetches the symbols of the block after it
-      auto build_feed = [&](int blk) __attribute__((always_inline)) {
+      // prefetches the symbols of the block after it.  LEAN (FEED2, a block whose steps all lie before t_switch): no column of the
+      // block is a last or padded column of any target of the wave, and only phase B reads the symbols + flags and (QR_t, R_t), so
+      // the block carries the profile offsets, H and F = H - QR_t(interior) alone
+      auto build_feed = [&](int blk, auto lean_tag) __attribute__((always_inline)) {
+              constexpr bool LEAN = FEED2 && decltype(lean_tag)::value;
               const int c = 16 * blk + l;
+              if (LEAN)
+                {
+                  f_H = (s == 0) ? bpack(rawH - pad * tl) : rawS.x;
+                  f_F = (s == 0) ? vsub(f_H, qrt_i_pk) : rawS.y;
+                  const u32 f_off = PAIR ? (((rawA >> 1) - (rawA >> 3)) * 4u + ((rawB >> 1) - (rawB >> 3))) * (u32) (16 * RPP * 4)
+                                         : (rawA * (u32) (16 * RP) | ((rawB * (u32) (16 * RP)) << 16));
+                  FEED4[(blk & 1) * 64 + gw * 16 + l] = make_uint4(f_off, 0u, f_H, f_F);
+                  prefetch(blk + 1);
+                  return;
+                }
               auto mne = [&](u32 code) -> int {     // score of an unambiguous query row vs `code` when codes differ
                 const bool unamb = (code != 0) && ((code & (code - 1)) == 0);
                 return unamb ? P.mismatch : ((P.n_mismatch && code == 15) ? P.mismatch : 0);
@@ -513,7 +527,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
       };
       if (QPL)
         {
-          build_feed(0);
+          build_feed(0, std::false_type {});
           sym = dpp_shr1(FEED4[gw * 16].x, 0u);           // the symbols of step 0
           load_profile(profA, sym);
         }
@@ -525,7 +539,6 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
       // INTERIOR (phase A of the strip, see the loops below): no lane of the wave has reached a last / padded column yet, so
       // the column penalties are the interior constants (not pipelined), H - QR is shared by E and F, no score capture.
       u32 pendH = 0, pendF = 0;                    // row checkpoint of the even step, stored together with the odd step's
-      u32 jpk_run = 0;                             // the column of this lane in both halves, carried by the steady loop
       u32 pendMH = 0, pendMF = 0, curMH = 0, curMF = 0;          // the same for the mid-row checkpoint (MIDCK)
       bool pend_on = false;
       // per-lane base addresses of this strip's checkpoint regions (computed once: the step only adds a uniform offset)
@@ -561,7 +574,10 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                       auto interior_tag, auto odd_tag, auto steady_tag) __attribute__((always_inline)) {
           constexpr bool INTERIOR = decltype(interior_tag)::value;
           constexpr bool ODD = decltype(odd_tag)::value;
-          constexpr bool STEADY = decltype(steady_tag)::value;
+          // steady_tag: 0 = fill / phase B, 1 = steady, 2 = steady inside a 16-step block whose successor block is steady as well (the
+          // block loop below: the next feed block is built LEAN)
+          constexpr bool STEADY = decltype(steady_tag)::value != 0;
+          constexpr bool LEANFEED = decltype(steady_tag)::value == 2;
           u32 symn = 0;
           // PAIR: this step's packed scores, one dword per row, straight from the pair profile (`sym` = the byte offset of the pair's
           // block, as the feed delivers it); issued first, consumed a quarter at a time by the row loop below
@@ -576,8 +592,8 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                   pp[k] = v.x; pp[k + 1] = v.y; pp[k + 2] = v.z; pp[k + 3] = v.w;
                 }
             }
-          if (QPL) { if ((t & 15) == 15) build_feed((t >> 4) + 1); }      // the next block, one step early (look-ahead below)
-          else if ((t & 15) == 0) build_feed(t >> 4);
+          if (QPL) { if ((t & 15) == 15) build_feed((t >> 4) + 1, std::integral_constant<bool, LEANFEED> {}); }   // the next block, one step early (look-ahead below)
+          else if ((t & 15) == 0) build_feed(t >> 4, std::false_type {});
 
           // ---- systolic shift (all lanes, full EXEC) ----
           // feed reads: lane part (the group's 16-column row) hoisted, the step's part is uniform -- one v_add per address
@@ -721,15 +737,16 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               diag = inH;
               if (CKPT)
                 {
-                  // (the steady loop carries j in both halves along: one add per step instead of forming it from t and the lane)
-                  const u32 jpk = STEADY ? jpk_run : ((u32) j | ((u32) j << 16));
-                  if (STEADY) jpk_run += 0x00010001u;
+                  // (the steady loop tracks lv1 + l instead, i.e. the STEP t = j + l at which cont was false: t is wave-uniform, an
+                  //  SGPR operand of the select, so no per-step VALU work forms the column; the loops below convert before and after)
+                  const u32 jpk = (u32) j | ((u32) j << 16);
                   if (!INTERIOR)
                     {
                       const u32 atlast = a_pk_ashr15((FEED2 ? symf : sym) << 7);               // bit 8 (column == D-1)
                       leave = a_bfi_v(atlast, a_bfi_v(a_pk_ashr15(lastL), lv1, jpk), leave);
                     }
-                  lv1 = a_bfi_v(a_pk_ashr15((MAX3 && INTERIOR) ? lastEL : (lastL | lastEL)), lv1, jpk);
+                  const u32 lmask = a_pk_ashr15((MAX3 && INTERIOR) ? lastEL : (lastL | lastEL));
+                  lv1 = STEADY ? a_bfi_vs(lmask, lv1, (u32) t * 0x00010001u) : a_bfi_v(lmask, lv1, jpk);
                 }
 
               // per-block h_min/h_max tracking incl. padded columns (:772-773, :1774-1786), gated per half
@@ -792,12 +809,14 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                   if (TILT && !CKST)
                     {
                       // bytes 0 / 2 of the two wrapped differences = the signed 8-bit H - F of the lo / hi target, steps t-1 and t
+                      // (unrolled block: one base per block, the pair's place in it a constant -- an immediate store offset)
+                      const size_t ckp = LEANFEED ? (size_t) ((t & ~15) >> 1) * 192 + (size_t) (((t & 15) >> 1) * 192) : (size_t) (t >> 1) * 192;
                       const u32 dpk = __builtin_amdgcn_perm(psubw(outH, outF), psubw(pendH, pendF), 0x06040200u);
-                      __builtin_nontemporal_store((u32x3) {pendH + CK_REBIAS, outH + CK_REBIAS, dpk}, reinterpret_cast<u32x3 *>(rck_base + (size_t) (t >> 1) * 192));
+                      __builtin_nontemporal_store((u32x3) {pendH + CK_REBIAS, outH + CK_REBIAS, dpk}, reinterpret_cast<u32x3 *>(rck_base + ckp));
                       if (MIDCK)
                         {
                           const u32 dpm = __builtin_amdgcn_perm(psubw(curMH, curMF), psubw(pendMH, pendMF), 0x06040200u);
-                          __builtin_nontemporal_store((u32x3) {pendMH + CK_REBIAS, curMH + CK_REBIAS, dpm}, reinterpret_cast<u32x3 *>(mck_base + (size_t) (t >> 1) * 192));
+                          __builtin_nontemporal_store((u32x3) {pendMH + CK_REBIAS, curMH + CK_REBIAS, dpm}, reinterpret_cast<u32x3 *>(mck_base + ckp));
                         }
                     }
                   else
@@ -905,11 +924,29 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                                                               //  others had finished: a task with fewer than 7 of its 8 targets took 2.3 x
                                                               //  the time of a full one, profiles/r04/r04w_uniform_steps_ab.txt.  Their
                                                               //  stores land in their own, unread checkpoint slots)
-        for (jpk_run = (u32) (t - l) * 0x00010001u; t < t_switch; t += 2)
-          {
-            step(t, hprev, hnext, profA, profB, std::true_type {}, std::false_type {}, std::true_type {});
-            step(t + 1, hnext, hprev, profB, profA, std::true_type {}, std::true_type {}, std::true_type {});
-          }
+        {
+          const u32 lpk = (u32) l * 0x00010001u;
+          lv1 = psubw(lv1, psubw(0u, lpk));                   // lv1 + l per half: the steady steps track the step, not the column
+          // whole 16-step blocks whose successor block is steady too (t is a multiple of 16 here: the fill loop stops at 16 or at
+          // t_switch): every feed slot, the block-boundary work and the row checkpoint offsets are fixed per unrolled step, and the
+          // next feed block is built lean
+          for (; t + 32 <= t_switch; t += 16)
+            {
+              const int tb = t & ~15;
+#pragma unroll
+              for (int k = 0; k < 16; k += 2)
+                {
+                  step(tb + k, hprev, hnext, profA, profB, std::true_type {}, std::false_type {}, std::integral_constant<int, 2> {});
+                  step(tb + k + 1, hnext, hprev, profB, profA, std::true_type {}, std::true_type {}, std::integral_constant<int, 2> {});
+                }
+            }
+          for (; t < t_switch; t += 2)
+            {
+              step(t, hprev, hnext, profA, profB, std::true_type {}, std::false_type {}, std::true_type {});
+              step(t + 1, hnext, hprev, profB, profA, std::true_type {}, std::true_type {}, std::true_type {});
+            }
+          lv1 = psubw(lv1, lpk);
+        }
       for (; t < steps; t += 2)
         {
           step(t, hprev, hnext, profA, profB, std::false_type {}, std::false_type {}, std::false_type {});
