@@ -266,6 +266,62 @@ int vsx_msa_device_batch(vsx_ctx * ctx, uint32_t n_clusters, const uint64_t * cl
                          const char * const * seqs, const uint32_t * lens, const char * const * cigars,
                          const uint64_t * abundances /* NULL = all 1 */, vsx_msa_out * outs /* n_clusters */);
 
+/* ---- reference-based chimera detection: --uchime_ref with the default UCHIME algorithm (vsx_chimera.cpp / vsx_chimera.hip) ----
+   Per query (chimera_process_query, core/chimera.cpp:2003-2170): the query is cut into 4 parts (partition_query :1930-1955), every
+   part is searched like a --usearch_global query (id 0.55, maxaccepts 4, maxrejects 16; each part masked on its own), the ACCEPTED
+   hits of the parts -- part by part, best first, repeated targets dropped -- are the candidate parents, the whole query is aligned
+   globally with each of them, and find_best_parents (:627-751) + eval_parents (:1245-1700) pick two parents and score the query.
+   Parent selection and scoring run in one kernel (one workgroup per query) that reads the alignments' run words where the
+   traceback left them; queries above VSX_CHIMERA_MAX_QLEN, and queries with a candidate the 16-bit aligner refused (realigned with
+   vsx_lma_align), are answered by a host restatement of the same two functions.  Plus strand only (the reference refuses
+   --strand both here).  Not covered: --uchime_denovo / uchime2 / uchime3, --chimeras_denovo, --uchimealns. */
+typedef struct vsx_chimera_opts {
+  vsx_search_opts search;   /* the searcher's options: masking, hardmask, wordlength, threads, window (of the part search) and the
+                               detection parameters id = weak_id = 0.55, maxaccepts 4, maxrejects 16.  As in the reference, the
+                               query parts are searched as given: qmask dust / soft mask their lower-case symbols for the k-mers,
+                               none does not, and neither DUST nor --hardmask rewrites a query (search_onequery, chimera.cpp:2023) */
+  double  minh;             /* --minh,     default 0.28 */
+  double  mindiv;           /* --mindiv,   default 0.8  */
+  int64_t mindiffs;         /* --mindiffs, default 3    */
+  double  xn;               /* --xn,       default 8.0  */
+  double  dn;               /* --dn,       default 1.4  */
+  int64_t window;           /* queries per chimera window (parts searched, aligned and evaluated together); 0 = 16 384 */
+} vsx_chimera_opts;
+/* the defaults of src/vsearch.h:420-484 and the detection parameters of chimera_detection_parameters (chimera.cpp:2805-2824) */
+void vsx_chimera_opts_default(vsx_chimera_opts * o);
+
+#define VSX_CHIMERA_MAX_QLEN 4096   /* longest query the evaluation kernel takes (its LDS layout); longer ones: host restatement */
+
+#define VSX_CHIMERA_NO_PARENTS   0  /* fewer than two parents found: Status::no_parents                          */
+#define VSX_CHIMERA_NO_ALIGNMENT 1  /* two parents, but no column gave an h score: Status::no_alignment          */
+#define VSX_CHIMERA_SCORED       2  /* scored: flag is 'Y' (chimeric), '?' (suspicious) or 'N' (low score)        */
+/* The fields of chimera_result_s (core/chimera.hpp:72-87) with parents as database indices (UINT32_MAX = none); the caller resolves
+   labels.  Unless status == VSX_CHIMERA_SCORED the record is zero except status, flag 'N' and the parents found. */
+typedef struct vsx_chimera_result {
+  double   score;                                     /* h */
+  uint32_t parent_a, parent_b, closest;
+  int32_t  status;
+  double   id_query_model, id_query_a, id_query_b, id_a_b, id_query_top;   /* QM QA QB AB QT, percent */
+  int32_t  left_yes, left_no, left_abstain;
+  int32_t  right_yes, right_no, right_abstain;
+  double   divergence;                                /* QM - QT */
+  char     flag;                                      /* 'Y', 'N' or '?' */
+  char     pad[7];
+} vsx_chimera_result;
+
+/* n queries (ASCII) against the searcher's database; out[k] = query k.  The searcher must have been created from
+   vsx_chimera_opts_default's `search` (id = weak_id = 0.55, maxaccepts 4, maxrejects 16, plus strand): VSX_EINVAL otherwise.
+   VSX_CHIMERA=host in the environment answers every query with the host restatement (A/B, tests). */
+int vsx_uchime_ref(vsx_searcher * s, const vsx_chimera_opts * opts, uint64_t n, const char * qblob, uint64_t qbytes,
+                   const uint64_t * qoff, const uint32_t * qlen, vsx_chimera_result * out);
+/* accounting of the calling thread's last vsx_uchime_ref */
+typedef struct vsx_chimera_stats {
+  double   seconds_search, seconds_align, seconds_eval, seconds_total;   /* part search / whole-query alignment / selection + scoring */
+  uint64_t windows, parts, pairs_aligned, sentinel_pairs;
+  uint64_t queries_kernel, queries_host;              /* answered by the evaluation kernel / the host restatement */
+} vsx_chimera_stats;
+void vsx_chimera_last_stats(vsx_chimera_stats * out);
+
 /* The scalar fallback the callers run on the SHRT_MAX sentinel: LinearMemoryAligner::align + alignstats
    (core/linmemalign.cpp:694-808; call sites core/searchcore.cpp:806-832, commands/allpairs_global.cpp:447-473).
    Host CPU, int64 arithmetic, linear memory, the reference's tie-breaks; uses the UNclamped scoring values

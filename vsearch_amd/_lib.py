@@ -28,7 +28,8 @@ SEARCH_SYMBOLS = ["vsx_search_opts_default", "vsx_searcher_create", "vsx_searche
                   "vsx_hits_free", "vsx_search_candidates", "vsx_search_candidates_batch", "vsx_candidates_free", "vsx_lma_align", "vsx_allpairs_block", "vsx_allpairs_rows", "vsx_allpairs_stream", "vsx_cluster_fast", "vsx_cluster_out_free", "vsx_msa", "vsx_msa_out_free",
                   "vsx_msa_device", "vsx_msa_device_batch", "vsx_dust_mask", "vsx_abundance_ratio_cmp",
                   "vsx_multi_searcher_create", "vsx_multi_searcher_destroy", "vsx_multi_searcher_devices", "vsx_multi_searcher_replica",
-                  "vsx_multi_search_batch", "vsx_multi_allpairs"]
+                  "vsx_multi_search_batch", "vsx_multi_allpairs",
+                  "vsx_chimera_opts_default", "vsx_uchime_ref", "vsx_chimera_last_stats"]
 
 
 class Candidates(C.Structure):
@@ -52,6 +53,28 @@ class SearchOpts(C.Structure):
                 ("maxqsize", C.c_int64), ("mintsize", C.c_int64), ("minsizeratio", C.c_double), ("maxsizeratio", C.c_double),
                 ("self", C.c_int32), ("sizeorder", C.c_int32), ("cluster_unoise", C.c_int32), ("qmask", C.c_int32),
                 ("unoise_alpha", C.c_double), ("hardmask", C.c_int32)]
+
+
+class ChimeraOpts(C.Structure):
+    """vsx_chimera_opts (include/vsx_search.h): searcher options + the UCHIME scoring parameters"""
+    _fields_ = [("search", SearchOpts), ("minh", C.c_double), ("mindiv", C.c_double), ("mindiffs", C.c_int64),
+                ("xn", C.c_double), ("dn", C.c_double), ("window", C.c_int64)]
+
+
+class ChimeraResult(C.Structure):
+    """vsx_chimera_result (include/vsx_search.h): one query's chimera_result_s with parents as database indices"""
+    _fields_ = [("score", C.c_double), ("parent_a", C.c_uint32), ("parent_b", C.c_uint32), ("closest", C.c_uint32),
+                ("status", C.c_int32), ("id_query_model", C.c_double), ("id_query_a", C.c_double), ("id_query_b", C.c_double),
+                ("id_a_b", C.c_double), ("id_query_top", C.c_double), ("left_yes", C.c_int32), ("left_no", C.c_int32),
+                ("left_abstain", C.c_int32), ("right_yes", C.c_int32), ("right_no", C.c_int32), ("right_abstain", C.c_int32),
+                ("divergence", C.c_double), ("flag", C.c_char), ("pad", C.c_char * 7)]
+
+
+class ChimeraStats(C.Structure):
+    """vsx_chimera_stats (include/vsx_search.h)"""
+    _fields_ = [("seconds_search", C.c_double), ("seconds_align", C.c_double), ("seconds_eval", C.c_double),
+                ("seconds_total", C.c_double), ("windows", C.c_uint64), ("parts", C.c_uint64), ("pairs_aligned", C.c_uint64),
+                ("sentinel_pairs", C.c_uint64), ("queries_kernel", C.c_uint64), ("queries_host", C.c_uint64)]
 
 
 class SeqMeta(C.Structure):

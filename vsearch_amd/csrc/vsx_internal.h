@@ -132,9 +132,27 @@ struct VsxRankedOut {
   uint64_t * text_off;
 };
 
+// vsx_chimera.hip: one query of the evaluation kernel -- its whole-query alignments against cand[0 .. ncand) are plan pairs
+// pair0 .. pair0 + ncand - 1 (hit records + run words exported from the plan)
+#define VSX_CHIM_MAXCAND 16
+struct VsxChimItem {
+  uint32_t q;                        // index in the query set
+  uint32_t ncand;
+  uint32_t pair0;
+  uint32_t out;                      // index of its result record
+  uint32_t cand[VSX_CHIM_MAXCAND];   // database indices
+};
+struct VsxChimParams { double minh, mindiv, xn, dn; int64_t mindiffs; };
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+// vsx_chimera.hip: find_best_parents + eval_parents per item; out is indexed by item.out (struct vsx_chimera_result, include/vsx_search.h)
+hipError_t vsx_launch_chimera_eval(const VsxChimItem * d_items, uint32_t nitems, const uint8_t * qcodes, const uint64_t * qoff,
+                                   const uint32_t * qlen, const uint8_t * tcodes, const uint64_t * toff, const uint32_t * tlen,
+                                   const VsxPairOut * d_hits, const uint32_t * d_runs, uint64_t n_runs, VsxChimParams P,
+                                   void * d_out, hipStream_t st);
 
 // vsx_rank.hip: keep flags + identities + exclusive scan (d_temp == NULL: only *temp_bytes is set) ...
 hipError_t vsx_rank_gather_list(const uint32_t * d_kept_pair, const double * d_kept_id, uint32_t kept, const VsxPairOut * d_out,

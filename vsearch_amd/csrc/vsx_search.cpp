@@ -1254,8 +1254,11 @@ int vsx_search_batch(vsx_searcher * S, uint64_t nq, const char * qblob, uint64_t
   return vsx_search_batch_meta(S, nq, qblob, qbytes, qoff, qlen, nullptr, out);
 }
 
+// raw_queries: the queries are searched as given -- no DUST, no --hardmask of the query text; only the k-mer stage's lower-case
+// masking applies (every mode but none).  That is search_onequery called directly, as chimera detection does for its query parts
+// (core/chimera.cpp:2023): the query-side masking of --usearch_global lives in search_query (search.cpp:294-303), which it skips.
 static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, uint64_t qbytes, const uint64_t * qoff,
-                             const uint32_t * qlen, const vsx_seq_meta * qmeta, vsx_hits * out);
+                             const uint32_t * qlen, const vsx_seq_meta * qmeta, vsx_hits * out, bool raw_queries = false);
 int vsx_search_batch_meta(vsx_searcher * S, uint64_t nq, const char * qblob, uint64_t qbytes, const uint64_t * qoff,
                           const uint32_t * qlen, const vsx_seq_meta * qmeta, vsx_hits * out)
 {
@@ -1269,7 +1272,7 @@ int vsx_search_batch_meta(vsx_searcher * S, uint64_t nq, const char * qblob, uin
   return rc;
 }
 static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, uint64_t qbytes, const uint64_t * qoff,
-                             const uint32_t * qlen, const vsx_seq_meta * qmeta, vsx_hits * out)
+                             const uint32_t * qlen, const vsx_seq_meta * qmeta, vsx_hits * out, bool raw_queries)
 {
   if (!S || !out || (nq && (!qblob || !qoff || !qlen))) return sfail(VSX_EINVAL, "vsx_search_batch: null argument");
   std::memset(out, 0, sizeof *out);
@@ -1332,10 +1335,10 @@ static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, 
   // does any host step read a minus-strand query as text? (host k-mer path; idprefix / idsuffix / selfid compare symbols;
   // the '*' penalties send every pair to the linear-memory aligner; VSX_RC_TEXT=1 forces it for tests)
   static const bool rc_text_env = std::getenv("VSX_RC_TEXT") != nullptr;
-  const bool dust = S->qmode == 2;                // every strand of every query is DUST-masked on its own (search.cpp:294-303)
+  const bool dust = S->qmode == 2 && !raw_queries;                // every strand of every query is DUST-masked on its own (search.cpp:294-303)
   // r06, --hardmask on the queries (search.cpp:294-303): the masked symbols of each strand become 'N' in the text the k-mer stage AND the
   // aligner read -- the window's strands then exist as (masked) text, which is what the device set is made from
-  const bool hardq = (S->o.hardmask & 2) != 0 && S->qmode != 0;
+  const bool hardq = (S->o.hardmask & 2) != 0 && S->qmode != 0 && !raw_queries;
   const bool per_strand = dust || hardq;          // every strand's words come from its own masked text
   const bool need_rc_text = both && (!dev_kmer || S->o.idprefix > 0 || S->o.idsuffix > 0 || S->o.selfid != 0 || S->o.gap_infinite != 0 || rc_text_env || per_strand);
 
@@ -2726,6 +2729,27 @@ void vsx_hits_free(vsx_hits * h)
   if (!h) return;
   std::free(h->first); std::free(h->hit); std::free(h->cigar_blob);
   std::memset(h, 0, sizeof *h);
+}
+
+// what vsx_chimera.cpp reads of a searcher: its context, options (weak_id clamped), unclamped scoring, database set and masked text
+vsx_ctx * vsx_internal_searcher_ctx(const vsx_searcher * S) { return S->ctx; }
+const vsx_search_opts * vsx_internal_searcher_opts(const vsx_searcher * S) { return &S->o; }
+const vsx_scoring * vsx_internal_searcher_scoring(const vsx_searcher * S) { return &S->scoring; }
+const vsx_seqset * vsx_internal_searcher_dbset(const vsx_searcher * S) { return S->dbset; }
+// chimera detection's part search (vsx_chimera.cpp): the parts searched as given (raw_queries above) with candidate heaps of `tophits`
+// entries -- chimera_thread_core sizes them maxaccepts + maxrejects (chimera.cpp:2180-2182), --usearch_global adds MAXDELAYED.  The
+// searcher's own heap size is restored before returning: the handle behaves as before for every later call.
+int vsx_internal_search_parts(vsx_searcher * S, int64_t tophits, uint64_t nq, const char * qblob, uint64_t qbytes, const uint64_t * qoff,
+                              const uint32_t * qlen, vsx_hits * out)
+{
+  if (!S) return sfail(VSX_EINVAL, "vsx_internal_search_parts: null searcher");
+  struct Restore { vsx_searcher * S; int64_t v; ~Restore() { S->tophits = v; } } restore {S, S->tophits};
+  S->tophits = std::min<int64_t>(tophits, (int64_t) S->len.size());
+  return search_batch_impl(S, nq, qblob, qbytes, qoff, qlen, nullptr, out, true);
+}
+void vsx_internal_searcher_text(const vsx_searcher * S, const char ** blob, const uint64_t ** off, const uint32_t ** len)
+{
+  *blob = S->blob.data(); *off = S->off.data(); *len = S->len.data();
 }
 
 }  // extern "C"
