@@ -274,7 +274,8 @@ int vsx_msa_device_batch(vsx_ctx * ctx, uint32_t n_clusters, const uint64_t * cl
    Parent selection and scoring run in one kernel (one workgroup per query) that reads the alignments' run words where the
    traceback left them; queries above VSX_CHIMERA_MAX_QLEN, and queries with a candidate the 16-bit aligner refused (realigned with
    vsx_lma_align), are answered by a host restatement of the same two functions.  Plus strand only (the reference refuses
-   --strand both here).  Not covered: --uchime_denovo / uchime2 / uchime3, --chimeras_denovo, --uchimealns. */
+   --strand both here).  The de novo forms (--uchime_denovo / uchime2 / uchime3) are vsx_uchime_denovo below.  Not covered:
+   --chimeras_denovo, --uchimealns. */
 typedef struct vsx_chimera_opts {
   vsx_search_opts search;   /* the searcher's options: masking, hardmask, wordlength, threads, window (of the part search) and the
                                detection parameters id = weak_id = 0.55, maxaccepts 4, maxrejects 16.  As in the reference, the
@@ -321,6 +322,45 @@ typedef struct vsx_chimera_stats {
   uint64_t queries_kernel, queries_host;              /* answered by the evaluation kernel / the host restatement */
 } vsx_chimera_stats;
 void vsx_chimera_last_stats(vsx_chimera_stats * out);
+
+/* ---- de novo chimera detection: --uchime_denovo, --uchime2_denovo, --uchime3_denovo (vsx_chimera.cpp) ----
+   The searcher's own sequences are both the queries and the database, processed IN THE GIVEN ORDER: sort them first as
+   Database::sortbyabundance does (abundance descending, then strcmp of the header, then input order; core/db.cpp:471-485) and mask
+   them through the searcher's soft_mask / hardmask the way --qmask / --hardmask mask the de novo input (chimera.cpp:2546-2555).
+   Abundances and labels come from vsx_searcher_set_meta (abundances are required; labels drive --self).  Query i is searched
+   against the sequences before it that were neither chimeric nor borderline (chimera.cpp:2365-2372), with the detection
+   parameters plus self = selfid = 1 and maxsizeratio = 1 / abskew (a candidate less than abskew times as abundant as the query is
+   rejected unaligned, and still takes a slot of the candidate loop).  The verdict is the UCHIME rule for variant 1 and, for
+   variants 2 and 3, 'Y' iff the model matches the query on every column and the closest parent does not (chimera.cpp:1633-1640).
+   The queries run in windows (base.window, 0 = 4 096) of speculative passes with an in-order fix-up; the result does not depend
+   on the window.  Word lengths 3..8 only (the growing index is a pair of device subset indexes); plus strand only. */
+typedef struct vsx_chimera_denovo_opts {
+  vsx_chimera_opts base;    /* minh, mindiv, mindiffs, xn, dn, window (queries per speculative window) and the searcher's options */
+  int32_t variant;          /* 1 = --uchime_denovo, 2 = --uchime2_denovo, 3 = --uchime3_denovo */
+  double  abskew;           /* >= 1.0 */
+} vsx_chimera_denovo_opts;
+/* vsx_chimera_opts_default + abskew 2 / 2 / 16 (cli.cc:4478-4492), search.self = search.selfid = 1 and
+   search.maxsizeratio = 1 / abskew (chimera_detection_parameters, chimera.cpp:2805-2824) */
+void vsx_chimera_denovo_opts_default(vsx_chimera_denovo_opts * o, int32_t variant);
+/* out[k] = the searcher's sequence k (one record per sequence).  VSX_EINVAL: a searcher not created with the options above
+   (maxsizeratio must equal 1 / abskew), --strand both, no abundances, a word length above 8, a variant outside 1..3, abskew < 1.
+   VSX_CHIMERA=host answers every query with the host restatement. */
+int vsx_uchime_denovo(vsx_searcher * s, const vsx_chimera_denovo_opts * opts, vsx_chimera_result * out);
+/* accounting of the calling thread's last vsx_uchime_denovo */
+typedef struct vsx_chimera_denovo_stats {
+  double   seconds_rank;                /* parts ranked against the committed non-chimeras (device main + delta indexes) */
+  double   seconds_members;             /* parts counted against the window's own members (device window index) */
+  double   seconds_search;              /* staged accept / reject replay of the parts */
+  double   seconds_align;               /* whole queries against their candidate parents */
+  double   seconds_eval;                /* parent selection + scoring (kernel and host restatement) */
+  double   seconds_reconcile;           /* merging the candidate lists, in-order validation */
+  double   seconds_total;
+  uint64_t windows, passes, passes_max; /* passes over all windows, and the most of one window */
+  uint64_t queries_reevaluated;         /* queries searched and evaluated more than once */
+  uint64_t parts, pairs_searched, pairs_aligned, sentinel_pairs;   /* part-target pairs of the search, whole-query pairs */
+  uint64_t queries_kernel, queries_host;                           /* evaluations by the kernel / the host restatement */
+} vsx_chimera_denovo_stats;
+void vsx_chimera_denovo_last_stats(vsx_chimera_denovo_stats * out);
 
 /* The scalar fallback the callers run on the SHRT_MAX sentinel: LinearMemoryAligner::align + alignstats
    (core/linmemalign.cpp:694-808; call sites core/searchcore.cpp:806-832, commands/allpairs_global.cpp:447-473).

@@ -29,7 +29,8 @@ SEARCH_SYMBOLS = ["vsx_search_opts_default", "vsx_searcher_create", "vsx_searche
                   "vsx_msa_device", "vsx_msa_device_batch", "vsx_dust_mask", "vsx_abundance_ratio_cmp",
                   "vsx_multi_searcher_create", "vsx_multi_searcher_destroy", "vsx_multi_searcher_devices", "vsx_multi_searcher_replica",
                   "vsx_multi_search_batch", "vsx_multi_allpairs",
-                  "vsx_chimera_opts_default", "vsx_uchime_ref", "vsx_chimera_last_stats"]
+                  "vsx_chimera_opts_default", "vsx_uchime_ref", "vsx_chimera_last_stats",
+                  "vsx_chimera_denovo_opts_default", "vsx_uchime_denovo", "vsx_chimera_denovo_last_stats"]
 
 
 class Candidates(C.Structure):
@@ -75,6 +76,21 @@ class ChimeraStats(C.Structure):
     _fields_ = [("seconds_search", C.c_double), ("seconds_align", C.c_double), ("seconds_eval", C.c_double),
                 ("seconds_total", C.c_double), ("windows", C.c_uint64), ("parts", C.c_uint64), ("pairs_aligned", C.c_uint64),
                 ("sentinel_pairs", C.c_uint64), ("queries_kernel", C.c_uint64), ("queries_host", C.c_uint64)]
+
+
+class ChimeraDenovoOpts(C.Structure):
+    """vsx_chimera_denovo_opts (include/vsx_search.h): vsx_chimera_opts + variant (1 uchime, 2 uchime2, 3 uchime3) + abskew"""
+    _fields_ = [("base", ChimeraOpts), ("variant", C.c_int32), ("abskew", C.c_double)]
+
+
+class ChimeraDenovoStats(C.Structure):
+    """vsx_chimera_denovo_stats (include/vsx_search.h)"""
+    _fields_ = [("seconds_rank", C.c_double), ("seconds_members", C.c_double), ("seconds_search", C.c_double),
+                ("seconds_align", C.c_double), ("seconds_eval", C.c_double), ("seconds_reconcile", C.c_double),
+                ("seconds_total", C.c_double), ("windows", C.c_uint64), ("passes", C.c_uint64), ("passes_max", C.c_uint64),
+                ("queries_reevaluated", C.c_uint64), ("parts", C.c_uint64), ("pairs_searched", C.c_uint64),
+                ("pairs_aligned", C.c_uint64), ("sentinel_pairs", C.c_uint64), ("queries_kernel", C.c_uint64),
+                ("queries_host", C.c_uint64)]
 
 
 class SeqMeta(C.Structure):

@@ -1,8 +1,12 @@
-"""Reference-based chimera detection (--uchime_ref, default UCHIME algorithm) over include/vsx_search.h vsx_uchime_ref.
+"""Chimera detection (UCHIME) over include/vsx_search.h: reference-based (vsx_uchime_ref) and de novo (vsx_uchime_denovo).
 
     ChimeraSession(aligner, db, labels=None, **opts)     ~ chimera() with --uchime_ref --db (core/chimera.cpp)
     .uchime_ref(queries) -> per-query dicts (the fields of chimera_result_s, parents as database indices or None)
     .uchimeout(queries, qnames, tnames) -> the --uchimeout lines, byte for byte
+
+    DenovoChimeraSession(aligner, seqs, labels, variant="uchime", **opts)   ~ --uchime_denovo / --uchime2_denovo / --uchime3_denovo
+    .uchime_denovo() -> per-sequence dicts in processing order (abundance-sorted); .order[k] = input index of record k
+    .uchimeout() -> the --uchimeout lines in processing order;  .nonchimeras() -> input indices of the non-chimeras
 
 Options: minh, mindiv, mindiffs, xn, dn (the UCHIME parameters) and the searcher's soft_mask (--dbmask: 0 none, 1 soft, 2 dust =
 default), qmask (--qmask when it differs: 1 + mode), hardmask, wordlength, threads, window (queries per chimera window) and
@@ -10,8 +14,8 @@ search_window (queries per window of the part search)."""
 import ctypes as C
 
 from . import _lib
-from ._lib import ChimeraOpts, ChimeraResult, ChimeraStats, check
-from .search import _blob
+from ._lib import ChimeraDenovoOpts, ChimeraDenovoStats, ChimeraOpts, ChimeraResult, ChimeraStats, check
+from .search import _blob, _meta
 
 NONE = 0xFFFFFFFF
 STATUS = {0: "no_parents", 1: "no_alignment", 2: "scored"}
@@ -105,3 +109,148 @@ class ChimeraSession:
         qnames = qnames or [f"q{i}" for i in range(len(queries))]
         tnames = tnames or self.labels or [f"t{i}" for i in range(len(self.db))]
         return [format_uchimeout(r, qn, tnames) for r, qn in zip(records, qnames)]
+
+
+def _records(out, n):
+    recs = []
+    for k in range(n):
+        r = out[k]
+        d = {nm: getattr(r, nm) for nm, _ in ChimeraResult._fields_ if nm != "pad"}
+        for p in ("parent_a", "parent_b", "closest"):
+            d[p] = None if d[p] == NONE else int(d[p])
+        d["status"] = STATUS[d["status"]]
+        d["flag"] = d["flag"].decode()
+        recs.append(d)
+    return recs
+
+
+VARIANTS = {"uchime": 1, "uchime2": 2, "uchime3": 3}
+MASK_MODES = {"none": 0, "soft": 1, "dust": 2}
+
+
+def header_size(label):
+    """the abundance of a FASTA header as header_get_size reads it (core/attributes.cpp:98-188): the first (^|;)size=DIGITS(;|$),
+    found with the reference's own scan; 1 when there is none (Database::read)"""
+    h = label.encode() if isinstance(label, str) else bytes(label)
+    att, n, off = b"size=", len(h), 0
+    while off < n - len(att):
+        i = h.find(att, off)
+        if i < 0:
+            break
+        off = i
+        if off > 0 and h[off - 1:off] != b";":
+            off += len(att) + 1
+            continue
+        d = 0
+        while off + len(att) + d < n and h[off + len(att) + d] in b"0123456789":
+            d += 1
+        if d == 0:
+            off += len(att) + 1
+            continue
+        if off + len(att) + d < n and h[off + len(att) + d:off + len(att) + d + 1] != b";":
+            off += len(att) + d + 2
+            continue
+        v = int(h[off + len(att):off + len(att) + d])
+        if v == 0:
+            raise ValueError(f"invalid (zero) abundance annotation in header {label!r}")
+        return v
+    return 1
+
+
+def sort_by_abundance(sizes, labels):
+    """Database::sortbyabundance (core/db.cpp:471-485): abundance descending, then the header (strcmp: bytes), then input order"""
+    keys = [l.encode() if isinstance(l, str) else bytes(l) for l in labels]
+    return sorted(range(len(labels)), key=lambda i: (-sizes[i], keys[i], i))
+
+
+def denovo_default_opts(variant="uchime"):
+    """vsx_chimera_denovo_opts_default as a ChimeraDenovoOpts structure"""
+    o = ChimeraDenovoOpts()
+    _lib.load().vsx_chimera_denovo_opts_default(C.byref(o), VARIANTS[variant])
+    return o
+
+
+class DenovoChimeraSession:
+    """--uchime_denovo / --uchime2_denovo / --uchime3_denovo of one set of sequences.  Sequences shorter than minseqlength (1) or
+    longer than maxseqlength (50 000) are dropped as Database::read drops them; the rest are sorted like sortbyabundance.
+    Options as ChimeraSession: minh, mindiv, mindiffs, xn, dn, window (sequences per speculative window), soft_mask (the --qmask
+    mode of the de novo input: 0 none, 1 soft, 2 dust = default, or its name), hardmask (1: --hardmask), wordlength (3..8),
+    minwordmatches, threads, search_window; plus abskew (default 2, uchime3 16)."""
+
+    def __init__(self, aligner, seqs, labels, variant="uchime", minseqlength=1, maxseqlength=50000, **opts):
+        lib = _lib.load()
+        if variant not in VARIANTS:
+            raise ValueError(f"variant must be one of {sorted(VARIANTS)}")
+        if len(labels) != len(seqs):
+            raise ValueError("labels: one header per sequence")
+        self.aligner = aligner
+        aligner._children.add(self)
+        o = denovo_default_opts(variant)
+        for k, v in opts.items():
+            if k == "soft_mask" and isinstance(v, str):
+                v = MASK_MODES[v]
+            if k in _SEARCH_KEYS:
+                setattr(o.base.search, k, v)
+            elif k == "search_window":
+                o.base.search.window = v
+            elif k in ("minh", "mindiv", "mindiffs", "xn", "dn", "window"):
+                setattr(o.base, k, v)
+            elif k == "abskew":
+                o.abskew = v
+                o.base.search.maxsizeratio = 1.0 / v
+            else:
+                raise TypeError(f"unknown chimera option {k}")
+        self.opts = o
+        keep = [i for i, s in enumerate(seqs) if minseqlength <= len(s) <= maxseqlength]
+        sizes = {i: header_size(labels[i]) for i in keep}
+        kl = [labels[i] for i in keep]
+        self.order = [keep[j] for j in sort_by_abundance([sizes[i] for i in keep], kl)]
+        self.seqs = [seqs[i] for i in self.order]
+        self.labels = [labels[i] for i in self.order]
+        self.sizes = [sizes[i] for i in self.order]
+        blob, off, lens = _blob(self.seqs)
+        self._keep = (blob, off, lens)
+        self.h = C.c_void_p()
+        check(lib.vsx_searcher_create(aligner.h, C.byref(self.h), C.byref(o.base.search), len(lens),
+                                      C.cast(C.c_char_p(blob), C.c_void_p), len(blob),
+                                      off.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p)),
+              "vsx_searcher_create")
+        m, self._meta_keep = _meta(self.sizes, self.labels, len(lens))
+        check(lib.vsx_searcher_set_meta(self.h, C.byref(m)), "vsx_searcher_set_meta")
+        self.stats = {}
+        self._records = None
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            _lib.load().vsx_searcher_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def uchime_denovo(self):
+        """one dict per sequence in processing order (the fields of uchime_ref's records; parents as processing-order indices)"""
+        lib = _lib.load()
+        n = len(self.seqs)
+        out = (ChimeraResult * max(n, 1))()
+        check(lib.vsx_uchime_denovo(self.h, C.byref(self.opts), out), "vsx_uchime_denovo")
+        st = ChimeraDenovoStats()
+        lib.vsx_chimera_denovo_last_stats(C.byref(st))
+        self.stats = {k: getattr(st, k) for k, _ in ChimeraDenovoStats._fields_}
+        self._records = _records(out, n)
+        return self._records
+
+    def uchimeout(self, records=None):
+        """--uchimeout lines in processing order (what the reference CLI writes)"""
+        if records is None:
+            records = self._records if self._records is not None else self.uchime_denovo()
+        return [format_uchimeout(r, qn, self.labels) for r, qn in zip(records, self.labels)]
+
+    def nonchimeras(self, records=None):
+        """input indices of the sequences whose status is below suspicious (neither 'Y' nor '?'), in processing order"""
+        if records is None:
+            records = self._records if self._records is not None else self.uchime_denovo()
+        return [self.order[k] for k, r in enumerate(records) if r["flag"] == "N"]

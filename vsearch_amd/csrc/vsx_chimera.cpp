@@ -1,4 +1,6 @@
-// vsx_chimera.cpp -- --uchime_ref dispatch (include/vsx_search.h vsx_uchime_ref) and the host restatement of its selection and scoring.
+// vsx_chimera.cpp -- --uchime_ref and de novo chimera dispatch (include/vsx_search.h vsx_uchime_ref, vsx_uchime_denovo) and the host
+// restatement of the selection and scoring.  The de novo loop (denovo_window below) reuses steps 4-5; its part search lives in
+// vsx_search.cpp (vsx_internal_denovo_*).
 //
 // chimera_process_query (reference core/chimera.cpp:2003-2170) for a WINDOW of queries at a time:
 //   1. partition_query (:1930-1955): 4 parts per query of length >= 4 -- offsets into the caller's blob, nothing is copied
@@ -291,7 +293,11 @@ void vsx_internal_chimera_eval_host(const uint8_t * q, int L, int nc, const uint
   r->right_yes = best_right_y; r->right_no = best_right_n; r->right_abstain = best_right_a;
   r->divergence = divdiff;
   r->flag = 'N';
-  if (best_h >= P.minh)
+  if (P.variant >= 2)
+    {
+      if ((match_QM == cols) && (QT < 100.0)) r->flag = 'Y';     // uchime2 / uchime3 (:1633-1640): a perfect model, no '?'
+    }
+  else if (best_h >= P.minh)
     {
       r->flag = '?';
       if ((divdiff >= P.mindiv) && (sumL >= P.mindiffs) && (sumR >= P.mindiffs)) r->flag = 'Y';
@@ -300,7 +306,7 @@ void vsx_internal_chimera_eval_host(const uint8_t * q, int L, int nc, const uint
 
 namespace {
 
-// device buffers of one vsx_uchime_ref call, grown as windows need them (a hipFree synchronises the whole device)
+// device buffers of one call, grown as windows need them (a hipFree synchronises the whole device)
 template <class T>
 struct GrowBuf {
   T * p = nullptr;
@@ -323,11 +329,24 @@ struct CallBufs {
   GrowBuf<vsx_chimera_result> out;
 };
 
-#define CHIP(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return cfail(VSX_EHIP, std::string("vsx_uchime_ref: ") + hipGetErrorString(e_)); } while (0)
+// one query of steps 4-5: its index in the query set of the plan, its text, its candidate parents and where its record goes
+struct EvalJob {
+  uint32_t q;
+  const char * text;
+  uint32_t len;
+  uint32_t ncand;
+  const uint32_t * cand;
+  vsx_chimera_result * out;
+};
+struct EvalAcct { double t_align = 0, t_eval = 0; uint64_t pairs = 0, sentinels = 0, kernel = 0, host = 0; };
 
-// one window: queries [w0, w0 + nw) of the call
-int run_window(vsx_searcher * S, const vsx_chimera_opts & O, CallBufs & B, bool host_all, uint64_t w0, uint64_t nw, const char * qblob, uint64_t qbytes,
-               const uint64_t * qoff, const uint32_t * qlen, vsx_chimera_result * out)
+#define CHIP(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return cfail(VSX_EHIP, std::string(who) + ": " + hipGetErrorString(e_)); } while (0)
+
+// 4. whole queries against their candidates: one plan of (job.q in qset, candidate in the database set) pairs; 5. selection + scoring
+// on the kernel, or on the host restatement (long query, sentinel pair, host_all).  A job with < 2 candidates, or shorter than the
+// 32-column window, cannot get two parents and is answered at once.
+int align_and_eval(vsx_searcher * S, const VsxChimParams & P, CallBufs & B, bool host_all, const vsx_seqset * qset,
+                   const std::vector<EvalJob> & jobs, EvalAcct & A, const char * who)
 {
   vsx_ctx * ctx = vsx_internal_searcher_ctx(S);
   const vsx_seqset * dbset = vsx_internal_searcher_dbset(S);
@@ -335,74 +354,22 @@ int run_window(vsx_searcher * S, const vsx_chimera_opts & O, CallBufs & B, bool 
   const uint64_t * dboff;
   const uint32_t * dblen;
   vsx_internal_searcher_text(S, &dbtext, &dboff, &dblen);
-  const VsxChimParams P {O.minh, O.mindiv, O.xn, O.dn, O.mindiffs};
-  const vsx_search_opts & so = *vsx_internal_searcher_opts(S);
-
-  // 1-2. parts through the window search
-  double t0 = now_s();
-  std::vector<uint64_t> poff;
-  std::vector<uint32_t> plen, pquery;
-  for (uint64_t k = 0; k < nw; ++k)
-    {
-      const uint32_t L = qlen[w0 + k];
-      if (L < (uint32_t) kParts) continue;
-      uint32_t rest = L;
-      uint64_t cur = qoff[w0 + k];
-      for (int i = 0; i < kParts; ++i)
-        {
-          const uint32_t length = (rest + (uint32_t) (kParts - i - 1)) / (uint32_t) (kParts - i);
-          poff.push_back(cur);
-          plen.push_back(length);
-          pquery.push_back((uint32_t) k);
-          rest -= length;
-          cur += length;
-        }
-    }
-  std::vector<uint32_t> ncand(nw, 0), cand(nw * VSX_CHIM_MAXCAND, 0);
-  if (!poff.empty())
-    {
-      vsx_hits H {};
-      const int rc = vsx_internal_search_parts(S, so.maxaccepts + so.maxrejects, poff.size(), qblob, qbytes, poff.data(), plen.data(), &H);
-      if (rc != VSX_OK) return rc;
-      // 3. accepted hits part by part, best first; repeated targets dropped
-      for (uint64_t p = 0; p < poff.size(); ++p)
-        {
-          const uint32_t k = pquery[p];
-          uint32_t * c = &cand[(size_t) k * VSX_CHIM_MAXCAND];
-          for (uint64_t h = H.first[p]; h < H.first[p + 1]; ++h)
-            {
-              if (!H.hit[h].accepted) continue;
-              const uint32_t tg = H.hit[h].target;
-              if (std::find(c, c + ncand[k], tg) == c + ncand[k] && ncand[k] < VSX_CHIM_MAXCAND) c[ncand[k]++] = tg;
-            }
-        }
-      g_stats.parts += poff.size();
-      vsx_hits_free(&H);
-    }
   const double t1 = now_s();
-  g_stats.seconds_search += t1 - t0;
-
-  // 4. whole queries against their candidates: one plan for the window
-  std::vector<uint32_t> qidx, tidx, pair0(nw, 0);
-  std::vector<uint64_t> woff(nw);
-  std::string wblob;
-  for (uint64_t k = 0; k < nw; ++k)
+  const size_t nj = jobs.size();
+  std::vector<uint32_t> qidx, tidx, pair0(nj, 0);
+  std::vector<bool> scored(nj, false);
+  for (size_t k = 0; k < nj; ++k)
     {
-      woff[k] = wblob.size();
-      wblob.append(qblob + qoff[w0 + k], qlen[w0 + k]);
-      if (ncand[k] < 2 || qlen[w0 + k] < (uint32_t) kWindow) continue;        // no two parents possible
+      const EvalJob & j = jobs[k];
+      if (j.ncand < 2 || j.len < (uint32_t) kWindow) { unscored(j.out, VSX_CHIMERA_NO_PARENTS, kNone, kNone); continue; }
+      scored[k] = true;
       pair0[k] = (uint32_t) qidx.size();
-      for (uint32_t c = 0; c < ncand[k]; ++c) { qidx.push_back((uint32_t) k); tidx.push_back(cand[(size_t) k * VSX_CHIM_MAXCAND + c]); }
+      for (uint32_t c = 0; c < j.ncand; ++c) { qidx.push_back(j.q); tidx.push_back(j.cand[c]); }
     }
-  for (uint64_t k = 0; k < nw; ++k)
-    if (ncand[k] < 2 || qlen[w0 + k] < (uint32_t) kWindow) unscored(&out[w0 + k], VSX_CHIMERA_NO_PARENTS, kNone, kNone);
   if (qidx.empty()) return VSX_OK;
 
-  vsx_seqset * qs = nullptr;
-  int rc = vsx_seqset_create(ctx, &qs, nw, wblob.data(), wblob.size(), woff.data(), qlen + w0);
-  if (rc != VSX_OK) return rc;
-  struct Guard { vsx_seqset * s; vsx_plan * p = nullptr; ~Guard() { vsx_plan_destroy(p); vsx_seqset_destroy(s); } } g {qs};
-  rc = vsx_plan_create(ctx, &g.p, qs, dbset, qidx.size(), qidx.data(), tidx.data(), 0);
+  struct Guard { vsx_plan * p = nullptr; ~Guard() { vsx_plan_destroy(p); } } g;
+  int rc = vsx_plan_create(ctx, &g.p, qset, dbset, qidx.size(), qidx.data(), tidx.data(), 0);
   if (rc == VSX_OK) rc = vsx_plan_run(g.p);
   if (rc == VSX_OK) rc = vsx_plan_sync(g.p, nullptr);
   if (rc != VSX_OK) return rc;
@@ -430,32 +397,34 @@ int run_window(vsx_searcher * S, const vsx_chimera_opts & O, CallBufs & B, bool 
   std::vector<VsxPairOut> h_hits(npairs);
   CHIP(hipMemcpy(h_hits.data(), d_hits.p, npairs * sizeof(VsxPairOut), hipMemcpyDeviceToHost));
   const double t2 = now_s();
-  g_stats.seconds_align += t2 - t1;
-  g_stats.pairs_aligned += npairs;
+  A.t_align += t2 - t1;
+  A.pairs += npairs;
 
   // every run list the evaluation reads must lie inside the exported buffer: checked here for both routes, so that a bad export
   // fails the call the same way whichever route a query takes (the kernel's own bound check only keeps it inside the buffer)
   for (uint64_t p = 0; p < npairs; ++p)
     if (h_hits[p].score != VSX_SCORE_SENTINEL && h_hits[p].run_off + h_hits[p].nruns > nruns)
-      return cfail(VSX_EHIP, "vsx_uchime_ref: run words out of range");
+      return cfail(VSX_EHIP, std::string(who) + ": run words out of range");
 
   // 5. route: kernel, or host restatement (long query, sentinel pair, VSX_CHIMERA=host)
   std::vector<VsxChimItem> items;
-  std::vector<uint64_t> host_q;
-  for (uint64_t k = 0; k < nw; ++k)
+  std::vector<size_t> item_job, host_q;
+  for (size_t k = 0; k < nj; ++k)
     {
-      if (ncand[k] < 2 || qlen[w0 + k] < (uint32_t) kWindow) continue;
+      if (!scored[k]) continue;
+      const EvalJob & j = jobs[k];
       bool sentinel = false;
-      for (uint32_t c = 0; c < ncand[k]; ++c)
-        if (h_hits[pair0[k] + c].score == VSX_SCORE_SENTINEL) { sentinel = true; ++g_stats.sentinel_pairs; }
-      if (host_all || sentinel || qlen[w0 + k] > VSX_CHIMERA_MAX_QLEN) { host_q.push_back(k); continue; }
+      for (uint32_t c = 0; c < j.ncand; ++c)
+        if (h_hits[pair0[k] + c].score == VSX_SCORE_SENTINEL) { sentinel = true; ++A.sentinels; }
+      if (host_all || sentinel || j.len > VSX_CHIMERA_MAX_QLEN) { host_q.push_back(k); continue; }
       VsxChimItem it {};
-      it.q = (uint32_t) k;
-      it.ncand = ncand[k];
+      it.q = j.q;
+      it.ncand = j.ncand;
       it.pair0 = pair0[k];
       it.out = (uint32_t) items.size();
-      std::copy(&cand[(size_t) k * VSX_CHIM_MAXCAND], &cand[(size_t) k * VSX_CHIM_MAXCAND] + VSX_CHIM_MAXCAND, it.cand);
+      std::copy(j.cand, j.cand + j.ncand, it.cand);
       items.push_back(it);
+      item_job.push_back(k);
     }
   if (!items.empty())
     {
@@ -463,7 +432,7 @@ int run_window(vsx_searcher * S, const vsx_chimera_opts & O, CallBufs & B, bool 
       const uint64_t * qo, * to;
       const uint32_t * ql, * tl;
       uint64_t dummy;
-      vsx_internal_seqset_device(qs, &qc, &qo, &ql, &dummy);
+      vsx_internal_seqset_device(qset, &qc, &qo, &ql, &dummy);
       vsx_internal_seqset_device(dbset, &tc, &to, &tl, &dummy);
       hipStream_t st = vsx_internal_stream(ctx);
       GrowBuf<VsxChimItem> & d_items = B.items;
@@ -475,8 +444,8 @@ int run_window(vsx_searcher * S, const vsx_chimera_opts & O, CallBufs & B, bool 
       std::vector<vsx_chimera_result> res(items.size());
       CHIP(hipMemcpyAsync(res.data(), d_out.p, res.size() * sizeof(vsx_chimera_result), hipMemcpyDeviceToHost, st));
       CHIP(hipStreamSynchronize(st));
-      for (const VsxChimItem & it : items) out[w0 + it.q] = res[it.out];
-      g_stats.queries_kernel += items.size();
+      for (size_t x = 0; x < items.size(); ++x) *jobs[item_job[x]].out = res[items[x].out];
+      A.kernel += items.size();
     }
   if (!host_q.empty())
     {
@@ -485,14 +454,15 @@ int run_window(vsx_searcher * S, const vsx_chimera_opts & O, CallBufs & B, bool 
       const vsx_scoring * sc = vsx_internal_searcher_scoring(S);
       std::vector<uint8_t> qcode;
       std::vector<std::vector<uint8_t>> tcode;
-      for (uint64_t k : host_q)
+      for (size_t k : host_q)
         {
-          const uint32_t L = qlen[w0 + k];
-          const char * qt = qblob + qoff[w0 + k];
+          const EvalJob & j = jobs[k];
+          const uint32_t L = j.len;
+          const char * qt = j.text;
           qcode.resize(L);
           for (uint32_t i = 0; i < L; ++i) qcode[i] = map4((unsigned char) qt[i]);
-          const uint32_t nc = ncand[k];
-          const uint32_t * ck = &cand[(size_t) k * VSX_CHIM_MAXCAND];
+          const uint32_t nc = j.ncand;
+          const uint32_t * ck = j.cand;
           std::vector<std::vector<uint32_t>> runs(nc);
           std::vector<const uint8_t *> tp(nc);
           tcode.assign(nc, {});
@@ -518,11 +488,239 @@ int run_window(vsx_searcher * S, const vsx_chimera_opts & O, CallBufs & B, bool 
                   runs[c].assign(h_runs.rbegin() + (ptrdiff_t) (nruns - h.run_off - h.nruns), h_runs.rbegin() + (ptrdiff_t) (nruns - h.run_off));
                 }
             }
-          vsx_internal_chimera_eval_host(qcode.data(), (int) L, (int) nc, ck, runs, tp, P, &out[w0 + k]);
+          vsx_internal_chimera_eval_host(qcode.data(), (int) L, (int) nc, ck, runs, tp, P, j.out);
         }
-      g_stats.queries_host += host_q.size();
+      A.host += host_q.size();
     }
-  g_stats.seconds_eval += now_s() - t2;
+  A.t_eval += now_s() - t2;
+  return VSX_OK;
+}
+
+// the 4 parts of a query of length L >= 4 (partition_query, :1930-1955): lengths of the integer split, front to back
+template <class F>
+void for_each_part(uint32_t L, F && f)
+{
+  uint32_t rest = L, at = 0;
+  for (int i = 0; i < kParts; ++i)
+    {
+      const uint32_t length = (rest + (uint32_t) (kParts - i - 1)) / (uint32_t) (kParts - i);
+      f(at, length);
+      rest -= length;
+      at += length;
+    }
+}
+
+// one window: queries [w0, w0 + nw) of the call
+int run_window(vsx_searcher * S, const vsx_chimera_opts & O, CallBufs & B, bool host_all, uint64_t w0, uint64_t nw, const char * qblob, uint64_t qbytes,
+               const uint64_t * qoff, const uint32_t * qlen, vsx_chimera_result * out)
+{
+  vsx_ctx * ctx = vsx_internal_searcher_ctx(S);
+  const VsxChimParams P {O.minh, O.mindiv, O.xn, O.dn, O.mindiffs, 0};
+  const vsx_search_opts & so = *vsx_internal_searcher_opts(S);
+
+  // 1-2. parts through the window search
+  double t0 = now_s();
+  std::vector<uint64_t> poff;
+  std::vector<uint32_t> plen, pquery;
+  for (uint64_t k = 0; k < nw; ++k)
+    {
+      const uint32_t L = qlen[w0 + k];
+      if (L < (uint32_t) kParts) continue;
+      for_each_part(L, [&](uint32_t at, uint32_t length) { poff.push_back(qoff[w0 + k] + at); plen.push_back(length); pquery.push_back((uint32_t) k); });
+    }
+  std::vector<uint32_t> ncand(nw, 0), cand(nw * VSX_CHIM_MAXCAND, 0);
+  if (!poff.empty())
+    {
+      vsx_hits H {};
+      const int rc = vsx_internal_search_parts(S, so.maxaccepts + so.maxrejects, poff.size(), qblob, qbytes, poff.data(), plen.data(), &H);
+      if (rc != VSX_OK) return rc;
+      // 3. accepted hits part by part, best first; repeated targets dropped
+      for (uint64_t p = 0; p < poff.size(); ++p)
+        {
+          const uint32_t k = pquery[p];
+          uint32_t * c = &cand[(size_t) k * VSX_CHIM_MAXCAND];
+          for (uint64_t h = H.first[p]; h < H.first[p + 1]; ++h)
+            {
+              if (!H.hit[h].accepted) continue;
+              const uint32_t tg = H.hit[h].target;
+              if (std::find(c, c + ncand[k], tg) == c + ncand[k] && ncand[k] < VSX_CHIM_MAXCAND) c[ncand[k]++] = tg;
+            }
+        }
+      g_stats.parts += poff.size();
+      vsx_hits_free(&H);
+    }
+  g_stats.seconds_search += now_s() - t0;
+
+  // 4-5. whole queries against their candidates (one plan for the window), selection + scoring
+  std::vector<uint64_t> woff(nw);
+  std::string wblob;
+  std::vector<EvalJob> jobs(nw);
+  for (uint64_t k = 0; k < nw; ++k)
+    {
+      woff[k] = wblob.size();
+      wblob.append(qblob + qoff[w0 + k], qlen[w0 + k]);
+      jobs[k] = EvalJob {(uint32_t) k, qblob + qoff[w0 + k], qlen[w0 + k], ncand[k], &cand[(size_t) k * VSX_CHIM_MAXCAND], &out[w0 + k]};
+    }
+  bool any = false;
+  for (uint64_t k = 0; k < nw && !any; ++k) any = ncand[k] >= 2 && qlen[w0 + k] >= (uint32_t) kWindow;
+  if (!any)
+    {
+      for (const EvalJob & j : jobs) unscored(j.out, VSX_CHIMERA_NO_PARENTS, kNone, kNone);
+      return VSX_OK;
+    }
+  vsx_seqset * qs = nullptr;
+  int rc = vsx_seqset_create(ctx, &qs, nw, wblob.data(), wblob.size(), woff.data(), qlen + w0);
+  if (rc != VSX_OK) return rc;
+  struct Guard { vsx_seqset * s; ~Guard() { vsx_seqset_destroy(s); } } g {qs};
+  EvalAcct A;
+  rc = align_and_eval(S, P, B, host_all, qs, jobs, A, "vsx_uchime_ref");
+  g_stats.seconds_align += A.t_align;
+  g_stats.pairs_aligned += A.pairs;
+  g_stats.sentinel_pairs += A.sentinels;
+  g_stats.queries_kernel += A.kernel;
+  g_stats.queries_host += A.host;
+  g_stats.seconds_eval += A.t_eval;
+  return rc;
+}
+
+}  // namespace
+
+// the de novo part search in vsx_search.cpp (searcher internals)
+struct VsxDenovo;
+int vsx_internal_denovo_create(vsx_searcher * S, VsxDenovo ** out);
+void vsx_internal_denovo_destroy(VsxDenovo * D);
+int vsx_internal_denovo_window(VsxDenovo * D, uint64_t s0, uint64_t wn, const std::vector<uint64_t> & poff, const std::vector<uint32_t> & plen,
+                               const std::vector<uint32_t> & pmember, double * t_rank, double * t_members);
+void vsx_internal_denovo_merge(VsxDenovo * D, uint64_t p, const uint8_t * present, std::vector<uint32_t> & targets);
+int vsx_internal_denovo_search(VsxDenovo * D, const std::vector<uint32_t> & parts, std::vector<std::vector<uint32_t>> & accepted,
+                               uint64_t * pairs, uint64_t * sentinels);
+void vsx_internal_denovo_commit(VsxDenovo * D, const std::vector<uint32_t> & seqnos);
+bool vsx_internal_searcher_has_abundances(const vsx_searcher * S);
+
+namespace {
+
+thread_local vsx_chimera_denovo_stats g_dstats {};
+
+// status < suspicious (chimera.cpp:2314, :2365): what joins the index of later queries
+bool nonchimeric(const vsx_chimera_result & r) { return r.flag == 'N'; }
+
+// One window [s0, s0 + wn) of vsx_uchime_denovo: speculative passes with an in-order fix-up.
+//   present[j]  member j's assumed status in the current pass: its final one when resolved, "non-chimera" while pending
+//   lists[p]    part p's merged candidate list of the pass that produced the query's current result
+//   deps[k]     the earlier members that appeared in one of query k's lists
+// A pass re-searches, re-aligns and re-evaluates only the pending queries whose lists changed; a pending query whose lists did not
+// change keeps its result (the same lists give the same search, the same parents and the same scores).  A member reaches a list only
+// while it is assumed present, so query k is final once every member in deps[k] is final and a non-chimera: a member that did not
+// reach a list could only have pushed others out, and a pending member assumed present that turns out chimeric leaves the lists it
+// was not in unchanged.  The first pending query sees only final members, so every pass resolves at least one query.
+int denovo_window(vsx_searcher * S, VsxDenovo * D, const vsx_chimera_denovo_opts & O, CallBufs & B, bool host_all, uint64_t s0, uint64_t wn,
+                  vsx_chimera_result * out, std::vector<uint32_t> & commit)
+{
+  const char * text;
+  const uint64_t * off;
+  const uint32_t * len;
+  vsx_internal_searcher_text(S, &text, &off, &len);
+  const VsxChimParams P {O.base.minh, O.base.mindiv, O.base.xn, O.base.dn, O.base.mindiffs, O.variant};
+
+  std::vector<uint64_t> poff;
+  std::vector<uint32_t> plen, pmember, part0(wn + 1, 0);
+  for (uint64_t k = 0; k < wn; ++k)
+    {
+      part0[k] = (uint32_t) poff.size();
+      const uint32_t L = len[s0 + k];
+      if (L >= (uint32_t) kParts)
+        for_each_part(L, [&](uint32_t at, uint32_t length) { poff.push_back(off[s0 + k] + at); plen.push_back(length); pmember.push_back((uint32_t) k); });
+    }
+  part0[wn] = (uint32_t) poff.size();
+  g_dstats.parts += poff.size();
+  int rc = vsx_internal_denovo_window(D, s0, wn, poff, plen, pmember, &g_dstats.seconds_rank, &g_dstats.seconds_members);
+  if (rc != VSX_OK) return rc;
+
+  std::vector<uint8_t> present(wn, 1), final_(wn, 0), done_once(wn, 0);
+  std::vector<std::vector<uint32_t>> lists(poff.size()), deps(wn);
+  std::vector<uint32_t> ncand(wn, 0), cand(wn * VSX_CHIM_MAXCAND, 0);
+  std::vector<uint32_t> pending(wn);
+  for (uint64_t k = 0; k < wn; ++k) pending[k] = (uint32_t) k;
+  uint64_t passes = 0;
+  std::vector<uint32_t> tl;
+  while (!pending.empty())
+    {
+      ++passes;
+      // which pending queries have new lists
+      double t0 = now_s();
+      std::vector<uint32_t> redo, parts;
+      for (uint32_t k : pending)
+        {
+          bool changed = !done_once[k];
+          for (uint32_t p = part0[k]; p < part0[k + 1]; ++p)
+            {
+              vsx_internal_denovo_merge(D, p, present.data(), tl);
+              if (tl != lists[p]) { changed = true; lists[p].swap(tl); }
+            }
+          if (!changed) continue;
+          if (done_once[k]) ++g_dstats.queries_reevaluated;
+          done_once[k] = 1;
+          redo.push_back(k);
+          for (uint32_t p = part0[k]; p < part0[k + 1]; ++p) parts.push_back(p);
+          deps[k].clear();
+          for (uint32_t p = part0[k]; p < part0[k + 1]; ++p)
+            for (uint32_t t : lists[p])
+              if (t >= s0 && std::find(deps[k].begin(), deps[k].end(), (uint32_t) (t - s0)) == deps[k].end()) deps[k].push_back((uint32_t) (t - s0));
+        }
+      g_dstats.seconds_reconcile += now_s() - t0;
+
+      // the parts of those queries through the staged search; accepted hits part by part, repeated targets dropped (:2017-2071)
+      t0 = now_s();
+      std::vector<std::vector<uint32_t>> acc;
+      rc = vsx_internal_denovo_search(D, parts, acc, &g_dstats.pairs_searched, &g_dstats.sentinel_pairs);
+      if (rc != VSX_OK) return rc;
+      g_dstats.seconds_search += now_s() - t0;
+      size_t x = 0;
+      for (uint32_t k : redo)
+        {
+          ncand[k] = 0;
+          uint32_t * c = &cand[(size_t) k * VSX_CHIM_MAXCAND];
+          for (uint32_t p = part0[k]; p < part0[k + 1]; ++p, ++x)
+            for (uint32_t tg : acc[x])
+              if (std::find(c, c + ncand[k], tg) == c + ncand[k] && ncand[k] < VSX_CHIM_MAXCAND) c[ncand[k]++] = tg;
+        }
+
+      // whole queries (in the database set) against their candidates, selection + scoring
+      if (!redo.empty())
+        {
+          std::vector<EvalJob> jobs;
+          jobs.reserve(redo.size());
+          for (uint32_t k : redo)
+            jobs.push_back(EvalJob {(uint32_t) (s0 + k), text + off[s0 + k], len[s0 + k], ncand[k], &cand[(size_t) k * VSX_CHIM_MAXCAND], &out[s0 + k]});
+          EvalAcct A;
+          rc = align_and_eval(S, P, B, host_all, vsx_internal_searcher_dbset(S), jobs, A, "vsx_uchime_denovo");
+          if (rc != VSX_OK) return rc;
+          g_dstats.seconds_align += A.t_align;
+          g_dstats.seconds_eval += A.t_eval;
+          g_dstats.pairs_aligned += A.pairs;
+          g_dstats.sentinel_pairs += A.sentinels;
+          g_dstats.queries_kernel += A.kernel;
+          g_dstats.queries_host += A.host;
+        }
+
+      // validate in order
+      t0 = now_s();
+      std::vector<uint32_t> still;
+      for (uint32_t k : pending)
+        {
+          bool ok = true;
+          for (uint32_t j : deps[k])
+            if (!final_[j] || !nonchimeric(out[s0 + j])) { ok = false; break; }          // (a member in a list was assumed present)
+          if (ok) { final_[k] = 1; present[k] = nonchimeric(out[s0 + k]) ? 1 : 0; }
+          else still.push_back(k);
+        }
+      pending.swap(still);
+      g_dstats.seconds_reconcile += now_s() - t0;
+    }
+  g_dstats.passes += passes;
+  g_dstats.passes_max = std::max<uint64_t>(g_dstats.passes_max, passes);
+  for (uint64_t k = 0; k < wn; ++k)
+    if (present[k]) commit.push_back((uint32_t) (s0 + k));
   return VSX_OK;
 }
 
@@ -572,6 +770,64 @@ int vsx_uchime_ref(vsx_searcher * S, const vsx_chimera_opts * O, uint64_t n, con
       ++g_stats.windows;
     }
   g_stats.seconds_total = now_s() - t0;
+  return VSX_OK;
+}
+
+void vsx_chimera_denovo_opts_default(vsx_chimera_denovo_opts * o, int32_t variant)
+{
+  std::memset(o, 0, sizeof *o);
+  vsx_chimera_opts_default(&o->base);
+  o->variant = variant;
+  o->abskew = variant == 3 ? 16.0 : 2.0;          // cli.cc:4478-4492
+  o->base.search.self = 1;                          // chimera_detection_parameters (chimera.cpp:2805-2824)
+  o->base.search.selfid = 1;
+  o->base.search.maxsizeratio = 1.0 / o->abskew;
+}
+
+void vsx_chimera_denovo_last_stats(vsx_chimera_denovo_stats * out) { if (out) *out = g_dstats; }
+
+int vsx_uchime_denovo(vsx_searcher * S, const vsx_chimera_denovo_opts * O, vsx_chimera_result * out)
+{
+  g_dstats = vsx_chimera_denovo_stats {};
+  const double t0 = now_s();
+  if (!O) return cfail(VSX_EINVAL, "vsx_uchime_denovo: null options");
+  if (O->variant < 1 || O->variant > 3) return cfail(VSX_EINVAL, "vsx_uchime_denovo: variant must be 1 (uchime), 2 (uchime2) or 3 (uchime3)");
+  if (!(O->abskew >= 1.0)) return cfail(VSX_EINVAL, "vsx_uchime_denovo: abskew must be >= 1.0");
+  if (O->base.mindiffs < 0 || !(O->base.xn > 0.0) || !(O->base.dn >= 0.0))
+    return cfail(VSX_EINVAL, "vsx_uchime_denovo: xn must be > 0, dn >= 0, mindiffs >= 0");
+  if (!S || !out) return cfail(VSX_EINVAL, "vsx_uchime_denovo: null argument");
+  const vsx_search_opts & so = *vsx_internal_searcher_opts(S);
+  if (so.strand_both) return cfail(VSX_EINVAL, "vsx_uchime_denovo: --strand both is not provided (the reference refuses it)");
+  if (so.id != 0.55 || so.weak_id != 0.55 || so.maxaccepts != 4 || so.maxrejects != 16 || so.cluster_unoise || so.self != 1 ||
+      so.selfid != 1 || so.maxsizeratio != 1.0 / O->abskew || (so.qmask != 0 && so.qmask != so.soft_mask + 1))
+    return cfail(VSX_EINVAL, "vsx_uchime_denovo: the searcher was not created with the detection parameters (vsx_chimera_denovo_opts_default: "
+                             "id = weak_id = 0.55, maxaccepts 4, maxrejects 16, self = selfid = 1, maxsizeratio = 1 / abskew, qmask as soft_mask)");
+  if (!vsx_internal_searcher_has_abundances(S)) return cfail(VSX_EINVAL, "vsx_uchime_denovo: the searcher has no abundances (vsx_searcher_set_meta)");
+  if (so.wordlength > 8) return cfail(VSX_EINVAL, "vsx_uchime_denovo: word lengths above 8 are not provided");
+  const char * text;
+  const uint64_t * off;
+  const uint32_t * len;
+  vsx_internal_searcher_text(S, &text, &off, &len);
+  const uint64_t n = vsx_seqset_count(vsx_internal_searcher_dbset(S));
+  if (n == 0) { g_dstats.seconds_total = now_s() - t0; return VSX_OK; }
+  VsxDenovo * D = nullptr;
+  int rc = vsx_internal_denovo_create(S, &D);
+  if (rc != VSX_OK) return rc;
+  struct DGuard { VsxDenovo * d; ~DGuard() { vsx_internal_denovo_destroy(d); } } dg {D};
+  const char * env = std::getenv("VSX_CHIMERA");
+  const bool host_all = env && std::strcmp(env, "host") == 0;
+  const uint64_t window = O->base.window > 0 ? (uint64_t) O->base.window : 4096;
+  CallBufs bufs;
+  std::vector<uint32_t> commit;
+  for (uint64_t s0 = 0; s0 < n; s0 += window)
+    {
+      commit.clear();
+      rc = denovo_window(S, D, *O, bufs, host_all, s0, std::min(window, n - s0), out, commit);
+      if (rc != VSX_OK) return rc;
+      vsx_internal_denovo_commit(D, commit);
+      ++g_dstats.windows;
+    }
+  g_dstats.seconds_total = now_s() - t0;
   return VSX_OK;
 }
 

@@ -392,7 +392,11 @@ vsx_chimera_eval_kernel(const VsxChimItem * __restrict__ items, const uint8_t * 
   r.divergence = divdiff;
   const int sumL = r.left_no + r.left_abstain + r.left_yes, sumR = r.right_no + r.right_abstain + r.right_yes;
   r.flag = 'N';
-  if (r.score >= P.minh)
+  if (P.variant >= 2)
+    {
+      if (s_cnt[4] == c0 && QT < 100.0) r.flag = 'Y';          // uchime2 / uchime3 (chimera.cpp:1633-1640): a perfect model, no '?'
+    }
+  else if (r.score >= P.minh)
     {
       r.flag = '?';
       if ((divdiff >= P.mindiv) && (sumL >= P.mindiffs) && (sumR >= P.mindiffs)) r.flag = 'Y';

@@ -142,7 +142,12 @@ struct VsxChimItem {
   uint32_t out;                      // index of its result record
   uint32_t cand[VSX_CHIM_MAXCAND];   // database indices
 };
-struct VsxChimParams { double minh, mindiv, xn, dn; int64_t mindiffs; };
+struct VsxChimParams {
+  double minh, mindiv, xn, dn;
+  int64_t mindiffs;
+  int32_t variant;                   // 0 / 1: the minh / mindiv / mindiffs verdict (--uchime_ref, --uchime_denovo); 2 / 3: uchime2 / uchime3
+  int32_t pad;
+};
 
 #ifdef __cplusplus
 extern "C" {
