@@ -9,12 +9,16 @@ A "step" = one pass of the hot path over one batch: every (query, candidate) pai
 queries against their 8 candidates in a device-resident 1 M x 1 kbp family-structured DB
 (BASELINE config[1]) -> packed-int16 DP kernel (scores + checkpoints) + traceback kernel (statistics +
 CIGAR run lists) + text kernel (CIGAR strings, output arrays).  Inputs (DB, queries, pair/task list) are
-resident in HBM before the timed region; results stay in HBM -- that is `value`.  Next to it, never in it:
+resident in HBM before the timed region; results stay in HBM -- that is `value`.  A plain run sets up, warms up,
+times the steps, writes --dump-outputs and prints its line.  --full adds, after the timed steps and never in them:
+  fetch_s           one plan's results on the host (PCIe + result arrays + CIGAR text), value_incl_fetch
   end_to_end        vsx_align_pairs on the same pair list, host arrays in / host arrays + CIGAR text out
                     (planning, kernels, PCIe, pipelined slices; pools warm), steady state
+  cpu_baseline      the reference's SSE2 search16 on a sample of the same pairs, all fields compared
   search_end_to_end vsx_search_batch (= --usearch_global --id 0.9) for the same queries against the same DB:
                     k-mer candidate stage + dispatch + alignments + hit lists, next to the reference CLI
                     (oracle/_ref/vsearch_ref, all usable cores) on a sample of the same queries
+  shapes            the other BASELINE pair shapes (SHAPES), kernels timed, each with a parity sample
 With --gpus N every rank plays one block of a query-sharded job (vsearch_amd/sharding.py): own queries, DB
 replica, no data-path collective, one gather of hit records + CIGAR run words at the end of every step.
 
@@ -119,10 +123,13 @@ def parse():
     ap.add_argument("--db", type=int, default=1_000_000)
     ap.add_argument("--dlen", type=int, default=1000)
     ap.add_argument("--cands", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement of the line: the fetch to the host, end_to_end, "
+                         "cpu_baseline, search_end_to_end, shapes (the options below narrow them); a plain run only times the steps")
     ap.add_argument("--cpu-pairs", type=int, default=400_000, help="pairs in the bounded CPU-baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = all online cores")
     ap.add_argument("--no-cpu", action="store_true", help="skip every CPU leg (cpu_baseline and the reference CLI)")
-    ap.add_argument("--kernels-only", action="store_true", help="only the timed kernel steps (profiling passes)")
+    ap.add_argument("--kernels-only", action="store_true", help="with --full: still only the timed kernel steps (profiling passes)")
     ap.add_argument("--e2e-calls", type=int, default=5, help="timed vsx_align_pairs calls of the end-to-end figure")
     ap.add_argument("--no-search", action="store_true", help="skip the vsx_search_batch end-to-end figure")
     ap.add_argument("--no-shapes", action="store_true", help="skip the kernels-only runs of the other BASELINE shapes (configs 3 / 4 / 5)")
@@ -336,10 +343,12 @@ def main():
                             and int(other["run_off"][other["nruns"] > 0].min()) >= n_runs0
                             and int(runs_all.numel()) >= n_runs0 + int(other["nruns"].sum()))
 
-    # ---- results on the host (PCIe + malloc'd arrays + CIGAR text), one plan, informational ----
-    t0 = time.perf_counter()
-    res = plan.fetch()
-    t_fetch = time.perf_counter() - t0
+    # ---- results on the host (PCIe + malloc'd arrays + CIGAR text), one plan: what --dump-outputs writes and the --full legs compare ----
+    res = None
+    if a.full or a.dump_outputs:
+        t0 = time.perf_counter()
+        res = plan.fetch()
+        t_fetch = time.perf_counter() - t0
     dumped = dump_outputs(a.dump_outputs, res) if a.dump_outputs else None
 
     total_cells = job_cells * a.steps
@@ -403,8 +412,6 @@ def main():
         "kernel_split_ms_per_step": {"forward": round(fwd_ms / a.steps, 3), "traceback": round(tb_ms / a.steps, 3),
                                      "cigar_text_and_rest": round((tot_ms - fwd_ms - tb_ms) / a.steps, 3)},
         "plan_s": round(t_plan, 3),
-        "fetch_s": round(t_fetch, 3),
-        "value_incl_fetch": round(cells / (ms_per_step * 1e-3 + t_fetch) / 1e9, 2),
         "gen_s": round(t_gen, 2),
     }
     if pmc:
@@ -445,7 +452,11 @@ def main():
             rccl["fixed_gather_overlap"] = fixed.stats()       # rank 0's view: did step k's collective finish while step k + 1 computed?
         out["rccl"] = rccl
 
-    if not a.kernels_only and world == 1:
+    if a.full:
+        out["fetch_s"] = round(t_fetch, 3)
+        out["value_incl_fetch"] = round(cells / (ms_per_step * 1e-3 + t_fetch) / 1e9, 2)
+    side = a.full and not a.kernels_only and world == 1        # the side legs: rank 0 at N = 1 only (the other ranks would idle in the barrier)
+    if side:
         # ---- end to end through the one-call entry (host index arrays in, host result arrays + CIGAR text out) ----
         try:
             out["end_to_end"] = end_to_end(a, al, Q, T, qidx, tidx, cells, res)
@@ -455,7 +466,7 @@ def main():
 
     # ---- CPU baseline: the reference's own SSE2 search16 (oracle/_ref, built from /root/reference) on a
     #      bounded sample of the SAME workload; falls back to the scalar port if _ref was not shipped ----
-    if not a.no_cpu and not a.kernels_only and world == 1:          # rank 0 at N = 1 only: the other ranks would idle in the barrier
+    if side and not a.no_cpu:
         try:
             out["cpu_baseline"] = cpu_baseline(a, db_ascii, db_off, db_len, q_ascii, q_off, q_len, qidx, tidx, res)
             if "value_end_to_end" in out and out["cpu_baseline"].get("value"):
@@ -463,14 +474,14 @@ def main():
         except Exception as e:  # the baseline is a side measurement: never lose the bench line over it
             out["cpu_baseline"] = {"error": repr(e)}
 
-    if not a.kernels_only and not a.no_search and world == 1:
+    if side and not a.no_search:
         plan.close()
         try:
             out["search_end_to_end"] = search_end_to_end(a, al, db_ascii, db_off, db_len, q_ascii, q_off, q_len)
         except Exception as e:
             import traceback
             out["search_end_to_end"] = {"error": repr(e), "traceback": traceback.format_exc()[-1500:]}
-    if not a.kernels_only and not a.no_shapes and world == 1:
+    if side and not a.no_shapes:
         try:
             plan.close()
         except Exception:

@@ -9,7 +9,7 @@ cd $REPO
 n=0
 for E in "$@"; do
   n=$((n + 1))
-  env $E python bench.py --no-cpu --no-search --steps 2 --warmup 1 --e2e-calls 7 > $OUT/run$n.json 2> $OUT/run$n.err
+  env $E python bench.py --full --no-cpu --no-search --steps 2 --warmup 1 --e2e-calls 7 > $OUT/run$n.json 2> $OUT/run$n.err
   python - $OUT/run$n.json "$E" <<'PY'
 import json, sys
 try:

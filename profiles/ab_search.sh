@@ -9,7 +9,7 @@ cd $REPO
 n=0
 for E in "$@"; do
   n=$((n + 1))
-  env $E VSX_BENCH_SEARCH_REPS=9 python bench.py --no-cpu --no-shapes --steps 1 --warmup 0 --e2e-calls 1 --ref-search-queries 0 > $OUT/run$n.json 2> $OUT/run$n.err
+  env $E VSX_BENCH_SEARCH_REPS=9 python bench.py --full --no-cpu --no-shapes --steps 1 --warmup 0 --e2e-calls 1 --ref-search-queries 0 > $OUT/run$n.json 2> $OUT/run$n.err
   python - $OUT/run$n.json "$E" <<'PY'
 import json, sys
 try:

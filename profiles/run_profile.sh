@@ -11,7 +11,7 @@ echo "cgroup cpu.max: $(cat /sys/fs/cgroup/cpu.max 2>/dev/null)  nproc: $(nproc)
 python -c "import os; print('affinity', len(os.sched_getaffinity(0)))" >> $OUT/host.txt; cat $OUT/host.txt
 cd /tmp && export TMPDIR=/tmp
 BENCH="python $REPO/bench.py --steps 3 --warmup 1"
-if [ "${FULL_BENCH:-0}" = "1" ]; then $BENCH > $OUT/bench.json 2> $OUT/bench.err; else $BENCH --no-cpu --no-search > $OUT/bench.json 2> $OUT/bench.err; fi
+if [ "${FULL_BENCH:-0}" = "1" ]; then $BENCH --full > $OUT/bench.json 2> $OUT/bench.err; else $BENCH --full --no-cpu --no-search > $OUT/bench.json 2> $OUT/bench.err; fi
 tail -c 3000 $OUT/bench.json
 # per-kernel time (same command, no CPU leg)
 rocprofv3 --output-format csv --kernel-trace --stats -d $WORK/trace -o trace -- $BENCH --kernels-only > $OUT/trace.log 2>&1

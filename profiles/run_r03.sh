@@ -18,7 +18,7 @@ trace() {   # name, command...
   for f in $(find /tmp/vsxmisc_$name -name "*kernel_stats.csv"); do grep -E "Name|vsx_" $f > $REPO/gpurun_out/${TAG}_misc/${name}_kernel_stats.csv; done
 }
 trace allpairs python $REPO/bench_allpairs.py --n 6000 --parity-prefix 0
-trace search_dust python $REPO/bench.py --no-cpu --search-mask dust --steps 1 --warmup 0 --e2e-calls 1
+trace search_dust python $REPO/bench.py --full --no-cpu --search-mask dust --steps 1 --warmup 0 --e2e-calls 1
 trace cluster python $REPO/bench_cluster.py --n 200000 --parity-prefix 0
 trace msa python $REPO/bench_msa.py
 trace kmer_w12 python -c "

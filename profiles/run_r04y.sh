@@ -22,7 +22,7 @@ rocprofv3 --output-format csv --kernel-trace --pmc WRITE_SIZE -d $WORK/pmc_write
 python $REPO/profiles/summarize.py $WORK > $OUT/summary_early.txt 2>&1
 cp $WORK/traffic.json $OUT/traffic_early.json 2>/dev/null && cp $WORK/traffic.json $REPO/profiles/pmc_current.json
 echo "trace + fetch + write done after $(( $(date +%s) - T0 )) s"
-$BENCH > $OUT/bench.json 2> $OUT/bench.err
+$BENCH --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 2500 $OUT/bench.json
 echo "bench done after $(( $(date +%s) - T0 )) s"
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY -d $WORK/pmc_sq -o pmc -- $BENCH --kernels-only --steps 1 --warmup 0 > $OUT/pmc_sq.log 2>&1

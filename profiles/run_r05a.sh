@@ -13,7 +13,7 @@ cd $REPO
 T0=$(date +%s)
 { echo "cgroup cpu.max: $(cat /sys/fs/cgroup/cpu.max 2>/dev/null)  nproc: $(nproc)"; free -g | head -2; df -h /tmp | tail -1; rocm-smi --showmeminfo vram 2>/dev/null | grep -i total | head -1; } > $OUT/host.txt 2>&1
 cat $OUT/host.txt
-python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench rc=$? after $(( $(date +%s) - T0 )) s"; tail -c 1500 $OUT/bench_full.json
 cd /tmp && export TMPDIR=/tmp
 BENCH="python $REPO/bench.py --steps 3 --warmup 1"
@@ -28,7 +28,7 @@ grep -E "vsx_forward|vsx_traceback_tilt|cigar_text" $OUT/summary.txt | head -8 |
 echo "trace + pmc done after $(( $(date +%s) - T0 )) s"
 cd $REPO
 # BASELINE config 5, one GPU's share of the 8-GPU job (10 M queries / 8), the database at its stated size
-VSX_BENCH_SEARCH_REPS=3 timeout 1500 python bench.py --queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --steps 2 --warmup 1 \
+VSX_BENCH_SEARCH_REPS=3 timeout 1500 python bench.py --full --queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --steps 2 --warmup 1 \
     --no-shapes --ref-search-queries 2048 --e2e-calls 1 > $OUT/config5_share.json 2> $OUT/config5_share.err
 echo "config5 rc=$? after $(( $(date +%s) - T0 )) s"; tail -c 3000 $OUT/config5_share.json; tail -5 $OUT/config5_share.err
 free -g | head -2 >> $OUT/host.txt

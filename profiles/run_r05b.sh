@@ -39,7 +39,7 @@ echo "feed2 tests rc=$? after $(el): $(tail -1 $OUT/feed2_tests.log)"
 VSX_LIBRARY=$REPO/vsearch_amd/libvsx_feed2.so timeout 100 python oracle/soak.py --seconds 40 --seed 5151 --out gpurun_out/$TAG/feed2_soak.json > $OUT/feed2_soak.log 2>&1
 echo "feed2 soak rc=$? $(python -c "import json; d=json.load(open('gpurun_out/$TAG/feed2_soak.json')); print({k: v for k, v in d.items() if k in ('rounds','pairs','mismatches','seed')})" 2>&1 | cut -c1-200)"
 # ---- (4) default bench line
-python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench rc=$? after $(el)"; python - $OUT/bench_full.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -48,7 +48,7 @@ s = d.get("search_end_to_end", {})
 print({k: s.get(k) for k in ("error", "traceback", "queries_per_s", "seconds_later_calls", "reference_cli")})
 PY
 # ---- (5) config 5 share
-VSX_BENCH_SEARCH_REPS=3 timeout 1500 python bench.py --queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --steps 2 --warmup 1 \
+VSX_BENCH_SEARCH_REPS=3 timeout 1500 python bench.py --full --queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --steps 2 --warmup 1 \
     --no-shapes --ref-search-queries 2048 --e2e-calls 1 > $OUT/config5_share.json 2> $OUT/config5_share.err
 echo "config5 rc=$? after $(el)"; python - $OUT/config5_share.json <<'PY'
 import json, sys

@@ -32,7 +32,7 @@ echo "sparse A/B done after $(el)"
 VSX_SHIM_STATS=1 GRAFT_REPO_ROOT=$REPO timeout 300 bash profiles/shim_cost.sh > $OUT/shim_cost.txt 2>&1
 cat $OUT/shim_cost.txt | cut -c1-300
 echo "shim cost done after $(el)"
-python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench rc=$? after $(el)"; python - $OUT/bench_full.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -41,7 +41,7 @@ s = d.get("search_end_to_end", {})
 print({k: s.get(k) for k in ("error", "traceback", "queries_per_s", "seconds_later_calls", "reference_cli")})
 for k, v in d.get("shapes", {}).items(): print(k, v.get("value"), v.get("kernel_split_ms_per_step"), v.get("parity_all_fields_match"))
 PY
-VSX_BENCH_SEARCH_REPS=3 timeout 1500 python bench.py --queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --steps 2 --warmup 1 \
+VSX_BENCH_SEARCH_REPS=3 timeout 1500 python bench.py --full --queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --steps 2 --warmup 1 \
     --no-shapes --ref-search-queries 2048 --e2e-calls 1 > $OUT/config5_share.json 2> $OUT/config5_share.err
 echo "config5 rc=$? after $(el)"; python - $OUT/config5_share.json <<'PY'
 import json, sys

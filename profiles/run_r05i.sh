@@ -11,5 +11,5 @@ timeout 700 python -m pytest tests -x -q -m gpu > $OUT/tests.log 2>&1
 echo "tests rc=$? after $(( $(date +%s) - T0 )) s: $(tail -1 $OUT/tests.log)"
 grep -E "FAILED|Error|assert" $OUT/tests.log | head
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$? $(tail -1 $OUT/smoke.log)"
-python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench rc=$? after $(( $(date +%s) - T0 )) s: $(python -c "import json; d=json.loads(open('$OUT/bench_full.json').read().strip().splitlines()[-1]); print(d['value'], d['kernel_split_ms_per_step'], d.get('value_end_to_end'), d['roofline']['frac'], d['roofline'].get('traffic'), d['search_end_to_end'].get('queries_per_s'), d['cpu_baseline'].get('parity_all_fields_match'))" 2>&1 | cut -c1-300)"

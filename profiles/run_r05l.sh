@@ -17,7 +17,7 @@ for s in soak_search soak_api; do
   echo "$s rc=$? $(python -c "import json; d=json.load(open('gpurun_out/$TAG/$s.json')); print({k: v for k, v in d.items() if k not in ('failures', 'examples', 'what')})" 2>&1 | cut -c1-300)"
 done
 for LZ in 0 1 0 1; do
-  VSX_SEARCH_LAZY=$LZ python bench.py --no-shapes > $OUT/bench_lazy$LZ.json 2> $OUT/bench_lazy$LZ.err
+  VSX_SEARCH_LAZY=$LZ python bench.py --full --no-shapes > $OUT/bench_lazy$LZ.json 2> $OUT/bench_lazy$LZ.err
   echo "lazy=$LZ after $(el): $(python -c "import json; d=json.loads(open('$OUT/bench_lazy$LZ.json').read().strip().splitlines()[-1]); s=d['search_end_to_end']; print(d['value'], 'search', s['queries_per_s'], s['seconds_later_calls'], 'pairs', s['pairs_aligned'], 'hits', s['hits'], 'kmer', s['seconds_kmer'], 'align', s['seconds_align'], (s.get('reference_cli') or {}).get('same_hits_as_vsx'))" 2>&1 | cut -c1-400)"
 done
 echo "all done after $(el)"

@@ -15,7 +15,7 @@ for LZ in 0 1; do
   grep -E "vsx_cluster_fast:" $OUT/cluster_lazy$LZ.err | tail -1 | cut -c1-400
 done
 for rep in 1 2; do
-  python bench.py > $OUT/bench_full_$rep.json 2> $OUT/bench_full_$rep.err
+  python bench.py --full > $OUT/bench_full_$rep.json 2> $OUT/bench_full_$rep.err
   echo "bench $rep rc=$? after $(el): $(python -c "import json; d=json.loads(open('$OUT/bench_full_$rep.json').read().strip().splitlines()[-1]); s=d['search_end_to_end']; print(d['value'], d['kernel_split_ms_per_step'], 'e2e', d.get('value_end_to_end'), 'frac', d['roofline']['frac'], 'search', s['queries_per_s'], s['seconds_later_calls'], s['pairs_aligned'], (s.get('reference_cli') or {}).get('same_hits_as_vsx'), {k: v['value'] for k, v in d['shapes'].items()})" 2>&1 | cut -c1-600)"
 done
 echo "all done after $(el)"

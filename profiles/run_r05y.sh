@@ -32,7 +32,7 @@ cp $WORK/traffic.json $OUT/traffic.json 2>/dev/null && cp $WORK/traffic.json $RE
 grep -E "vsx_forward|vsx_traceback_tilt|cigar_text" $OUT/summary.txt | head -12 | cut -c1-330
 echo "trace + pmc done after $(el)"
 cd $REPO
-python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench rc=$? after $(el)"; python - $OUT/bench_full.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

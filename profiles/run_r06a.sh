@@ -13,7 +13,7 @@ T0=$(date +%s)
 el() { echo "$(( $(date +%s) - T0 )) s"; }
 { echo "cgroup cpu.max: $(cat /sys/fs/cgroup/cpu.max 2>/dev/null)  nproc: $(nproc)"; free -g | head -2; } > $OUT/host.txt 2>&1
 # (1) search timeline
-VSX_DEBUG_TIMELINE=1 VSX_DEBUG_TIMING=1 VSX_BENCH_SEARCH_REPS=7 python bench.py --no-cpu --no-shapes --steps 1 --warmup 0 --e2e-calls 1 --ref-search-queries 0 \
+VSX_DEBUG_TIMELINE=1 VSX_DEBUG_TIMING=1 VSX_BENCH_SEARCH_REPS=7 python bench.py --full --no-cpu --no-shapes --steps 1 --warmup 0 --e2e-calls 1 --ref-search-queries 0 \
     > $OUT/search_timeline.json 2> $OUT/search_timeline.err
 echo "search timeline rc=$? after $(el)"
 python - $OUT/search_timeline.json <<'PY'
@@ -37,7 +37,7 @@ cd $REPO
 timeout 300 python bench_kmer.py > $OUT/bench_kmer.json 2> $OUT/bench_kmer.err
 echo "kmer rc=$? after $(el): $(cut -c1-600 $OUT/bench_kmer.json)"
 # (3) the default line
-python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench rc=$? after $(el)"; python - $OUT/bench_full.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

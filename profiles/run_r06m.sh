@@ -10,7 +10,7 @@ T0=$(date +%s)
 el() { echo "$(( $(date +%s) - T0 )) s"; }
 timeout 1500 python -m pytest tests -x -q -m gpu > $OUT/tests.log 2>&1; echo "tests after $(el): $(tail -1 $OUT/tests.log)"; grep -E "FAILED|Error" $OUT/tests.log | head -5
 bash profiles/run_soaks.sh $TAG/soaks 45 606 2>&1 | cut -c1-330; echo "soaks after $(el)"
-python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench rc=$? after $(el)"; python - $OUT/bench_full.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/$TAG; WORK=/tmp/vsxprof_$TAG
 rm -rf $WORK; mkdir -p $OUT $WORK
 cd /tmp && export TMPDIR=/tmp
-ARGS="--queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --no-cpu --no-shapes --steps 1 --warmup 0 --e2e-calls 1 --ref-search-queries 0"
+ARGS="--full --queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --no-cpu --no-shapes --steps 1 --warmup 0 --e2e-calls 1 --ref-search-queries 0"
 VSX_BENCH_SEARCH_REPS=2 VSX_DEBUG_TIMELINE=1 VSX_DEBUG_TIMING=1 rocprofv3 --output-format csv --kernel-trace --stats -d $WORK/trace -o trace -- python $REPO/bench.py $ARGS > $OUT/c5.json 2> $OUT/c5.err
 for f in $(find $WORK/trace -name "*kernel_stats.csv"); do cp $f $OUT/kernel_stats.csv; done
 python - $OUT/kernel_stats.csv <<'PY'

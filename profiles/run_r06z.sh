@@ -44,7 +44,7 @@ cd $REPO
 timeout 300 python bench_kmer.py > $OUT/bench_kmer.json 2> $OUT/bench_kmer.err
 echo "kmer rc=$? after $(el): $(python -c "import json; d=json.loads(open('$OUT/bench_kmer.json').read().strip().splitlines()[-1]); r=d['roofline']; print(d['value'], d['kernel_ms'], 'achieved', r['achieved'], 'traffic', r['traffic'], r.get('traffic_GBps'), d['parity_lists_equal_on_sample'])" 2>&1 | cut -c1-300)"
 # (4) default line
-python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err
+python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err
 echo "bench rc=$? after $(el)"; python - $OUT/bench_full.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -59,7 +59,7 @@ echo "cluster rc=$? after $(el): $(cut -c1-900 $OUT/bench_cluster_2M.json)"
 grep -E "vsx_cluster_fast:" $OUT/bench_cluster_2M.err | tail -1 | cut -c1-400 | tee $OUT/bench_cluster_2M_phases.txt
 timeout 900 python bench_allpairs.py --n 50000 --block 1000 --stream 1 --parity-prefix 3000 > $OUT/bench_allpairs_50k.json 2> $OUT/bench_allpairs_50k.err
 echo "allpairs 50k rc=$? after $(el): $(python -c "import json; d=json.loads(open('$OUT/bench_allpairs_50k.json').read().strip().splitlines()[-1]); print(d['value'], d['wall_s'], d['align_calls_s'], d['accepted_hits'], d['block_s'][:4], d['parity'])" 2>&1 | cut -c1-600)"
-VSX_BENCH_SEARCH_REPS=3 timeout 1500 python bench.py --queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --steps 2 --warmup 1 \
+VSX_BENCH_SEARCH_REPS=3 timeout 1500 python bench.py --full --queries 1250000 --qlen 150 --db 5000000 --dlen 1000 --steps 2 --warmup 1 \
     --no-shapes --ref-search-queries 2048 --e2e-calls 1 > $OUT/config5_share.json 2> $OUT/config5_share.err
 echo "config5 rc=$? after $(el)"; python - $OUT/config5_share.json <<'PY'
 import json, sys

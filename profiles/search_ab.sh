@@ -4,7 +4,7 @@
 export VSX_BENCH_SEARCH_REPS=${REPS:-7}
 run() {
   echo "== $*"
-  env "$@" python bench.py --steps 1 --warmup 0 --no-cpu --e2e-calls 1 2>/dev/null | python -c "
+  env "$@" python bench.py --full --steps 1 --warmup 0 --no-cpu --e2e-calls 1 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])['search_end_to_end']
 print(d['queries_per_s'], d['seconds'], sorted(d['seconds_later_calls']), d['hits'], 'create', d['searcher_create_s'], 'first', d['seconds_first_call'])"
