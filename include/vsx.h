@@ -202,7 +202,7 @@ void vsx_results_free(vsx_results * r);
 /* Ranking and compaction on the device: of a pair list grouped by query (all pairs of a query contiguous)
    only the pairs the filter KEEPS come back -- verdict ACCEPTED, plus WEAK with keep_weak -- already in report order:
    queries in list order, inside a query identity descending, then list order (= target ascending when the caller lists
-   targets ascending): hit_compare_byid (core/searchcore.cpp:133-179), allpairs_hit_compare (commands/allpairs_global.cpp:
+   targets ascending; in a list that is not grouped, every run of equal query indices is ranked as a group of its own): hit_compare_byid (core/searchcore.cpp:133-179), allpairs_hit_compare (commands/allpairs_global.cpp:
    116-138).  `id` is the identity the filter compared (iddef of the filter).  Pairs the 16-bit aligner refused (sentinel)
    are listed in `undecided` for the caller's fallback.  The filter is required. */
 typedef struct vsx_ranked {

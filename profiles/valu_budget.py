@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/valu_budget.py [--lib vsearch_amd/libvsx.so] [--kernel "16,true,false,true,true,true,1,false,true"] [--rows R] [--loop N]
+"""profiles/valu_budget.py [--lib vsearch_amd/libvsx.so] [--kernel "16,false,true,true,1,false,true"] [--rows R] [--loop N]
 
 VALU budget of the steady interior loop of one vsx_forward_kernel instantiation, read from the gfx950 code object inside the built
 library (llvm-objdump; no GPU needed).  Prints every loop of the kernel (backward branches), then for the chosen one (default: the loop
@@ -126,7 +126,7 @@ def budget(body, R, S):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=os.path.join(ROOT, "vsearch_amd", "libvsx.so"))
-    ap.add_argument("--kernel", default="16,true,false,true,true,true,1,false,true", help="template arguments of vsx_forward_kernel")
+    ap.add_argument("--kernel", default="16,false,true,true,1,false,true", help="template arguments of vsx_forward_kernel")
     ap.add_argument("--rows", type=int, default=None, help="R (default: the first template argument)")
     ap.add_argument("--loop", type=int, default=None, help="loop index to budget (default: most v_pk_maximum3_f16)")
     ap.add_argument("--ops", action="store_true", help="print the opcode histogram of the loop too")

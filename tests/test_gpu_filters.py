@@ -258,9 +258,10 @@ def test_device_reverse_complement_matches_reference_cli(gpu_required, tmp_path)
 
 @pytest.mark.parametrize("keep_weak", [False, True])
 def test_device_ranking_equals_host_sort(gpu_required, keep_weak):
-    """vsx_align_pairs_ranked (flag + scan + per-query stable sort by identity + gather on the device, vsx_rank.hip) against a
-    host sort of the full vsx_align_pairs_filtered result: same kept set, same order (query, id descending, pair order), same
-    fields (the pipelined form of the same path runs in tests/test_gpu_scale.py: 2.0 M pairs)."""
+    """vsx_align_pairs_ranked (kept-pair lists from the traceback, gather on the device in vsx_rank.hip, order on the host) against
+    a host sort of the full vsx_align_pairs_filtered result: same kept set, same order (query, id descending, pair order), same
+    fields (the pipelined form of the same path runs in tests/test_gpu_scale.py: 2.0 M pairs).  A second input whose query keys
+    are not contiguous (A, B, A): every run of equal keys is its own group, the runs in list order."""
     from vsearch_amd import Aligner
     rng = random.Random(7)
     db, fam = common.family_db(rng, 12, 10, 260, div=0.06)
@@ -275,6 +276,15 @@ def test_device_ranking_equals_host_sort(gpu_required, keep_weak):
         S = al.sequences(db)
         full = al.align_pairs_oneshot(S, S, qi, ti, filter=flt)
         rk = al.align_pairs_ranked(S, S, qi, ti, flt, keep_weak=keep_weak)
+        qa, qb = 0, 10                                              # two queries of different families
+        ta = np.array([t for t in range(1, n - 2) if t != qa], np.uint32)
+        tb = np.array([t for t in range(n - 2) if t != qb], np.uint32)
+        ta1, ta2 = ta[0::2], ta[1::2]                               # (both halves hold members of qa's family)
+        qi2 = np.concatenate([np.full(len(ta1), qa), np.full(len(tb), qb), np.full(len(ta2), qa)]).astype(np.uint32)
+        ti2 = np.concatenate([ta1, tb, ta2]).astype(np.uint32)
+        run2 = np.concatenate([np.zeros(len(ta1), int), np.ones(len(tb), int), np.full(len(ta2), 2)])
+        full2 = al.align_pairs_oneshot(S, S, qi2, ti2, filter=flt)
+        rk2 = al.align_pairs_ranked(S, S, qi2, ti2, flt, keep_weak=keep_weak)
     keep = [k for k in range(len(qi)) if full.verdict[k] == 1 or (keep_weak and full.verdict[k] == 2)]
     # identity of the filter (iddef 2) recomputed from the row is not needed: the order key is (query, -id, pair) and the id
     # comes back from the device; check it is consistent with matches / internal length and monotone inside every query
@@ -294,3 +304,14 @@ def test_device_ranking_equals_host_sort(gpu_required, keep_weak):
     assert sorted(rk["undecided"].tolist()) == und and len(und) == (n - 1) + (n - 2)
     overflowed = [k for k in und if int(ti[k]) == n - 2]
     assert len(overflowed) == n - 2 and all(full.row(k)[0] == 32767 and full.row(k)[5] == "" for k in overflowed)
+    # the non-contiguous input
+    keep2 = [k for k in range(len(qi2)) if full2.verdict[k] == 1 or (keep_weak and full2.verdict[k] == 2)]
+    assert sorted(rk2["pair"].tolist()) == keep2
+    assert all(sum(1 for k in keep2 if run2[k] == r) >= 2 for r in range(3))
+    pos2 = {int(p): j for j, p in enumerate(rk2["pair"])}
+    for k in keep2:
+        assert (int(rk2["score"][pos2[k]]), int(rk2["aligned"][pos2[k]]), int(rk2["matches"][pos2[k]]), int(rk2["mismatches"][pos2[k]]),
+                int(rk2["gaps"][pos2[k]]), rk2["cigar"][pos2[k]]) == full2.row(k), k
+    order2 = sorted(keep2, key=lambda k: (int(run2[k]), -float(rk2["id"][pos2[k]]), k))
+    assert rk2["pair"].tolist() == order2
+    assert len(rk2["undecided"]) == 0

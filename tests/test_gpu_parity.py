@@ -334,7 +334,7 @@ def test_chunked_plan_equals_single_chunk(gpu_required, oracle):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("env", [
-    {"VSX_TRACEBACK": "dirs"}, {"VSX_TB_ARITH": "packed"}, {"VSX_SCORE": "arith"}, {"VSX_NO_SHARE_SUB": "1"}, {"VSX_ROWS": "4"},
+    {"VSX_TB_ARITH": "packed"}, {"VSX_NO_SHARE_SUB": "1"}, {"VSX_ROWS": "4"},
     {"VSX_TILT": "0"}, {"VSX_TILT": "0", "VSX_ROWS": "4"}, {"VSX_MAX3": "0"}, {"VSX_MAX3": "0", "VSX_ROWS": "4"},
     {"VSX_SPARSE": "0"}, {"VSX_SPARSE": "0", "VSX_MAX3": "0"},
     # r06: single-strip launches run the ONE variants of the TILT kernels by default; VSX_ONESTRIP=0 keeps the general (multi-strip capable)
@@ -342,8 +342,8 @@ def test_chunked_plan_equals_single_chunk(gpu_required, oracle):
     {"VSX_ONESTRIP": "0"}, {"VSX_ONESTRIP": "0", "VSX_SPARSE": "0"}, {"VSX_ONESTRIP": "0", "VSX_SPARSE": "0", "VSX_MAX3": "0"},
 ], ids=lambda e: "+".join(f"{k}={v}" for k, v in e.items()))
 def test_alternate_kernel_modes(gpu_required, env):
-    """the A/B switches of DESIGN.md section 8 select other kernel variants (stored direction bits, saturating packed traceback,
-    table-free scores, unshared subtraction, many strips, plain instead of tilted coordinates, the 16-bit TILT class instead of its
+    """the switches of DESIGN.md section 8 select other kernel variants (saturating packed traceback,
+    unshared subtraction, many strips, plain instead of tilted coordinates, the 16-bit TILT class instead of its
     MAX3 sub-class -- r02's default, which the fixtures otherwise reach only for 1 900 < Q + D < 3 900; r05: every task a whole wave --
     the golden fixtures are one-target tasks, which by default share their waves four at a time): each must reproduce the golden vectors and the torture slice"""
     import subprocess
@@ -538,8 +538,8 @@ def test_sparse_task_classes(gpu_required, oracle, name):
         p.close()
         Qs.close()
         Ts.close()
-    if os.environ.get("VSX_SPARSE") == "0" or os.environ.get("VSX_TILT") == "0" or os.environ.get("VSX_TRACEBACK") == "dirs" \
-            or os.environ.get("VSX_TB_ARITH") == "packed" or os.environ.get("VSX_SCORE") == "arith" or os.environ.get("VSX_ROWS"):
+    if os.environ.get("VSX_SPARSE") == "0" or os.environ.get("VSX_TILT") == "0" \
+            or os.environ.get("VSX_TB_ARITH") == "packed" or os.environ.get("VSX_ROWS"):
         pass                                   # (re-run by test_alternate_kernel_modes: other classes, same results)
     elif info["tasks_tilted"] == 0:
         assert info["tasks_sparse"] == 0 and info["waves"] == info["tasks"], info

@@ -353,7 +353,7 @@ class Aligner:
         return RawResults(res)
 
     def align_pairs_ranked(self, queries, targets, qidx, tidx, filter, keep_weak=False):
-        """vsx_align_pairs_ranked: the pairs the filter keeps, ranked and compacted on the device (queries in list order, id
+        """vsx_align_pairs_ranked: the pairs the filter keeps, ranked and compacted on the device (runs of equal query index in list order, id
         descending, then list order).  -> dict of numpy arrays (pair, score, aligned, matches, mismatches, gaps, verdict, id),
         cigar list, undecided pair indices"""
         lib = _lib.load()

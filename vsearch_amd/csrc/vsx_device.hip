@@ -12,7 +12,7 @@
 //     and E / the left-neighbour H never leave VGPRs;
 //   * the column descriptor (target symbol pair, column penalties, score delta) travels down the
 //     same DPP pipeline; lane 0 is fed from a 16-column block parked in LDS once per 16 steps;
-//   * default (CKPT): no direction bits are stored.  Every step each lane stores the (H, F) pair it hands to the next pipeline
+//   * no direction bits are stored.  Every step each lane stores the (H, F) pair it hands to the next pipeline
 //     position (row checkpoints) and every 16 steps its column state hprev[R], E[R] (column checkpoints); the traceback kernel
 //     (one lane per pair: vsx_traceback_tilt_kernel for the tilted class -- r04: position-synchronous iterations, two rows of a pair
 //     per register -- vsx_traceback_ck_kernel for the plain classes) recomputes the direction bits only for the <= R x 16 tiles
@@ -20,9 +20,6 @@
 //   * default arithmetic (TILT, tasks whose score range the planner can bound): tilted coordinates X* = X + (i + j) g remove
 //     F - R and E - R from the interior (7 instructions per lane-row); values biased into unsigned halves so that the add and
 //     the subtraction are 32-bit ops over both halves.  Exact: every maximum compares two values of the same cell;
-//   * VSX_TRACEBACK=dirs keeps the first design: the 4 direction bits per cell are the SIGN bits of four saturating
-//     subtractions (a > b  <=>  ssub(b, a) < 0, exact under saturation), funnelled into 16-bit fields with v_lshrrev_b32 +
-//     v_bfi_b32, R/4 dwords per lane and step, walked by vsx_traceback_kernel;
 //   * no MFMA: this is a max-plus recurrence on int16, bound by VALU issue.
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -57,8 +54,6 @@ DEV u32 pmad(u32 a, u32 b, u32 c) { return UI((us2) (U2(a) * U2(b) + U2(c))); } 
 DEV u32 pashr15(u32 a) { return UI((s2) (S2(a) >> (s2){15, 15})); }                      // v_pk_ashrrev_i16
 DEV u32 bfi(u32 mask, u32 a, u32 b) { return (a & mask) | (b & ~mask); }                 // v_bfi_b32
 // Pinned encodings: hipcc otherwise rewrites these idioms into v_cmp/v_cndmask/v_perm sequences.
-DEV u32 a_pk_minu(u32 a, u32 b) { u32 r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
-DEV u32 a_pk_mad(u32 a, u32 b, u32 c) { u32 r; asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c)); return r; }
 DEV u32 a_bfi(u32 mask, u32 a, u32 b) { u32 r; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(mask), "v"(a), "v"(b)); return r; }
 DEV u32 a_bfi_v(u32 mask, u32 a, u32 b) { u32 r; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(a), "v"(b)); return r; }
 DEV u32 a_bfi_vs(u32 mask, u32 a, u32 b) { u32 r; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(a), "s"(b)); return r; }
@@ -75,17 +70,14 @@ DEV u32 dpp_rol1(u32 src) { return (u32) __builtin_amdgcn_update_dpp((int) src, 
 
 
 // ---------------------------------------------------------------------------------------------
-// DP kernel: scores + direction bits.  R = query rows per lane.  GENERIC = score lookup through a
-// 16 KB LDS table (any IUPAC / unknown symbol in the QUERY); the fast variant requires a pure
-// A/C/G/T(U) query and derives the score from an XOR of the 4-bit codes (targets may contain
-// anything: an ambiguous target symbol scores a per-column constant against unambiguous rows).
+// DP kernel: scores + checkpoints.  R = query rows per lane.  Scores are looked up in a query
+// profile in LDS (any IUPAC / unknown symbol on either side).
 // ---------------------------------------------------------------------------------------------
 // TRACK = false drops the running H min/max (the overflow rule): the planner selects it only for tasks
 // whose score range provably stays inside (SHRT_MIN + max(go+ge), SHRT_MAX) -- see vsx_host.cpp no_overflow_possible().
-// CKPT = true replaces the 4 direction bits per cell by CHECKPOINTS: every step each lane stores the (H, F) pair it
-// hands to the next pipeline position (row checkpoints, 8 B) and every 16 steps its whole column state hprev[R], E[R]
-// (column checkpoints); the traceback kernel recomputes the direction bits only for the <= R x 16 tiles the path
-// crosses.  Same bytes to HBM, ~40 % fewer VALU cycles per cell (the sign-bit funnel is gone).
+// No direction bits are stored, only CHECKPOINTS: every step each lane stores the (H, F) pair it hands to the next
+// pipeline position (row checkpoints, 8 B) and every 16 steps its whole column state hprev[R], E[R] (column
+// checkpoints); the traceback kernel recomputes the direction bits only for the <= R x 16 tiles the path crosses.
 // column checkpoint of one (strip, 16-step block): [group of G lanes][block of 4 rows: hprev blocks, then E blocks][lane in
 // group][4] dwords -- a store instruction (one block, all lanes) writes G x 16 B runs of complete lines
 #define VSX_COLCK_G 64      // lanes per group.  64 = [block][lane][4]: a store instruction writes 1 KB of full lines (DP kernel 32.1 ms, traceback 7.8 ms);
@@ -100,19 +92,13 @@ DEV u32 dpp_rol1(u32 src) { return (u32) __builtin_amdgcn_update_dpp((int) src, 
 #define VSX_ROWCK_PAIR_DW(TILT_) ((TILT_) ? 192 : 256)                       // dwords of one two-step pair of a wave
 #define VSX_COLCK_NBH(RT_) (((RT_) + ((RT_) + 1) / 2 + 3) / 4)                                  // ... of ONE half of RT rows (mid-row class)
 #define VSX_COLCK_NB(R_, TILT_) ((TILT_) ? (VSX_MID(R_, true) ? 2 * VSX_COLCK_NBH((R_) / 2) : ((R_) + ((R_) + 1) / 2 + 3) / 4) : (2 * (R_)) / 4)   // 4-dword blocks per lane and column checkpoint
-// Slot of pipeline lane (g, l) inside a wave's checkpoint chunk (TILT class).  1: l * 4 + g -- the four lane groups of a task
+// Slot of pipeline lane (g, l) inside a wave's checkpoint chunk.  TILT class: l * 4 + g -- the four lane groups of a task
 // (= its 8 targets, whose tracebacks move through the same tiles most of the time) sit next to each other, so the lanes of
-// a traceback wave that work on one task read the same lines; 0: g * 16 + l (lane order).
-#ifndef VSX_CK_TASKMAJOR
-#define VSX_CK_TASKMAJOR 1
-#endif
-#define VSX_CK_SLOT(TILT_, g_, l_) (((TILT_) && VSX_CK_TASKMAJOR) ? ((l_) * 4 + (g_)) : ((g_) * 16 + (l_)))
+// a traceback wave that work on one task read the same lines; otherwise g * 16 + l (lane order).
+#define VSX_CK_SLOT(TILT_, g_, l_) ((TILT_) ? ((l_) * 4 + (g_)) : ((g_) * 16 + (l_)))
 #ifndef VSX_COLCK_CG
 #define VSX_COLCK_CG 64     // lanes per group of the compressed layout: [group][block][lane in group][4] dwords
 #endif
-// transposed layout (VSX_CKT, vsx_internal.h): one block = 64 slots x 12 dwords = 3 KB, written as three 1 KB stores
-#define VSX_CKT_BLOCK_DW 768
-#define VSX_COLCK_NCHUNK(R_) ((VSX_COLCK_NB(R_, true) + 2) / 3)      // 48-byte chunks per lane and column checkpoint
 #define VSX_COLCK_CDW(NB_, lane_, block_) ((((size_t) ((lane_) / VSX_COLCK_CG) * (size_t) (NB_) + (size_t) (block_)) * VSX_COLCK_CG + (size_t) ((lane_) % VSX_COLCK_CG)) * 4)
 // TILT = true (a sub-class of TOPPAD: checkpoints, LDS profile, no tracking): the kernel runs in TILTED coordinates,
 //   X*(i, j) = X(i, j) + (i + j) g   for X in {H, E, F},   g = the interior gap extension (both sides equal),
@@ -130,8 +116,7 @@ DEV u32 dpp_rol1(u32 src) { return (u32) __builtin_amdgcn_update_dpp((int) src, 
 // spills into the loop: 500 x 500 25.5 -> 30.8 ms) -- profiles/r03/r03c_occupancy_ab.txt.  A/B builds override VSX_FWD_WAVES
 // FEED2 (r05, prepared in r04 as experiments/dp_feed2.patch): the feed record of the look-ahead classes, see vsx_forward_kernel
 // r05 same-box A/B (profiles/r05/r05b_feed2_ab.txt, two runs each): DP 250 x 1000 22.73 -> 22.41 ms, 150 x 1000 16.65 -> 16.40, 150 x 300
-// 5.58 -> 5.45, 300 x 300 10.24 -> 10.20, 400 x 400 17.06 -> 17.12 (R = 26: level); parity suite + aligner soak green on the build.  Default ON.
-// (the default of VSX_FEED2 lives in vsx_internal.h: the planner needs it for the pair-profile classes)
+// 5.58 -> 5.45, 300 x 300 10.24 -> 10.20, 400 x 400 17.06 -> 17.12 (R = 26: level); parity suite + aligner soak green on the build.
 #ifndef VSX_FWD_WAVES
 #define VSX_FWD_WAVES(R_, TILT_) ((R_) <= 16 ? 4 : ((R_) <= 24 ? 3 : 2))
 #endif
@@ -185,13 +170,12 @@ DEV u32 pk_max3_bits(u32 a, u32 b, u32 c)            // IEEE maximum of three: t
 // 16.22 -> 15.6, 300 x 300 10.10 -> 9.76, 400 x 400 16.83 -> 16.07, 150 x 300 5.43 -> 5.22 (same box, two runs each).  The sparse-task
 // classes (NQ > 1) always were single-strip, which is why they compiled without spills (VERDICT r05 "next" 3b asked what they do not
 // keep live: the strip state).
-template <int R, bool GENERIC, bool TRACK, bool CKPT, bool TILT = false, bool MAX3 = false, int NQ = 1, bool PAIR = false, bool ONE = false>
+template <int R, bool TRACK, bool TILT = false, bool MAX3 = false, int NQ = 1, bool PAIR = false, bool ONE = false>
 __global__ void __launch_bounds__(PAIR ? 256 : 64) __attribute__((amdgpu_waves_per_eu(NQ == 1 ? (ONE ? VSX_FWD_WAVES_ONE(R, TILT) : VSX_FWD_WAVES(R, TILT)) : VSX_FWD_WAVES_NQ(R, NQ), 8)))
 vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                    const uint8_t * __restrict__ qc, const uint8_t * __restrict__ tc,
                    u32 * __restrict__ dir, uint2 * strip, VsxSlotOut * __restrict__ slot_out, const u32 ntasks)
 {
-  constexpr int ND = (R + 3) / 4;                  // direction dwords per lane per step
   // TOPPAD: pipeline position 0 holds fewer than R query rows.  In this class its spare slots sit ABOVE the real rows and
   // are made transparent -- each dummy row reproduces the top border chain, H = Htop(j), via a constant profile score
   // -ge (query-left extension) and a diagonal seeded with -go, so the first real row sees exactly Htop(j-1), Htop(j) and
@@ -199,7 +183,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
   // Needs the LDS profile (a per-row constant score), no min/max tracking (the dummies would pollute it) and
   // QR_q(interior) >= ge (the planner checks both, vsx_host.cpp no_overflow_possible()).  The traceback of this class
   // (vsx_traceback_ck_kernel<R, true>) uses the same slot layout.
-  constexpr bool TOPPAD = CKPT && GENERIC && !TRACK;
+  constexpr bool TOPPAD = !TRACK;
   static_assert(!TILT || TOPPAD, "tilted coordinates exist for the TOPPAD class only");
   const int tl = TILT ? P.tilt : 0;                // g of the tilt (P then holds the primed constants)
   // TILT values are additionally BIASED into unsigned 16 bits (x + 0x8000 per half; the planner's range proof keeps every
@@ -215,39 +199,33 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
   auto vsubk = [](u32 a, u32 b) -> u32 { return TILT ? a - b : ssub(a, b); };      // b >= 0 per half, a >= b per half
   auto vsub = [](u32 a, u32 b) -> u32 { return TILT ? psubw(a, b) : ssub(a, b); };
   auto vmax = [](u32 a, u32 b) -> u32 { return TILT ? pmaxu(a, b) : pmax(a, b); };
-  // GENERIC: query profile in LDS, QP[target code][row of the strip] = S[code][query symbol of the row] (int16).
+  // Query profile in LDS, QP[target code][row of the strip] = S[code][query symbol of the row] (int16).
   // Any IUPAC / unknown symbol on either side is handled by construction; one v_perm_b32 per row packs the two targets.
-  // TILT + VSX_CKT: the primed scores are 0 .. 255 (planner-checked), so the profile holds BYTES (half the LDS, half the reads;
+  // TILT: the primed scores are 0 .. 255 (planner-checked), so the profile holds BYTES (half the LDS, half the reads;
   // the same single v_perm_b32 per row widens them): QPb[code][position][RP rows], RP = R rounded up to a multiple of 4
   constexpr bool MIDCK = VSX_MID(R, TILT);          // second row checkpoint after row R/2 - 1, column checkpoints per half
   constexpr int RT = MIDCK ? R / 2 : R;
-  constexpr bool CKST = TILT && (VSX_CKT != 0);     // LDS-transposed checkpoint stores (A/B build)
-  static_assert(!(MAX3 && CKST), "the transposed A/B layout predates the MAX3 class");
-  constexpr bool QPL = TILT && (VSX_QPL != 0);      // byte profile, read one step ahead
-  constexpr bool QP8 = CKST || QPL;
+  constexpr bool QPL = TILT;                        // byte profile, read one step ahead
   constexpr int RP = (R + 3) & ~3;
   static_assert(NQ == 1 || NQ == 2 || NQ == 4, "tasks per wave");
-  static_assert(NQ == 1 || (TILT && VSX_QPL != 0 && !VSX_CKT), "the sparse-task classes exist for the look-ahead TILT kernels only");
-  static_assert(!PAIR || (NQ == 1 && TILT && VSX_QPL != 0 && VSX_FEED2 != 0 && !VSX_CKT && GENERIC), "the pair-profile classes extend the FEED2 look-ahead kernels");
+  static_assert(NQ == 1 || TILT, "the sparse-task classes exist for the look-ahead TILT kernels only");
+  static_assert(!PAIR || (NQ == 1 && TILT), "the pair-profile classes extend the FEED2 look-ahead kernels");
   constexpr int WPB = PAIR ? 4 : 1;                  // waves per workgroup
   constexpr int QPBYTES = 16 * 16 * RP;              // one byte profile
   // pair profile: row stride RPP dwords with RPP / 4 odd, so that the 16 lanes of a group (each reading whole 16-byte quarters) start
   // in sixteen different 4-bank groups
   constexpr int RPP = ((RP / 4) & 1) ? RP : RP + 4;
   __shared__ __attribute__((aligned(16))) u32 PPf[PAIR ? 16 * 16 * RPP : 4];
-  __shared__ __attribute__((aligned(16))) int16_t QP[(GENERIC && !PAIR) ? (QP8 ? (NQ * QPBYTES) / 2 : 16 * 16 * R) : 8];
-  uint8_t * const QPb = reinterpret_cast<uint8_t *>(QP);
-  // checkpoint staging of the transposed layout: [slot][12 dwords]
-  __shared__ __attribute__((aligned(16))) u32 RS[CKST ? 64 * 12 : 4];
+  __shared__ __attribute__((aligned(16))) int16_t QP[!PAIR ? (QPL ? (NQ * QPBYTES) / 2 : 16 * 16 * R) : 8];
   // feed block of the column pipeline: [lane group][column of the 16-block] (sym, QR_t, R_t, H) and F -- written once per 16
   // steps by the 16 lanes of a group, read back one column per step for lane 0 (replaces five v_mov_b32_dpp row_ror rotations)
-  constexpr int FSZ = (TILT && VSX_QPL ? 2 : 1) * 4 * 16;             // feed entries of one wave
+  constexpr int FSZ = (TILT ? 2 : 1) * 4 * 16;                         // feed entries of one wave
   __shared__ uint4 FEED4a[FSZ * WPB];                                  // QPL: two blocks (the next one is built a step early)
-  __shared__ u32 FEEDFa[FSZ * WPB], FEEDN[GENERIC ? 1 : 4 * 16];
+  __shared__ u32 FEEDFa[FSZ * WPB];
   // FEED2 (the classes with the look-ahead byte profile): the record of a column is (byte offsets of the two targets' profile rows in
   // the halves of one dword, symbols + flags, H, F) -- an interior step reads H and F of its column and the offsets of the next column
   // from three neighbouring dwords, and the profile addresses are two adds -- and (QR_t, R_t) live in a second array for phase B
-  constexpr bool FEED2 = (VSX_FEED2 != 0) && TOPPAD && (TILT && (VSX_QPL != 0));
+  constexpr bool FEED2 = TILT;
   __shared__ uint2 FEEDBa[FEED2 ? 2 * 4 * 16 * WPB : 1];
 
   const int wv = PAIR ? __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) : 0;      // wave of the workgroup = task of the group of four (scalar: the task's fields stay in SGPRs)
@@ -298,7 +276,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
       const int pad = TOPPAD ? R - rcnt0 : 0;    // dummy slots above the rows of position 0
       const int i0 = first ? -pad : rcnt0 + (L - 1) * R;
 
-      if (GENERIC)
+      // ---- query profile of this strip (LDS) ----
         {
           __syncthreads();                           // previous strip's readers are done
           if (PAIR)
@@ -323,7 +301,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                   PPf[(pr * 16 + row / RP) * RPP + rr] = ((u32) va & 0xffu) | (((u32) vb & 0xffu) << 16);
                 }
             }
-          else if (QP8)
+          else if (QPL)
             {
               // (NQ > 1: the 64 / NQ lanes of a sub-task fill THEIR profile from their own task's query)
               constexpr int LPT = 64 / NQ;
@@ -365,7 +343,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
       u32 hprev[R];      // H(i, j-1): left neighbour, next column's diagonal for row i+1
       u32 hnext[R];      // its ping-pong partner
       u32 E[R];          // E(i, j)
-      u32 ac[R];         // query symbol of the row (fast: code in both halves; generic: code << 8)
+      u32 ac[R];         // scratch of the int16 profile reads (rows r+2, r+3)
 #pragma unroll
       for (int r = 0; r < R; ++r)
         {
@@ -373,8 +351,6 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
           const bool dummy = TOPPAD && first && r < pad;
           if (i > Q - 1) i = Q - 1;                // junk rows (skipped or idle lanes): any valid address
           if (i < 0) i = 0;
-          const u32 a = qq[i];
-          ac[r] = a | (a << 16);
           u32 hl = bpack(P.hleft[i]);
           u32 e0 = vsub(hl, (i < Q - 1) ? P.qrq_i_pk : P.qrq_r_pk);
           if (dummy)
@@ -394,11 +370,11 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
       const u32 rq_last = lastpos ? P.rq_r_pk : P.rq_i_pk;
 
       // ---- column pipeline ----
-      u32 sym = 0, nd = 0, qrt = 0, rt = 0;        // this lane's current column descriptor (FEED2: sym = the profile byte offsets)
+      u32 sym = 0, qrt = 0, rt = 0;                // this lane's current column descriptor (FEED2: sym = the profile byte offsets)
       u32 symf = 0;                                // FEED2: symbols + flags of the column, shifted along in phase B only (no column in
                                                    // flight at the switch is a last column: 0 is what every lane would hold)
       u32 outH = 0, outF = 0;                      // H(bottom row, j), F(bottom row + 1, j)
-      u32 f_sym = 0, f_nd = 0, f_qrt = 0, f_rt = 0, f_H = 0, f_F = 0;   // 16-column feed block
+      u32 f_sym = 0, f_qrt = 0, f_rt = 0, f_H = 0, f_F = 0;   // 16-column feed block
       u32 rawA = 0, rawB = 0;
       int rawH = 0;
       uint2 rawS = make_uint2(0, 0);
@@ -431,12 +407,6 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                   prefetch(blk + 1);
                   return;
                 }
-              auto mne = [&](u32 code) -> int {     // score of an unambiguous query row vs `code` when codes differ
-                const bool unamb = (code != 0) && ((code & (code - 1)) == 0);
-                return unamb ? P.mismatch : ((P.n_mismatch && code == 15) ? P.mismatch : 0);
-              };
-              const u32 ndA = (u32) (mne(rawA) - P.match) & 0xffffu;
-              const u32 ndB = (u32) (mne(rawB) - P.match) & 0xffffu;
               const u32 qA = (u32) ((c < DA - 1) ? P.qrt_i : P.qrt_r) & 0xffffu;   // :1719-1753
               const u32 qB = (u32) ((c < DB - 1) ? P.qrt_i : P.qrt_r) & 0xffffu;
               const u32 rA = (u32) ((c < DA - 1) ? P.rt_i : P.rt_r) & 0xffffu;
@@ -444,7 +414,6 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               const u32 sA = rawA | ((c == DA - 1) ? 0x100u : 0u) | ((c < DpA) ? 0x200u : 0u);
               const u32 sB = rawB | ((c == DB - 1) ? 0x100u : 0u) | ((c < DpB) ? 0x200u : 0u);
               f_sym = sA | (sB << 16);
-              f_nd = ndA | (ndB << 16);
               f_qrt = qA | (qB << 16);
               f_rt = rA | (rB << 16);
               if (s == 0)
@@ -472,7 +441,6 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                   FEED4[fo + gw * 16 + l] = make_uint4(f_sym, f_qrt, f_rt, f_H);
                   FEEDF[fo + gw * 16 + l] = f_F;
                 }
-              if (!GENERIC) FEEDN[gw * 16 + l] = f_nd;
               prefetch(blk + 1);
       };
       // QPL: byte profile rows of BOTH targets for one step, in registers ([target][4 rows per dword]); two sets ping-pong with
@@ -552,21 +520,6 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
       // mid-row checkpoints: a third region behind the column checkpoints, laid out like the row checkpoints
       u32 * const mck_base = dir + T.dir_off + ck_rowdw + (size_t) nstrips * ck_nblk * CK_COL_DW
                              + ((((size_t) s * steps) >> 1) * 64 + ck_slot) * CK_LANE_DW;                           // + (t >> 1) * 192
-      // transposed layout: block bases (steps is a multiple of 8 there); a lane adds (k * 64 + lane) * 4 dwords per store
-      u32 * const rck_blk = dir + T.dir_off + (((size_t) s * steps) >> 3) * VSX_CKT_BLOCK_DW;                       // + (t >> 3) * 768
-      u32 * const cck_blk = dir + T.dir_off + (((size_t) nstrips * steps) >> 3) * VSX_CKT_BLOCK_DW
-                            + (size_t) s * ck_nblk * VSX_COLCK_NCHUNK(R) * VSX_CKT_BLOCK_DW;                        // + ((t >> 4) * NCHUNK + c) * 768
-      // one 3 KB block: LDS -> HBM as it lies (three full 1 KB stores); the barriers order the lanes' LDS accesses (one wave)
-      auto flush_block = [&](u32 * gdst) __attribute__((always_inline)) {
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          {
-            const u32x4 v = *reinterpret_cast<const u32x4 *>(RS + (k * 64 + lane) * 4);
-            __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(gdst + (k * 64 + lane) * 4));
-          }
-        __syncthreads();
-      };
 
       // STEADY (the part of phase A after the pipeline has filled, t >= 15): every lane that owns rows is inside its targets, so the
       // per-lane activity test and its EXEC mask are dropped (lanes beyond the query's positions compute junk nobody reads).
@@ -609,7 +562,6 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               load_profile(pn, symn);
             }
           else sym = dpp_shr1(fv.x, sym);
-          if (!GENERIC) nd = dpp_shr1(FEEDN[gw * 16 + (t & 15)], nd);
           if (!INTERIOR)
             {
               if (FEED2)
@@ -628,15 +580,14 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
           if (active)
             {
               const u32 code = sym & 0x000F000Fu;
-              const int16_t * qpA = QP + (code & 0xFu) * (16 * R) + l * R;      // GENERIC only
+              const int16_t * qpA = QP + (code & 0xFu) * (16 * R) + l * R;
               const int16_t * qpB = QP + (code >> 16) * (16 * R) + l * R;
               u32 pa = 0, pb = 0;                                               // two rows' scores per dword
               u32 Hd = diag;
               u32 F = inF;
               u32 smn = 0x7FFF7FFFu, smx = 0x80008000u;
-              u32 acc = 0, h2 = 0;
+              u32 h2 = 0;
               u32 capH = 0, capF = 0, capmn = 0, capmx = 0;    // position 0: state after its last real row
-              u32 dw[ND];
               u32 lastL = 0, lastEL = 0;
               u32 midH = 0, midF = 0;
               // SHARED: the interior query-row and target-column gap penalties coincide (planner flag P.share_sub) and no
@@ -649,27 +600,19 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               // he - e alone: no h1 of its own (the row takes the three-way maximum like the others), no h1 - E, no OR.  The planner
               // admits a pair to the MAX3 class only with go_q(right end) > 0 (vsx_host.cpp tilt_possible()); phase B needs
               // left(D - 1) by itself and keeps the long form.
-              constexpr bool LASTFAST = MAX3 && SHARED && CKPT;
+              constexpr bool LASTFAST = MAX3 && SHARED;
 #pragma unroll
               for (int r = 0; r < R; ++r)
                 {
                   u32 V;
                   if (PAIR) V = pp[r];
-                  else if (GENERIC && QP8)
+                  else if (QPL)
                     {
-                      if ((r & 3) == 0)
-                        {
-                          if (QPL) { pa = pc[0][r >> 2]; pb = pc[1][r >> 2]; }
-                          else
-                            {
-                              pa = *reinterpret_cast<const u32 *>(QPb + (code & 0xFu) * (16 * RP) + l * RP + r);
-                              pb = *reinterpret_cast<const u32 *>(QPb + (code >> 16) * (16 * RP) + l * RP + r);
-                            }
-                        }
+                      if ((r & 3) == 0) { pa = pc[0][r >> 2]; pb = pc[1][r >> 2]; }
                       // byte r & 3 of the A rows -> low half, of the B rows -> high half, zero-extended (selector 0x0C = 0x00)
                       V = __builtin_amdgcn_perm(pb, pa, 0x0C040C00u + 0x00010001u * (u32) (r & 3));
                     }
-                  else if (GENERIC)
+                  else
                     {
                       if (R % 2 == 0)
                         {
@@ -692,7 +635,6 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                         }
                       else V = (u32) (uint16_t) qpA[r] | ((u32) (uint16_t) qpB[r] << 16);
                     }
-                  else V = a_pk_mad(a_pk_minu(ac[r] ^ code, 0x00010001u), nd, P.match_pk);
                   // onestep (:765-780)
                   const u32 h0 = vadd(Hd, V);
                   // (row R-1 keeps the two-step maximum where the leave-column tracking needs h1 = max(h0, F) on its own: the steps of
@@ -709,16 +651,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                   const u32 hf = (SHARED && r < R - 1) ? he : vsub(h2, qrt);
                   const u32 f = (TILT && INTERIOR) ? F : vsub(F, rt);                      // tilted interior: R' = 0
                   const u32 e = (TILT && INTERIOR && r < R - 1) ? E[r] : vsub(E[r], rq);   // (row R-1 may be the query's last row)
-                  if (CKPT && r == R - 1) { lastL = LASTFAST ? 0u : vsub(h1, E[r]); lastEL = vsub(he, e); }     // the last row's left / ext-left diffs
-                  if (!CKPT)
-                    {
-                      const u32 dU = ssub(h0, F);          // sign <=> F > H      (up)
-                      const u32 dL = ssub(h1, E[r]);       // sign <=> E > H      (left)
-                      const u32 dEU = ssub(hf, f);         // sign <=> F-R > H-QR (extend up)
-                      const u32 dEL = ssub(he, e);         // sign <=> E-R > H-QR (extend left)
-                      acc = funnel(funnel(funnel(funnel(acc, dU), dL), dEU), dEL);
-                      if ((r & 3) == 3 || r == R - 1) dw[r >> 2] = acc;
-                    }
+                  if (r == R - 1) { lastL = LASTFAST ? 0u : vsub(h1, E[r]); lastEL = vsub(he, e); }     // the last row's left / ext-left diffs
                   F = vmax(f, hf);
                   E[r] = vmax(e, he);
                   if (MIDCK && r == RT - 1) { midH = h2; midF = F; }          // what row R/2 - 1 hands to row R/2
@@ -735,19 +668,18 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               outH = hl;
               outF = F;
               diag = inH;
-              if (CKPT)
-                {
-                  // (the steady loop tracks lv1 + l instead, i.e. the STEP t = j + l at which cont was false: t is wave-uniform, an
-                  //  SGPR operand of the select, so no per-step VALU work forms the column; the loops below convert before and after)
-                  const u32 jpk = (u32) j | ((u32) j << 16);
-                  if (!INTERIOR)
-                    {
-                      const u32 atlast = a_pk_ashr15((FEED2 ? symf : sym) << 7);               // bit 8 (column == D-1)
-                      leave = a_bfi_v(atlast, a_bfi_v(a_pk_ashr15(lastL), lv1, jpk), leave);
-                    }
-                  const u32 lmask = a_pk_ashr15((MAX3 && INTERIOR) ? lastEL : (lastL | lastEL));
-                  lv1 = STEADY ? a_bfi_vs(lmask, lv1, (u32) t * 0x00010001u) : a_bfi_v(lmask, lv1, jpk);
-                }
+              {
+                // (the steady loop tracks lv1 + l instead, i.e. the STEP t = j + l at which cont was false: t is wave-uniform, an
+                //  SGPR operand of the select, so no per-step VALU work forms the column; the loops below convert before and after)
+                const u32 jpk = (u32) j | ((u32) j << 16);
+                if (!INTERIOR)
+                  {
+                    const u32 atlast = a_pk_ashr15((FEED2 ? symf : sym) << 7);               // bit 8 (column == D-1)
+                    leave = a_bfi_v(atlast, a_bfi_v(a_pk_ashr15(lastL), lv1, jpk), leave);
+                  }
+                const u32 lmask = a_pk_ashr15((MAX3 && INTERIOR) ? lastEL : (lastL | lastEL));
+                lv1 = STEADY ? a_bfi_vs(lmask, lv1, (u32) t * 0x00010001u) : a_bfi_v(lmask, lv1, jpk);
+              }
 
               // per-block h_min/h_max tracking incl. padded columns (:772-773, :1774-1786), gated per half
               if (TRACK)
@@ -762,68 +694,33 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                   score = a_bfi_v(lm, hl, score);            // S[(D+3)%4] of the last row (:1835-1836)
                 }
 
-              // [4-step block][lane][step in block][ND]: a lane's 4 consecutive steps share one 64 B line
-              // (4x fewer lines for the traceback walk) while a wave-step still lands in one 4 KB window
-              const size_t gt = (size_t) s * steps + t;
-              if (CKPT)
-                {
-                  if (!ODD) { pendH = outH; pendF = outF; }             // stored by the odd step below
-                  if (MIDCK) { if (!ODD) { pendMH = midH; pendMF = midF; } else { curMH = midH; curMF = midF; } }
-                }
-              else
-                {
-                  u32 * dp = dir + T.dir_off + (((gt >> 2) * 64 + lane) * 4 + (gt & 3)) * ND;
-                  if (ND == 4) *reinterpret_cast<uint4 *>(dp) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
-                  else if (ND == 2) *reinterpret_cast<uint2 *>(dp) = make_uint2(dw[0], dw[1]);
-                  else
-                    {
-#pragma unroll
-                      for (int w = 0; w < ND; ++w) dp[w] = dw[w];
-                    }
-                }
+              if (!ODD) { pendH = outH; pendF = outF; }             // stored by the odd step below
+              if (MIDCK) { if (!ODD) { pendMH = midH; pendMF = midF; } else { curMH = midH; curMF = midF; } }
               if (l == 15 && s + 1 < nstrips) strip_outp[j] = make_uint2(outH, outF);
             }
-          if (CKPT && CKST)
+          // row checkpoints [two-step pair][lane][2] uint2: one 16-byte store per lane and pair, so a wave writes
+          // 1 KB of full lines (steps is even: a pair never straddles two strips); halves that were not active hold junk
+          // nobody reads
+          if (!ODD) pend_on = active;
+          else if (pend_on || active)
             {
-              // transposed layout: the two-step pair goes to the lane's 48-byte segment of the staging block -- H of step i at
-              // dword i, the four difference bytes of the pair at dword 8 + i / 2 -- and every 8 steps the block leaves as it lies
-              if (!ODD) pend_on = active;
-              else
+              if (TILT)
                 {
+                  // bytes 0 / 2 of the two wrapped differences = the signed 8-bit H - F of the lo / hi target, steps t-1 and t
+                  // (unrolled block: one base per block, the pair's place in it a constant -- an immediate store offset)
+                  const size_t ckp = LEANFEED ? (size_t) ((t & ~15) >> 1) * 192 + (size_t) (((t & 15) >> 1) * 192) : (size_t) (t >> 1) * 192;
                   const u32 dpk = __builtin_amdgcn_perm(psubw(outH, outF), psubw(pendH, pendF), 0x06040200u);
-                  u32 * rs = RS + ck_slot * 12;
-                  const int i = t & 7;
-                  *reinterpret_cast<uint2 *>(rs + (i - 1)) = make_uint2(pendH, outH);
-                  rs[8 + (i >> 1)] = dpk;
-                  if (i == 7) flush_block(rck_blk + (size_t) (t >> 3) * VSX_CKT_BLOCK_DW);
-                }
-            }
-          else if (CKPT)
-            {
-              // row checkpoints [two-step pair][lane][2] uint2: one 16-byte store per lane and pair, so a wave writes
-              // 1 KB of full lines (steps is even: a pair never straddles two strips); halves that were not active hold junk
-              // nobody reads
-              if (!ODD) pend_on = active;
-              else if (pend_on || active)
-                {
-                  if (TILT && !CKST)
+                  __builtin_nontemporal_store((u32x3) {pendH + CK_REBIAS, outH + CK_REBIAS, dpk}, reinterpret_cast<u32x3 *>(rck_base + ckp));
+                  if (MIDCK)
                     {
-                      // bytes 0 / 2 of the two wrapped differences = the signed 8-bit H - F of the lo / hi target, steps t-1 and t
-                      // (unrolled block: one base per block, the pair's place in it a constant -- an immediate store offset)
-                      const size_t ckp = LEANFEED ? (size_t) ((t & ~15) >> 1) * 192 + (size_t) (((t & 15) >> 1) * 192) : (size_t) (t >> 1) * 192;
-                      const u32 dpk = __builtin_amdgcn_perm(psubw(outH, outF), psubw(pendH, pendF), 0x06040200u);
-                      __builtin_nontemporal_store((u32x3) {pendH + CK_REBIAS, outH + CK_REBIAS, dpk}, reinterpret_cast<u32x3 *>(rck_base + ckp));
-                      if (MIDCK)
-                        {
-                          const u32 dpm = __builtin_amdgcn_perm(psubw(curMH, curMF), psubw(pendMH, pendMF), 0x06040200u);
-                          __builtin_nontemporal_store((u32x3) {pendMH + CK_REBIAS, curMH + CK_REBIAS, dpm}, reinterpret_cast<u32x3 *>(mck_base + ckp));
-                        }
+                      const u32 dpm = __builtin_amdgcn_perm(psubw(curMH, curMF), psubw(pendMH, pendMF), 0x06040200u);
+                      __builtin_nontemporal_store((u32x3) {pendMH + CK_REBIAS, curMH + CK_REBIAS, dpm}, reinterpret_cast<u32x3 *>(mck_base + ckp));
                     }
-                  else
-                    __builtin_nontemporal_store((u32x4) {pendH, pendF, outH, outF}, reinterpret_cast<u32x4 *>(rck_base + (size_t) (t >> 1) * 256));
                 }
+              else
+                __builtin_nontemporal_store((u32x4) {pendH, pendF, outH, outF}, reinterpret_cast<u32x4 *>(rck_base + (size_t) (t >> 1) * 256));
             }
-          if (CKPT && (t & 15) == 15)
+          if ((t & 15) == 15)
             {
               // column checkpoint m = t / 16 of this lane: state after its column t - l (or its border state if it has
               // not started yet).  Layout VSX_COLCK_DW (R = 1: [strip][m][lane][2]).
@@ -854,30 +751,9 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                       }
                     return 0u;
                   };
-                  if (CKST)
-                    {
-                      // chunks of three 16-byte pieces per lane through the staging block: a lane's checkpoint is NCHUNK
-                      // contiguous 48-byte segments in HBM
-                      constexpr int NBC = VSX_COLCK_NB(R, true);
-#pragma unroll
-                      for (int c = 0; c < VSX_COLCK_NCHUNK(R); ++c)
-                        {
-#pragma unroll
-                          for (int pc = 0; pc < 3; ++pc)
-                            {
-                              const int z = 4 * (3 * c + pc);
-                              if (3 * c + pc < NBC)
-                                *reinterpret_cast<u32x4 *>(RS + ck_slot * 12 + pc * 4) = (u32x4) {flatc(z), flatc(z + 1), flatc(z + 2), flatc(z + 3)};
-                            }
-                          flush_block(cck_blk + ((size_t) (t >> 4) * VSX_COLCK_NCHUNK(R) + c) * VSX_CKT_BLOCK_DW);
-                        }
-                    }
-                  else
-                    {
 #pragma unroll
                   for (int z = 0; z < 4 * VSX_COLCK_NB(R, true); z += 4)
                     __builtin_nontemporal_store((u32x4) {flatc(z), flatc(z + 1), flatc(z + 2), flatc(z + 3)}, reinterpret_cast<u32x4 *>(cb + VSX_COLCK_CDW(VSX_COLCK_NB(R, true), ck_slot, z >> 2)));
-                    }
                 }
               else if (R % 2 == 0)
                 {
@@ -898,9 +774,9 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
       };
       // Phase A: steps before ANY lane of the wave reaches column D - 1 of one of its targets (lane l works on column
       // t - l <= t): every column in flight is interior.  Needs QR_q(interior) == QR_t(interior) for the shared
-      // subtraction (planner flag); the checkpoint kernels only.  Phase B: the general step for the rest.
+      // subtraction (planner flag).  Phase B: the general step for the rest.
       int t_switch = 0;
-      if (CKPT && P.share_sub)
+      if (P.share_sub)
         {
           int dmin = 0x7fffffff;
           if (DA > 0 && DA < dmin) dmin = DA;
@@ -991,109 +867,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
 }
 
 // ---------------------------------------------------------------------------------------------
-// Traceback: one lane per pair; follows backtrack16 (align_simd.cpp:1137-1235) over the direction
-// bits written above.  Emits statistics and the run-length op list (reverse order: last column first).
-// run word = (length << 2) | op,  op: 0 = M, 1 = I (gap in query, consumes target), 2 = D.
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-vsx_traceback_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
-                     const u32 * __restrict__ pair_slot, const u32 * __restrict__ pair_ids, u32 npairs,
-                     const uint8_t * __restrict__ qc, const uint8_t * __restrict__ tc,
-                     const u32 * __restrict__ dir, const VsxSlotOut * __restrict__ slot,
-                     u32 * __restrict__ slab, const uint64_t * __restrict__ slab_off,
-                     u32 * __restrict__ runs, uint64_t runs_capacity, unsigned long long * cursor,
-                     VsxPairOut * __restrict__ out)
-{
-  const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= npairs) return;
-  const u32 ts = pair_slot[k];
-  const u32 task = ts >> 3, sl = ts & 7;
-  const VsxTask & T = tasks[task];
-  const VsxSlotOut so = slot[ts];
-
-  VsxPairOut o;
-  o.pad = 0;
-  o.nruns = 0;
-  o.run_off = 0;
-  if (so.overflow)
-    {
-      o.score = 32767; o.aligned = 0; o.matches = 0; o.mismatches = 0; o.gaps = 0;
-      out[pair_ids[k]] = o;
-      return;
-    }
-
-  const int R = (int) T.rows;
-  const int ND = (R + 3) >> 2;
-  const int Q = (int) T.qlen;
-  const int D = (int) T.tlen[sl];
-  const int total_lanes = (Q + R - 1) / R;
-  const int rcnt0 = Q - (total_lanes - 1) * R;
-  const size_t steps = T.steps;
-  const int g = (int) (sl >> 1) + (int) T.group0;      // lane group of the DP wave (group0 > 0: a sparse task in a shared wave)
-  const bool hi = (sl & 1) != 0;
-  const uint8_t * __restrict__ q = qc + T.qoff;
-  const uint8_t * __restrict__ d = tc + T.toff[sl];
-  u32 * __restrict__ my = slab + slab_off[k];
-
-  int i = Q - 1, j = D - 1;
-  int L = total_lanes - 1;                 // pipeline position of row i
-  int r = (L == 0 ? rcnt0 : R) - 1;        // row inside that position
-  int op = -1;                             // -1 none, 0 M, 1 I, 2 D
-  u32 runlen = 0, nruns = 0;
-  u32 al = 0, ma = 0, mi = 0, ga = 0;
-
-  auto push = [&](int newop) {             // pushop (:1013-1030), run-length
-    if (newop == op) { ++runlen; return; }
-    if (op >= 0) my[nruns++] = (runlen << 2) | (u32) op;
-    op = newop;
-    runlen = 1;
-  };
-  auto row_up = [&]() {
-    --i;
-    if (--r < 0) { --L; r = (L == 0 ? rcnt0 : R) - 1; }
-  };
-
-  while (i >= 0 && j >= 0)
-    {
-      const int s = L >> 4, l = L & 15;
-      const size_t t = (size_t) j + (size_t) l;
-      const size_t gt = (size_t) s * steps + t;
-      const u32 w = dir[T.dir_off + (((gt >> 2) * 64 + (size_t) (g * 16 + l)) * 4 + (gt & 3)) * ND + (size_t) (r >> 2)];
-      const u32 hw = hi ? (w >> 16) : (w & 0xffffu);
-      int rid = R - 4 * (r >> 2);                          // every position funnels all R rows (dummy rows incl.)
-      if (rid > 4) rid = 4;                                // rows sharing this dword
-      const int pos = 16 - 4 * rid + 4 * (r & 3);
-      const u32 b = (hw >> pos) & 15u;                     // bit0 up, bit1 left, bit2 ext-up, bit3 ext-left
-      ++al;
-      if (op == 1 && (b & 8u)) { --j; push(1); }
-      else if (op == 2 && (b & 4u)) { row_up(); push(2); }
-      else if (b & 2u) { if (op != 1) ++ga; --j; push(1); }
-      else if (b & 1u) { if (op != 2) ++ga; row_up(); push(2); }
-      else
-        {
-          const u32 a = q[i], c = d[j];
-          if ((a & c) != 0 && !(P.n_mismatch && (a == 15 || c == 15))) ++ma; else ++mi;
-          row_up(); --j; push(0);
-        }
-    }
-  while (i >= 0) { ++al; if (op != 2) ++ga; --i; push(2); }
-  while (j >= 0) { ++al; if (op != 1) ++ga; --j; push(1); }
-  if (op >= 0) my[nruns++] = (runlen << 2) | (u32) op;     // finishop (:1033-1049)
-
-  // dense (unordered) allocation of the run list
-  const unsigned long long base = atomicAdd(cursor, (unsigned long long) nruns);
-  if (base + nruns <= runs_capacity)
-    for (u32 x = 0; x < nruns; ++x) runs[base + x] = my[x];
-
-  o.score = so.score;
-  o.aligned = (uint16_t) al; o.matches = (uint16_t) ma; o.mismatches = (uint16_t) mi; o.gaps = (uint16_t) ga;
-  o.nruns = nruns;
-  o.run_off = base;
-  out[pair_ids[k]] = o;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Traceback for the CKPT layout: one lane per pair.  The path is followed tile by tile; a tile is the
+// Traceback over the checkpoints: one lane per pair.  The path is followed tile by tile; a tile is the
 // part of one pipeline position (<= R rows) between two column checkpoints (<= 16 columns).  For the tile
 // under the cursor the lane recomputes the direction bits of the sub-rectangle above/left of the cursor
 // from the stored boundaries (left: column checkpoint or the left border; top: the row checkpoints of the
@@ -1215,7 +989,7 @@ vsx_traceback_ck_kernel(const VsxDevParams P, const VsxFilterDev FL, const VsxTa
   // MID (vsx_internal.h VSX_MID): the DP kernel also stored a row checkpoint after row R/2 - 1 of every position and laid the
   // column checkpoints out per half, so a tile is one HALF of a position: RT = R/2 rows.  The cursor keeps its position-level
   // row index r; hh = r / RT names the half, the tile's rows are slots hh * RT .. hh * RT + RT - 1 of the position.
-  static_assert(!MID || (CK8 && R % 2 == 0 && !VSX_CKT), "half-height tiles belong to the TILT class");
+  static_assert(!MID || (CK8 && R % 2 == 0), "half-height tiles belong to the TILT class");
   constexpr int RT = MID ? R / 2 : R;
   constexpr int ND = (RT + 3) / 4;
   constexpr bool TOPPAD = FAST;                    // slot layout of position 0, see vsx_forward_kernel
@@ -1252,8 +1026,7 @@ vsx_traceback_ck_kernel(const VsxDevParams P, const VsxFilterDev FL, const VsxTa
   const size_t steps = T.steps;
   const size_t nblk = (steps + 15) >> 4;
   const size_t rowsteps = ((size_t) nstrips * steps + 1) & ~(size_t) 1;
-  constexpr bool CKT = CK8 && (VSX_CKT != 0);      // transposed checkpoint layout (vsx_internal.h)
-  const size_t rowck_dw = CKT ? (((size_t) nstrips * steps) >> 3) * VSX_CKT_BLOCK_DW : (rowsteps >> 1) * VSX_ROWCK_PAIR_DW(CK8);
+  const size_t rowck_dw = (rowsteps >> 1) * VSX_ROWCK_PAIR_DW(CK8);
   constexpr size_t COL_DW = CK8 ? (size_t) 64 * 4 * VSX_COLCK_NB(R, true) : (size_t) 64 * (2 * R);     // column checkpoint dwords per wave
   const u32 * __restrict__ rowck = ck + T.dir_off;
   const u32 * __restrict__ colck = ck + T.dir_off + rowck_dw;
@@ -1326,37 +1099,6 @@ vsx_traceback_ck_kernel(const VsxDevParams P, const VsxFilterDev FL, const VsxTa
         if (e > 0 || par == 0) dst[(2 * e) * 64] = __builtin_amdgcn_perm(v[e].y, v[e].x, half_sel) ^ bias2;
         if (e < 8 || par == 1) dst[(2 * e + 1) * 64] = __builtin_amdgcn_perm(v[e].w, v[e].z, half_sel) ^ bias2;
       }
-  };
-  // transposed layout: the 17 steps gstart .. gstart + 16 of pipeline slot `slot` lie in (at most) three consecutive 8-step
-  // blocks, 48 contiguous bytes each: {H of the 8 steps, the 8 x 2 difference bytes}.  Nine 16-byte loads from <= 3 segments;
-  // entry cc + 1 of tbL = step gstart + cc.  Blocks outside [0, maxblk] are clamped (their entries are never used).
-  auto stage_top_t = [&](const u32 * rowbase, int slot, long gstart, long maxblk) {
-    const long b0 = gstart >> 3;                                 // floor, also for gstart = -1
-    const int o = (int) (gstart - 8 * b0);                       // 0 .. 7
-    Quad q[3][3];
-#pragma unroll
-    for (int e = 0; e < 3; ++e)
-      {
-        long b = b0 + e;
-        b = b < 0 ? 0 : (b > maxblk ? maxblk : b);
-        const u32 * src = rowbase + (size_t) b * VSX_CKT_BLOCK_DW + (size_t) slot * 12;
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) q[e][pc] = *reinterpret_cast<const Quad *>(src + pc * 4);
-      }
-#pragma unroll
-    for (int e = 0; e < 3; ++e)
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        {
-          const Quad & hq = q[e][i >> 2];
-          const u32 hw = (i & 3) == 0 ? hq.x : (i & 3) == 1 ? hq.y : (i & 3) == 2 ? hq.z : hq.w;
-          const Quad & dq = q[e][2];
-          const u32 dw2 = (i >> 1) == 0 ? dq.x : (i >> 1) == 1 ? dq.y : (i >> 1) == 2 ? dq.z : dq.w;
-          const u32 h = half_lo(hw, hi) & 0xffffu;
-          const int dd = (int) (int8_t) ((dw2 >> (8 * ((i & 1) * 2 + (hi ? 1 : 0)))) & 0xffu);
-          const int cc = 8 * e + i - o;
-          if (cc >= 0 && cc <= 16) tbL[(cc + 1) * 64 + tid] = h | ((h - (u32) dd) << 16);
-        }
   };
   auto inck = [&](u32 lo16) -> u32 { return FAST ? ((lo16 & 0xffffu) ^ ckb) : lo16; };     // a checkpoint value -> A's domain
   auto stage_symbols = [&](int c0) {
@@ -1465,9 +1207,6 @@ vsx_traceback_ck_kernel(const VsxDevParams P, const VsxFilterDev FL, const VsxTa
         {
           const int Lp = L - 1;
           const int sp = Lp >> 4, lp = Lp & 15;
-          if (CKT)
-            stage_top_t(rowck, VSX_CK_SLOT(true, g, lp), (long) ((size_t) sp * steps) + (long) (c0 - 1 + lp), (long) ((((size_t) nstrips * steps) >> 3)) - 1);
-          else
           stage_top(rowck + (size_t) VSX_CK_SLOT(CK8, g, lp) * (CK8 ? 3 : 4), VSX_ROWCK_PAIR_DW(CK8), (long) ((size_t) sp * steps) + (long) (c0 - 1 + lp),
                     (long) (rowsteps >> 1) - 1);
           if (c0 == 0) tbL[64 + tid] = vin((u32) (uint16_t) P.hleft[i0 - 1]);     // corner H(i0-1, -1)
@@ -1517,13 +1256,6 @@ vsx_traceback_ck_kernel(const VsxDevParams P, const VsxFilterDev FL, const VsxTa
                                    + (size_t) (hh * NBQ) * (4 * VSX_COLCK_CG);
 #pragma unroll
                   for (int b = 0; b < NBQ; ++b) fq[b] = *reinterpret_cast<const Quad *>(cb + (size_t) b * (4 * VSX_COLCK_CG));
-                }
-              else if (CKT)
-                {
-                  // piece b of the lane's checkpoint = piece b % 3 of its 48-byte segment in chunk b / 3
-                  const u32 * cb = colck + ((size_t) s * nblk + (size_t) (m - 1)) * VSX_COLCK_NCHUNK(R) * VSX_CKT_BLOCK_DW + (size_t) VSX_CK_SLOT(true, g, l) * 12;
-#pragma unroll
-                  for (int b = 0; b < NBQ; ++b) fq[b] = *reinterpret_cast<const Quad *>(cb + (size_t) (b / 3) * VSX_CKT_BLOCK_DW + (b % 3) * 4);
                 }
               else
                 {
@@ -1929,11 +1661,7 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
       const int total_lanes = ((int) Qb + R - 1) / R;
       const int rcnt0 = (int) Qb - (total_lanes - 1) * R;
       const int pad = R - rcnt0;                   // dummy slots above the rows of position 0 (TOPPAD layout)
-#ifdef VSX_TB_FORCE_ONE
-      const int nstrips = 1;                     // (A/B build only: every query single-strip; profiles/r06/r06t_tb_onestrip_ab.txt)
-#else
       const int nstrips = (total_lanes + 15) >> 4;
-#endif
       const size_t steps = stb;
       const size_t nblk = (steps + 15) >> 4;
       const size_t rowsteps = ((size_t) nstrips * steps + 1) & ~(size_t) 1;
@@ -1941,11 +1669,7 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
       const u32 * __restrict__ rowck = ck + dob;
       const u32 * __restrict__ colck = rowck + rowck_dw;
       const u32 * __restrict__ midck = colck + (size_t) nstrips * nblk * COL_DW;
-#ifdef VSX_TB_FORCE_ONE
-      const int s = 0, l = L;
-#else
       const int s = L >> 4, l = L & 15;
-#endif
       const int jj = busy ? j : 0;
       const int m = (jj + l) >> 4;
       const int c0 = (16 * m - l) > 0 ? 16 * m - l : 0;                     // tile 1 = columns c0 .. c0 + 15
@@ -1989,13 +1713,7 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
               }
             else
               {
-                
-#ifdef VSX_TB_FORCE_ONE
-                const int Lp = L - 1, sp = 0, lp = Lp;
-#else
                 const int Lp = L - 1, sp = Lp >> 4, lp = Lp & 15;
-#endif
-
                 base = rowck + (size_t) VSX_CK_SLOT(true, g, lp) * 3;
                 gstart = (long) ((size_t) sp * steps) + (long) (cst - 1 + lp);
               }
@@ -2516,19 +2234,19 @@ extern "C" hipError_t vsx_launch_purity(const uint8_t * d_codes, const uint64_t 
 
 #define VSX_FWD_GO(GRID_, ...) hipLaunchKernelGGL((vsx_forward_kernel<__VA_ARGS__>), dim3(GRID_), dim3(64), 0, st, P, d_tasks, q, t, dir, strip, slot, ntasks)
 #define VSX_FWD_GO4(GRID_, ...) hipLaunchKernelGGL((vsx_forward_kernel<__VA_ARGS__>), dim3(GRID_), dim3(256), 0, st, P, d_tasks, q, t, dir, strip, slot, ntasks)
-template <int R, bool CK>
-static hipError_t launch_fwd2(int generic, int track, int nq, int one, const VsxDevParams & P, const VsxTask * d_tasks, uint32_t ntasks,
+template <int R>
+static hipError_t launch_fwd2(int track, int nq, int one, const VsxDevParams & P, const VsxTask * d_tasks, uint32_t ntasks,
                               const uint8_t * q, const uint8_t * t, uint32_t * dir, uint2 * strip,
                               VsxSlotOut * slot, hipStream_t st)
 {
   if (nq == 8)
     {
       // the pair-profile classes: workgroups of four whole-wave tasks of one query (the planner launches whole groups)
-      if (!(P.tilt != 0 && CK && generic && !track) || (ntasks & 3u)) return hipErrorInvalidValue;
-      if constexpr (CK && R >= 4 && VSX_QPL != 0 && VSX_FEED2 != 0 && !VSX_CKT)
+      if (!(P.tilt != 0 && !track) || (ntasks & 3u)) return hipErrorInvalidValue;
+      if constexpr (R >= 4)
         {
           if (!one) return hipErrorInvalidValue;
-          if (P.max3) VSX_FWD_GO4(ntasks / 4, R, true, false, true, true, true, 1, true, true); else VSX_FWD_GO4(ntasks / 4, R, true, false, true, true, false, 1, true, true);
+          if (P.max3) VSX_FWD_GO4(ntasks / 4, R, false, true, true, 1, true, true); else VSX_FWD_GO4(ntasks / 4, R, false, true, false, 1, true, true);
           return hipGetLastError();
         }
       else return hipErrorInvalidValue;
@@ -2536,38 +2254,33 @@ static hipError_t launch_fwd2(int generic, int track, int nq, int one, const Vsx
   if (nq != 1)
     {
       // the sparse-task classes (NQ tasks per wave): TILT family only, R >= 4 (a one-row-per-lane wave has nothing to share)
-      if (!(P.tilt != 0 && CK && generic && !track && (nq == 2 || nq == 4))) return hipErrorInvalidValue;
-      if constexpr (CK && R >= 4 && VSX_QPL != 0 && !VSX_CKT)
+      if (!(P.tilt != 0 && !track && (nq == 2 || nq == 4))) return hipErrorInvalidValue;
+      if constexpr (R >= 4)
         {
           const uint32_t grid = (ntasks + (uint32_t) nq - 1) / (uint32_t) nq;
-          if (nq == 2) { if (P.max3) VSX_FWD_GO(grid, R, true, false, true, true, true, 2); else VSX_FWD_GO(grid, R, true, false, true, true, false, 2); }
-          else         { if (P.max3) VSX_FWD_GO(grid, R, true, false, true, true, true, 4); else VSX_FWD_GO(grid, R, true, false, true, true, false, 4); }
+          if (nq == 2) { if (P.max3) VSX_FWD_GO(grid, R, false, true, true, 2); else VSX_FWD_GO(grid, R, false, true, false, 2); }
+          else         { if (P.max3) VSX_FWD_GO(grid, R, false, true, true, 4); else VSX_FWD_GO(grid, R, false, true, false, 4); }
           return hipGetLastError();
         }
       else return hipErrorInvalidValue;
     }
   if (P.tilt != 0)
     {
-      if (!(CK && generic && !track)) return hipErrorInvalidValue;
-      if constexpr (CK)
+      if (track) return hipErrorInvalidValue;
+      if constexpr (R >= 4)
         {
-          if constexpr (R >= 4 && VSX_QPL != 0 && !VSX_CKT)
+          if (one)
             {
-              if (one)
-                {
-                  if (P.max3) VSX_FWD_GO(ntasks, R, true, false, true, true, true, 1, false, true);
-                  else VSX_FWD_GO(ntasks, R, true, false, true, true, false, 1, false, true);
-                  return hipGetLastError();
-                }
+              if (P.max3) VSX_FWD_GO(ntasks, R, false, true, true, 1, false, true);
+              else VSX_FWD_GO(ntasks, R, false, true, false, 1, false, true);
+              return hipGetLastError();
             }
-          if (P.max3 && !VSX_CKT) VSX_FWD_GO(ntasks, R, true, false, true, true, (VSX_CKT == 0));
-          else VSX_FWD_GO(ntasks, R, true, false, true, true);
         }
+      if (P.max3) VSX_FWD_GO(ntasks, R, false, true, true);
+      else VSX_FWD_GO(ntasks, R, false, true);
     }
-  else if (generic && track) VSX_FWD_GO(ntasks, R, true, true, CK);
-  else if (generic) VSX_FWD_GO(ntasks, R, true, false, CK);
-  else if (track) VSX_FWD_GO(ntasks, R, false, true, CK);
-  else VSX_FWD_GO(ntasks, R, false, false, CK);
+  else if (track) VSX_FWD_GO(ntasks, R, true);
+  else VSX_FWD_GO(ntasks, R, false);
   return hipGetLastError();
 }
 #undef VSX_FWD_GO
@@ -2576,34 +2289,18 @@ static hipError_t launch_fwd2(int generic, int track, int nq, int one, const Vsx
 // nq = tasks per wave: 1, or 2 / 4 for the sparse-task classes (tasks of <= 4 / <= 2 targets, TILT family, single-strip queries);
 // 8 = the pair-profile class: workgroups of four whole-wave tasks of one pure-ACGT query (ntasks a multiple of 4)
 // one != 0: every task of the launch is a single-strip query (ONE)
-extern "C" hipError_t vsx_launch_forward(int rows, int generic, int track, int ckpt, int nq, int one, VsxDevParams P, const VsxTask * d_tasks, uint32_t ntasks,
+extern "C" hipError_t vsx_launch_forward(int rows, int track, int nq, int one, VsxDevParams P, const VsxTask * d_tasks, uint32_t ntasks,
                                          const uint8_t * q, const uint8_t * t, uint32_t * dir, uint2 * strip,
                                          VsxSlotOut * slot, hipStream_t st)
 {
   if (ntasks == 0) return hipSuccess;
-#define FWDR(RR) case RR: return ckpt ? launch_fwd2<RR, true>(generic, track, nq, one, P, d_tasks, ntasks, q, t, dir, strip, slot, st) \
-                                       : launch_fwd2<RR, false>(generic, track, nq, one, P, d_tasks, ntasks, q, t, dir, strip, slot, st)
+#define FWDR(RR) case RR: return launch_fwd2<RR>(track, nq, one, P, d_tasks, ntasks, q, t, dir, strip, slot, st)
   switch (rows)
     {
     FWDR(1); FWDR(4); FWDR(8); FWDR(10); FWDR(12); FWDR(14); FWDR(16); FWDR(18); FWDR(20); FWDR(22); FWDR(24); FWDR(26); FWDR(28); FWDR(32);
     default: return hipErrorInvalidValue;
     }
 #undef FWDR
-}
-
-extern "C" hipError_t vsx_launch_traceback(VsxDevParams P, const VsxTask * d_tasks, const uint32_t * d_pair_slot,
-                                           const uint32_t * d_pair_ids, uint32_t npairs,
-                                           const uint8_t * q, const uint8_t * t,
-                                           const uint32_t * dir, const VsxSlotOut * slot,
-                                           uint32_t * slab, const uint64_t * slab_off,
-                                           uint32_t * runs, uint64_t runs_capacity, unsigned long long * cursor,
-                                           VsxPairOut * out, hipStream_t st)
-{
-  if (npairs == 0) return hipSuccess;
-  hipLaunchKernelGGL(vsx_traceback_kernel, dim3((npairs + 255) / 256), dim3(256), 0, st,
-                     P, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, dir, slot, slab, slab_off,
-                     runs, runs_capacity, cursor, out);
-  return hipGetLastError();
 }
 
 template <int R, bool MID>
@@ -2641,7 +2338,7 @@ extern "C" hipError_t vsx_launch_traceback_ck(int rows, int fast16, VsxDevParams
   static const bool v1_env = std::getenv("VSX_TB_V1") != nullptr;          // A/B: the first kernel for the TILT class too
   int dev_now = 0;
   if (hipGetDevice(&dev_now) != hipSuccess) { (void) hipGetLastError(); dev_now = 64; }
-  const bool v2 = g_tb_v1_dev[dev_now < 0 || dev_now > 64 ? 64 : dev_now].load(std::memory_order_relaxed) == 0 && !v1_env && !VSX_CKT;
+  const bool v2 = g_tb_v1_dev[dev_now < 0 || dev_now > 64 ? 64 : dev_now].load(std::memory_order_relaxed) == 0 && !v1_env;
 #define TBCK(RR) case RR: return (fast16 && P.tilt != 0 && v2 && RR >= 4) ? launch_tbtilt<RR, VSX_MID(RR, true)>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st) \
                                  : (fast16 && P.tilt != 0) ? launch_tbck<RR, true, true, VSX_MID(RR, true)>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st) \
                                  : fast16 ? launch_tbck<RR, true>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st) \
@@ -2658,8 +2355,6 @@ extern "C" hipError_t vsx_launch_traceback_ck(int rows, int fast16, VsxDevParams
 extern "C" uint64_t vsx_ckpt_dwords(uint64_t nstrips, uint64_t steps, uint64_t rows, int tilt)
 {
   const uint64_t nblk = (steps + 15) >> 4;
-  if (tilt && VSX_CKT)      // transposed layout: 3 KB blocks; steps is a multiple of 8
-    return ((nstrips * steps) >> 3) * VSX_CKT_BLOCK_DW + nstrips * nblk * (uint64_t) VSX_COLCK_NCHUNK(rows) * VSX_CKT_BLOCK_DW;
   const uint64_t rowck = (((nstrips * steps) + 1) >> 1) * VSX_ROWCK_PAIR_DW(tilt != 0);
   if (tilt)
     {

@@ -281,7 +281,6 @@ struct vsx_ctx {
   vsx_scoring sc {};
   bool force_fallback = false;      // a score/penalty left the 16-bit range: every pair -> sentinel
   bool tb_packed = false;           // VSX_TB_ARITH=packed: plan every task into the TRACK = 1 class (saturating packed ops, capture layout)
-  bool ckpt = true;                 // checkpoint + tile-recompute traceback (VSX_TRACEBACK=dirs selects stored direction bits)
   int pen[12] {};                   // clamped CELL penalties: go_q_l, go_t_l, go_q_i, go_t_i, go_q_r, go_t_r, ge_*
   VsxDevParams P {};
   DevBuf<int16_t> d_htop, d_hleft, d_matrix;
@@ -293,7 +292,7 @@ struct vsx_ctx {
   // plan i still reads its block, so the launch tails of one fill with the other's waves (a pipeline of small plans lost 15 %
   // to tails when every plan waited for its predecessor's traceback: r02 timeline in DESIGN 5).  ev_tb[s] = "the last traceback
   // that read block s has finished".
-  // r04: THREE blocks (VSX_CK_BLOCKS=2 restores two for A/B).  In a pipeline of slices the DP kernel of slice i + 2 used to wait for the
+  // r04: THREE blocks.  In a pipeline of slices the DP kernel of slice i + 2 used to wait for the
   // traceback of slice i, which shares the device with the DP kernel of slice i + 1 on bad terms (rocprofv3 trace of one call,
   // profiles/r03/r03v_e2e_trace_*.csv); with a third block only slice i + 3 waits for it.  A block is sized by the largest plan that
   // used it (<= 0.4 of what is free when it is made), 20 GB for the 200 k-pair slices of the bench shape.
@@ -301,7 +300,6 @@ struct vsx_ctx {
   std::atomic<uint64_t> req_hwm[2] {{0}, {0}};      // largest checkpoint block / slab a plan of this context asked for since the last reset (bytes)
   hipEvent_t ev_tb[3] = {nullptr, nullptr, nullptr};
   bool ev_tb_used[3] = {false, false, false};
-  int last_tb_slot = -1;            // the slot whose traceback was queued last (VSX_ALIGN_SERIAL: the next plan's DP waits for it)
   std::atomic<unsigned> plan_seq {0};
   // r06: which block a new plan takes (vsx_plan_create).  slot_refs[s] = live plans on block s (a plan is destroyed after its traceback
   // has finished), slot_stamp[s] = plan_seq at the last acquisition.
@@ -341,7 +339,7 @@ struct vsx_seqset {
   // not an upper-case A C G T U.  The aligner never sees it: alignment is case-blind in the reference too (chrmap_4bit)
   PoolBuf<uint8_t> d_lower;
   uint64_t lower_bytes = 0;
-  // VSX_SCORE=arith only: per-sequence "contains a non-ACGT symbol", computed on first use (vsx_purity_kernel) under the lock
+  // pair-profile classes only: per-sequence "contains a non-ACGT symbol", computed on first use (vsx_purity_kernel) under the lock
   mutable std::mutex impure_mu;
   mutable std::vector<uint8_t> impure;
   mutable bool have_impure = false;
@@ -349,7 +347,7 @@ struct vsx_seqset {
 
 namespace {
 
-struct Launch { int rows; int generic; int track; int tilt; int nq /* tasks per wave: 1, or 2 / 4 = a sparse-task class */; uint32_t first, count; uint32_t pair_first, pair_count;
+struct Launch { int rows; int track; int tilt; int nq /* tasks per wave: 1, or 2 / 4 = a sparse-task class */; uint32_t first, count; uint32_t pair_first, pair_count;
                 bool multi = false /* r06: some task of the launch spans several strips (Q > 16 rows): the general kernel; otherwise the ONE variants */; };
 
 struct Chunk {
@@ -629,10 +627,10 @@ int vsx_internal_scratch_reserve(vsx_ctx * ctx, const uint64_t want[4])
 static int pick_rows(int Q);
 // r06: what the checkpoint block of ONE plan of `ntasks` whole-wave tasks (a query of qlen rows against up to eight targets of tlen columns)
 // will ask for -- a caller that knows the largest plan it is going to submit (vsx_cluster_fast: a round of queries, eight candidates each)
-// reserves the block once instead of letting it grow over its first rounds; 0 when the context keeps direction bits instead of checkpoints
+// reserves the block once instead of letting it grow over its first rounds
 uint64_t vsx_internal_ckpt_bytes_estimate(const vsx_ctx * ctx, uint64_t ntasks, uint32_t qlen, uint32_t tlen)
 {
-  if (!ctx->ckpt || qlen == 0 || tlen == 0) return 0;
+  if (qlen == 0 || tlen == 0) return 0;
   const int rows = pick_rows((int) qlen);
   const uint64_t total_lanes = ((uint64_t) qlen + (uint64_t) rows - 1) / (uint64_t) rows, nstrips = (total_lanes + 15) / 16;
   const uint64_t steps = (((uint64_t) tlen + 3) & ~3ull) + 16;
@@ -684,7 +682,6 @@ int vsx_create(vsx_ctx ** out, const vsx_scoring * s, int device)
   auto * c = new vsx_ctx;
   c->device = device;
   c->sc = *s;
-  if (const char * mode = std::getenv("VSX_TRACEBACK")) c->ckpt = std::strcmp(mode, "dirs") != 0;
   if (const char * mode = std::getenv("VSX_POOL")) c->pool.enabled = std::strcmp(mode, "0") != 0;
   if (const char * mode = std::getenv("VSX_TB_ARITH")) c->tb_packed = std::strcmp(mode, "packed") == 0;
 
@@ -819,7 +816,7 @@ int vsx_create(vsx_ctx ** out, const vsx_scoring * s, int device)
   // prove the shifted range (tilt_possible()).  VSX_TILT=0 switches the class off (A/B measurements, tests).
   // The tilted kernel adds the primed scores with a 32-bit add over both int16 halves: they must be non-negative
   // (mismatch + 2g >= 0, the dummy rows' -ge(query left) + 2g >= 0).
-  if (geqi == geti && geti > 0 && P.share_sub && c->ckpt && !c->tb_packed && !c->force_fallback &&
+  if (geqi == geti && geti > 0 && P.share_sub && !c->tb_packed && !c->force_fallback &&
       std::min(match, mism) + 2 * geti >= 0 && 2 * geti - geql >= 0 &&
       std::max(match, mism) + 2 * geti <= 255 && 2 * geti - geql <= 255 &&       // the LDS query profile of the class holds bytes
       // compressed checkpoints: H - F(next row) and H - E(next column) lie in [-g, max QR'] (plus the dummy rows' seed
@@ -1063,7 +1060,7 @@ static int tilt_possible(const vsx_ctx * ctx, int64_t Q, int64_t D)
   const int64_t reach = 4 * G + 2 * (Q + Dp + 64) * B;          // |value| of anything the kernel forms stays below this
   // (pen[4] = the query's right-end gap open: the MAX3 kernel's interior steps read "the last row continues to the left" off ext-left
   //  alone, which covers "left" only when that penalty is positive -- vsx_forward_kernel LASTFAST; the reference's default is 1)
-  if (reach < 15800 && !max3_off && !VSX_CKT && ctx->pen[4] > 0 &&
+  if (reach < 15800 && !max3_off && ctx->pen[4] > 0 &&
       ctx->device < 64 && g_max3_state[ctx->device].load(std::memory_order_relaxed) == 1) return 2;         // 0x3E00 = 15872 each way inside [0, 0x7BFF]
   return reach < 32000 ? 1 : 0;
 }
@@ -1110,40 +1107,30 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
         return fail(VSX_EINVAL, "vsx_plan_create: pair %" PRIu64 " references a sequence out of range", bad[(size_t) t]);
   }
   HIPCHK(hipSetDevice(ctx->device));
-  static const bool arith = std::getenv("VSX_SCORE") && std::strcmp(std::getenv("VSX_SCORE"), "arith") == 0;
-  if (arith) { const int rc = ensure_impure(queries); if (rc != VSX_OK) return rc; }
   // r05, pair-profile classes (vsx_forward_kernel PAIR): groups of four whole-wave tasks of ONE pure-ACGT query with pure-ACGT targets
   // run as a workgroup that shares a pair-indexed dword profile (5 instead of 6 instructions per lane-row).  Worth it only for queries
   // with many targets (--allpairs_global); needs the purity of both sets.  VSX_PAIRPROF=0 / 1 overrides the default below
   // (r06, ADVICE r05: the purity of the two sets is asked for only once the grouping below has found a query with four whole-wave tasks --
-  //  a search's windows never have one, and every new query set used to pay a purity pass with a device-wide synchronisation; only the
-  //  environment and build parts of the switches are process-wide, ctx->ckpt is this context's)
-  static const bool pair_env = (std::getenv("VSX_PAIRPROF") ? std::strcmp(std::getenv("VSX_PAIRPROF"), "0") != 0 : (VSX_PAIRPROF_DEFAULT != 0)) &&
-                               !arith && VSX_QPL != 0 && VSX_FEED2 != 0 && !VSX_CKT;
-  const bool pair_try = pair_env && ctx->ckpt && n_pairs >= 32;
+  //  a search's windows never have one, and every new query set used to pay a purity pass with a device-wide synchronisation)
+  static const bool pair_env = std::getenv("VSX_PAIRPROF") ? std::strcmp(std::getenv("VSX_PAIRPROF"), "0") != 0 : (VSX_PAIRPROF_DEFAULT != 0);
+  const bool pair_try = pair_env && n_pairs >= 32;
 
   std::unique_ptr<vsx_plan> pl(new vsx_plan);
   pl->ctx = ctx; pl->Q = queries; pl->T = targets; pl->n_pairs = n_pairs;
-  static const unsigned ck_blocks = (std::getenv("VSX_CK_BLOCKS") && std::atoi(std::getenv("VSX_CK_BLOCKS")) == 2) ? 2u : 3u;
   // r06: a block nobody uses, the LARGEST such -- plans that follow one another (the stages of a clustering round, of a search window:
   // each is destroyed, i.e. its traceback has finished, before the next is made) then keep ONE block warm instead of growing three in
   // turn: 2 M x 300 bp --cluster_fast spent 1.1 s of its 6-7 s in eight multi-GB hipMallocs (profiles/r06/r06e_cluster_blocks.txt).
   // A pipeline of slices (vsx_align_pairs) finds the earlier plans' blocks taken and so still alternates; when all are taken, the one
-  // acquired longest ago (its traceback finishes first).  VSX_CK_ROTATE=1: the blind rotation of r04 / r05 (A/B).
+  // acquired longest ago (its traceback finishes first).
   {
-    static const bool rotate_env = std::getenv("VSX_CK_ROTATE") && std::strcmp(std::getenv("VSX_CK_ROTATE"), "1") == 0;
     std::lock_guard<std::mutex> lk(ctx->slot_mu);
     const unsigned seq = ctx->plan_seq.fetch_add(1);
     int pick = -1;
-    if (rotate_env) pick = (int) (seq % ck_blocks);
-    else
-      {
-        for (int k = 0; k < (int) ck_blocks; ++k)
-          if (ctx->slot_refs[k] == 0 && (pick < 0 || ctx->shared_dir[k].bytes() > ctx->shared_dir[pick].bytes())) pick = k;
-        if (pick < 0)
-          for (int k = 0; k < (int) ck_blocks; ++k)
-            if (pick < 0 || (int) (seq - ctx->slot_stamp[k]) > (int) (seq - ctx->slot_stamp[pick])) pick = k;
-      }
+    for (int k = 0; k < 3; ++k)
+      if (ctx->slot_refs[k] == 0 && (pick < 0 || ctx->shared_dir[k].bytes() > ctx->shared_dir[pick].bytes())) pick = k;
+    if (pick < 0)
+      for (int k = 0; k < 3; ++k)
+        if (pick < 0 || (int) (seq - ctx->slot_stamp[k]) > (int) (seq - ctx->slot_stamp[pick])) pick = k;
     ++ctx->slot_refs[pick];
     ctx->slot_stamp[pick] = seq;
     pl->dir_slot = pick;
@@ -1214,11 +1201,10 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
   // ---- group by query -> tasks of <= 8 targets, similar lengths together (host threads over query groups) ----
   auto by_query = [&](uint32_t a, uint32_t b) { return qidx[a] < qidx[b]; };
   if (!std::is_sorted(gpu_pairs.begin(), gpu_pairs.end(), by_query)) std::stable_sort(gpu_pairs.begin(), gpu_pairs.end(), by_query);
-  struct ProtoTask { uint32_t q; int rows; int generic; int track; int tilt; int nq; uint32_t n; uint32_t pair[8]; };
+  struct ProtoTask { uint32_t q; int rows; int track; int tilt; int nq; uint32_t n; uint32_t pair[8]; };
   // r05, sparse tasks: a task of <= 2 (<= 4) targets of the TILT family shares its wave with three (one) other tasks of its class
   // (vsx_forward_kernel NQ) instead of leaving three (two) of the four lane groups idle.  VSX_SPARSE=0: every task is a wave (A/B, tests)
-  static const bool sparse_env = !(std::getenv("VSX_SPARSE") && std::strcmp(std::getenv("VSX_SPARSE"), "0") == 0) && VSX_QPL != 0 && !VSX_CKT;
-  const bool sparse_on = sparse_env && ctx->ckpt;
+  static const bool sparse_on = !(std::getenv("VSX_SPARSE") && std::strcmp(std::getenv("VSX_SPARSE"), "0") == 0);
   std::vector<size_t> group_begin;                       // start of every query's run in gpu_pairs, plus the end
   for (size_t b = 0; b < gpu_pairs.size();)
     {
@@ -1229,8 +1215,6 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
       b = e;
     }
   group_begin.push_back(gpu_pairs.size());
-  // substitution scores: LDS query profile by default (handles every symbol); VSX_SCORE=arith selects the XOR/min/mad
-  // variant for queries made of A/C/G/T(U) only (kept for A/B measurements)
   const size_t ngroups = group_begin.size() - 1;
   const int nth = (int) std::max<size_t>(1, std::min<size_t>((size_t) vsx_internal_usable_cpus(), gpu_pairs.size() / 16384));
   std::vector<std::vector<ProtoTask>> part((size_t) nth);
@@ -1248,12 +1232,11 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
         std::stable_sort(gpu_pairs.begin() + (long) b, gpu_pairs.begin() + (long) e,
                          [&](uint32_t x, uint32_t y) { return targets->len[tidx[x]] > targets->len[tidx[y]]; });
         const int rows = pick_rows((int) queries->len[q]);
-        const int generic = (!arith || queries->impure[q]) ? 1 : 0;
         const size_t first_of_query = outp.size();
         for (size_t x = b; x < e; x += VSX_TASK_SLOTS)
           {
             ProtoTask pt {};
-            pt.q = q; pt.rows = rows; pt.generic = generic;
+            pt.q = q; pt.rows = rows;
             pt.n = (uint32_t) std::min<size_t>(VSX_TASK_SLOTS, e - x);
             uint32_t dmax = 0;
             for (uint32_t sidx = 0; sidx < pt.n; ++sidx)
@@ -1262,7 +1245,7 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
                 dmax = std::max(dmax, targets->len[tidx[pt.pair[sidx]]]);
               }
             pt.track = (!ctx->tb_packed && no_overflow_possible(ctx, queries->len[q], dmax)) ? 0 : 1;
-            pt.tilt = (pt.track == 0 && generic && ctx->ckpt) ? tilt_possible(ctx, queries->len[q], dmax) : 0;
+            pt.tilt = (pt.track == 0) ? tilt_possible(ctx, queries->len[q], dmax) : 0;
             pt.nq = 1;
             if (sparse_on && pt.tilt && rows >= 4 && pt.n <= 4 && (int64_t) queries->len[q] <= 16ll * rows)      // (one strip: the hand-over rows are per wave)
               pt.nq = pt.n <= 2 ? 4 : 2;
@@ -1330,20 +1313,20 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
   // 16 R >= Q is valid for a query, so the tasks of a sparse class join the next denser class of the same kind.
   {
     static const bool no_promote = std::getenv("VSX_NO_PROMOTE") != nullptr;      // A/B, tests
-    struct Cls { int rows, generic, track, tilt, nq; size_t count; };
+    struct Cls { int rows, track, tilt, nq; size_t count; };
     std::vector<Cls> cls;
     for (const ProtoTask & pt : protos)
       {
         bool found = false;
-        for (Cls & c : cls) if (c.rows == pt.rows && c.generic == pt.generic && c.track == pt.track && c.tilt == pt.tilt && c.nq == pt.nq) { ++c.count; found = true; break; }
-        if (!found) cls.push_back(Cls {pt.rows, pt.generic, pt.track, pt.tilt, pt.nq, 1});
+        for (Cls & c : cls) if (c.rows == pt.rows && c.track == pt.track && c.tilt == pt.tilt && c.nq == pt.nq) { ++c.count; found = true; break; }
+        if (!found) cls.push_back(Cls {pt.rows, pt.track, pt.tilt, pt.nq, 1});
       }
     std::vector<std::pair<size_t, int>> move;                                 // class index -> new rows
     for (size_t a = 0; a < cls.size() && !no_promote; ++a)
       {
         int best = 0;
         for (const Cls & c : cls)
-          if (c.generic == cls[a].generic && c.track == cls[a].track && c.tilt == cls[a].tilt && c.nq == cls[a].nq && c.rows > cls[a].rows &&
+          if (c.track == cls[a].track && c.tilt == cls[a].tilt && c.nq == cls[a].nq && c.rows > cls[a].rows &&
               c.count >= 32 * cls[a].count && (best == 0 || c.rows < best))
             best = c.rows;
         if (best && cls[a].count < 4096) move.emplace_back(a, best);
@@ -1353,14 +1336,14 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
         for (const auto & other : move)
           {
             const Cls & a = cls[mv.first], & o = cls[other.first];
-            if (o.rows == mv.second && o.generic == a.generic && o.track == a.track && o.tilt == a.tilt && o.nq == a.nq) { mv.second = other.second; break; }
+            if (o.rows == mv.second && o.track == a.track && o.tilt == a.tilt && o.nq == a.nq) { mv.second = other.second; break; }
           }
     if (!move.empty())
       for (ProtoTask & pt : protos)
         for (const auto & mv : move)
           {
             const Cls & c = cls[mv.first];
-            if (pt.rows == c.rows && pt.generic == c.generic && pt.track == c.track && pt.tilt == c.tilt && pt.nq == c.nq)
+            if (pt.rows == c.rows && pt.track == c.track && pt.tilt == c.tilt && pt.nq == c.nq)
               {
                 // (only queries that still span two pipeline positions: a query shorter than one position of the new class would make
                 //  position 0 the last position as well, a shape no row count chosen by pick_rows() ever produces)
@@ -1376,14 +1359,14 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
   if (sparse_on)
     {
       static const size_t sparse_min = std::getenv("VSX_SPARSE_MIN") ? (size_t) std::atoll(std::getenv("VSX_SPARSE_MIN")) : 4096;
-      struct Key { int rows, generic, track, tilt, nq; size_t count; };
+      struct Key { int rows, track, tilt, nq; size_t count; };
       std::vector<Key> ks;
       for (const ProtoTask & pt : protos)
         {
           if (pt.nq != 2 && pt.nq != 4) continue;
           bool found = false;
-          for (Key & c : ks) if (c.rows == pt.rows && c.generic == pt.generic && c.track == pt.track && c.tilt == pt.tilt && c.nq == pt.nq) { ++c.count; found = true; break; }
-          if (!found) ks.push_back(Key {pt.rows, pt.generic, pt.track, pt.tilt, pt.nq, 1});
+          for (Key & c : ks) if (c.rows == pt.rows && c.track == pt.track && c.tilt == pt.tilt && c.nq == pt.nq) { ++c.count; found = true; break; }
+          if (!found) ks.push_back(Key {pt.rows, pt.track, pt.tilt, pt.nq, 1});
         }
       bool any = false;
       for (const Key & c : ks) any = any || c.count < sparse_min;
@@ -1391,12 +1374,11 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
         for (ProtoTask & pt : protos)
           if (pt.nq == 2 || pt.nq == 4)
             for (const Key & c : ks)
-              if (c.count < sparse_min && pt.nq == c.nq && pt.rows == c.rows && pt.generic == c.generic && pt.track == c.track && pt.tilt == c.tilt) { pt.nq = 1; break; }
+              if (c.count < sparse_min && pt.nq == c.nq && pt.rows == c.rows && pt.track == c.track && pt.tilt == c.tilt) { pt.nq = 1; break; }
     }
   // kernel classes together (one launch per class and chunk)
   auto by_class = [](const ProtoTask & a, const ProtoTask & b) {
     if (a.rows != b.rows) return a.rows < b.rows;
-    if (a.generic != b.generic) return a.generic < b.generic;
     if (a.track != b.track) return a.track < b.track;
     if (a.tilt != b.tilt) return a.tilt < b.tilt;
     return a.nq < b.nq;
@@ -1452,12 +1434,9 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
           }
         t.steps = dmax + 16;                                // pipeline drain (15) rounded to an even step count: the DP
                                                             // kernel stores row checkpoints two steps at a time
-        if (pt.tilt && VSX_CKT) t.steps = (t.steps + 7u) & ~7u;   // ... and in blocks of 8 steps in the transposed layout
         const uint64_t total_lanes = (t.qlen + pt.rows - 1) / pt.rows;
         const uint64_t nstrips = (total_lanes + 15) / 16;
-        const uint64_t nd = (uint64_t) (pt.rows + 3) / 4;
-        t_dwords[x] = ctx->ckpt ? vsx_ckpt_dwords(nstrips, t.steps, (uint64_t) pt.rows, pt.tilt)
-                                : ((nstrips * t.steps + 3) & ~3ull) * 64 * nd;     // [4-step block][lane][4][nd]
+        t_dwords[x] = vsx_ckpt_dwords(nstrips, t.steps, (uint64_t) pt.rows, pt.tilt);
         t.strip_off = nstrips > 1 ? 2ull * 4 * t.steps : 0;                          // size for now, offset after the scan
         t_slab[x] = slab;
         pl->tasks[x] = t;
@@ -1477,7 +1456,7 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
   uint32_t wave_left = 0, wave_steps = 0, wave_group = 0, pair_left = 0;
   uint64_t wave_off = 0;
   auto same_class = [&](size_t a, size_t b) {
-    return protos[a].rows == protos[b].rows && protos[a].generic == protos[b].generic && protos[a].track == protos[b].track &&
+    return protos[a].rows == protos[b].rows && protos[a].track == protos[b].track &&
            protos[a].tilt == protos[b].tilt && protos[a].nq == protos[b].nq;
   };
   for (size_t x = 0; x < NT; ++x)
@@ -1527,9 +1506,9 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
       cur.dir_dwords += dwords;
       cur.strip_elems += strip;
       pl->dir_bytes_total += dwords * 4;
-      if (cur.launches.empty() || cur.launches.back().rows != pt.rows || cur.launches.back().generic != pt.generic ||
+      if (cur.launches.empty() || cur.launches.back().rows != pt.rows ||
           cur.launches.back().track != pt.track || cur.launches.back().tilt != pt.tilt || cur.launches.back().nq != pt.nq)
-        cur.launches.push_back(Launch {pt.rows, pt.generic, pt.track, pt.tilt, pt.nq, (uint32_t) x, 0, cur.pair_first + cur.pair_count, 0});
+        cur.launches.push_back(Launch {pt.rows, pt.track, pt.tilt, pt.nq, (uint32_t) x, 0, cur.pair_first + cur.pair_count, 0});
       cur.launches.back().count++;
       if (strip != 0) cur.launches.back().multi = true;           // (a task owns hand-over rows only when it has a second strip)
       cur.launches.back().pair_count += pt.n;
@@ -1646,7 +1625,6 @@ int vsx_plan_set_filter(vsx_plan * pl, const vsx_filter * f)
   if (!pl) return fail(VSX_EINVAL, "vsx_plan_set_filter: null plan");
   pl->filter = VsxFilterDev {};            // (also drops the lists of a ranked plan: plan_set_ranked() follows the filter)
   if (!f) return VSX_OK;
-  if (!pl->ctx->ckpt) return fail(VSX_EINVAL, "vsx_plan_set_filter: needs the checkpoint traceback (VSX_TRACEBACK=dirs is set)");
   if (f->iddef < 0 || f->iddef > 4) return fail(VSX_EINVAL, "vsx_plan_set_filter: iddef must be 0..4");
   VsxFilterDev & d = pl->filter;
   d.enabled = 1; d.iddef = f->iddef; d.leftjust = f->leftjust; d.rightjust = f->rightjust;
@@ -1657,15 +1635,9 @@ int vsx_plan_set_filter(vsx_plan * pl, const vsx_filter * f)
 }
 
 // r06: make `pl` a RANKED plan -- its traceback lists the kept and the refused pairs (vsx_device.hip rank_note) for fetch_ranked_core.
-// VSX_RANK_PRIM=1 keeps the r02-r05 path (flag kernel + rocPRIM scan / segmented sort over all pairs) for A/B.
-static bool rank_lists_on()
-{
-  static const bool prim = std::getenv("VSX_RANK_PRIM") && std::strcmp(std::getenv("VSX_RANK_PRIM"), "1") == 0;
-  return !prim;
-}
 static int plan_set_ranked(vsx_plan * pl)
 {
-  if (!rank_lists_on() || !pl->filter.enabled) return VSX_OK;
+  if (!pl->filter.enabled) return VSX_OK;
   vsx_ctx * ctx = pl->ctx;
   const size_t n = (size_t) pl->n_pairs;
   HIPCHK(hipSetDevice(ctx->device));
@@ -1698,54 +1670,41 @@ int vsx_plan_run(vsx_plan * pl)
       uint32_t * dir = pl->d_dir[0].p;
       if (k >= 1) HIPCHK(hipStreamWaitEvent(st, pl->chunks[k - 1].e2, 0));      // buffer reuse: the previous traceback is done
       else if (ctx->ev_tb_used[slot]) HIPCHK(hipStreamWaitEvent(st, ctx->ev_tb[slot], 0));
-      // VSX_ALIGN_SERIAL=1 (A/B, r05): no overlap between a plan's DP and the previous plan's traceback.  The trace of an allpairs run
-      // (profiles/r05/r05q_*) shows the R = 26 DP launches at 28.7 ms beside a traceback where the kernel alone takes 13.3 ms
-      static const bool serial_env = std::getenv("VSX_ALIGN_SERIAL") && std::strcmp(std::getenv("VSX_ALIGN_SERIAL"), "1") == 0;
-      if (k == 0 && serial_env && ctx->last_tb_slot >= 0 && ctx->last_tb_slot != slot) HIPCHK(hipStreamWaitEvent(st, ctx->ev_tb[ctx->last_tb_slot], 0));
       HIPCHK(hipEventRecord(c.e0, st));
       for (const Launch & L : c.launches)
         {
           VsxDevParams Pf = L.tilt ? ctx->Pt : ctx->P;
           Pf.max3 = (L.tilt == 2) ? 1 : 0;
           static const bool one_off = std::getenv("VSX_ONESTRIP") && std::strcmp(std::getenv("VSX_ONESTRIP"), "0") == 0;      // A/B, tests: the general kernels
-          HIPCHK(vsx_launch_forward(L.rows, L.generic, L.track, ctx->ckpt ? 1 : 0, L.nq, (L.multi || (one_off && L.nq != 8)) ? 0 : 1, Pf, pl->d_tasks.p + L.first, L.count,
+          HIPCHK(vsx_launch_forward(L.rows, L.track, L.nq, (L.multi || (one_off && L.nq != 8)) ? 0 : 1, Pf, pl->d_tasks.p + L.first, L.count,
                                     pl->Q->codes(), pl->T->codes(), dir, pl->d_strip.p,
                                     pl->d_slot.p + (size_t) L.first * VSX_TASK_SLOTS, st));
         }
       HIPCHK(hipEventRecord(c.e1, st));
       HIPCHK(hipStreamWaitEvent(st2, c.e1, 0));
       HIPCHK(hipEventRecord(c.e1b, st2));
-      if (ctx->ckpt)
+      for (size_t li = 0; li < c.launches.size();)      // the recompute traceback is specialised on R like the DP kernel
         {
-          for (size_t li = 0; li < c.launches.size();)      // the recompute traceback is specialised on R like the DP kernel
-            {
-              const Launch & L = c.launches[li];
-              // (the sparse-task variants of one class -- nq = 1, 2, 4, adjacent in the class order -- share ONE traceback launch: the
-              //  traceback finds a pair's lane group through its task and does not know about nq; their pairs are contiguous)
-              uint32_t pair_count = L.pair_count;
-              size_t lj = li + 1;
-              while (lj < c.launches.size() && c.launches[lj].rows == L.rows && c.launches[lj].generic == L.generic &&
-                     c.launches[lj].track == L.track && c.launches[lj].tilt == L.tilt) { pair_count += c.launches[lj].pair_count; ++lj; }
-              VsxDevParams Pb = L.tilt ? ctx->Pt : ctx->P;
-              Pb.max3 = (L.tilt == 2) ? 1 : 0;         // the checkpoints of the MAX3 class carry its bias
-              HIPCHK(vsx_launch_traceback_ck(L.rows, (L.track == 0 && L.generic != 0) ? 1 : 0, Pb, pl->filter, pl->d_tasks.p, pl->d_pair_slot.p + L.pair_first,
-                                             pl->d_pair_ids.p + L.pair_first, pair_count, pl->Q->codes(), pl->T->codes(),
-                                             dir, pl->d_slot.p, pl->d_slab.p, pl->d_slab_off.p + L.pair_first,
-                                             pl->d_runs.p, pl->runs_capacity, pl->d_cursor.p, pl->d_out.p, st2));
-              li = lj;
-            }
+          const Launch & L = c.launches[li];
+          // (the sparse-task variants of one class -- nq = 1, 2, 4, adjacent in the class order -- share ONE traceback launch: the
+          //  traceback finds a pair's lane group through its task and does not know about nq; their pairs are contiguous)
+          uint32_t pair_count = L.pair_count;
+          size_t lj = li + 1;
+          while (lj < c.launches.size() && c.launches[lj].rows == L.rows &&
+                 c.launches[lj].track == L.track && c.launches[lj].tilt == L.tilt) { pair_count += c.launches[lj].pair_count; ++lj; }
+          VsxDevParams Pb = L.tilt ? ctx->Pt : ctx->P;
+          Pb.max3 = (L.tilt == 2) ? 1 : 0;         // the checkpoints of the MAX3 class carry its bias
+          HIPCHK(vsx_launch_traceback_ck(L.rows, L.track == 0 ? 1 : 0, Pb, pl->filter, pl->d_tasks.p, pl->d_pair_slot.p + L.pair_first,
+                                         pl->d_pair_ids.p + L.pair_first, pair_count, pl->Q->codes(), pl->T->codes(),
+                                         dir, pl->d_slot.p, pl->d_slab.p, pl->d_slab_off.p + L.pair_first,
+                                         pl->d_runs.p, pl->runs_capacity, pl->d_cursor.p, pl->d_out.p, st2));
+          li = lj;
         }
-      else
-        HIPCHK(vsx_launch_traceback(ctx->P, pl->d_tasks.p, pl->d_pair_slot.p + c.pair_first, pl->d_pair_ids.p + c.pair_first,
-                                    c.pair_count, pl->Q->codes(), pl->T->codes(), dir, pl->d_slot.p,
-                                    pl->d_slab.p, pl->d_slab_off.p + c.pair_first, pl->d_runs.p, pl->runs_capacity,
-                                    pl->d_cursor.p, pl->d_out.p, st2));
       HIPCHK(hipEventRecord(c.e2, st2));
     }
   if (pl->chunks.empty()) HIPCHK(hipStreamWaitEvent(st2, pl->ev_begin, 0));          // (the cursor memset precedes the text kernel)
   HIPCHK(hipEventRecord(ctx->ev_tb[slot], st2));
   ctx->ev_tb_used[slot] = true;
-  ctx->last_tb_slot = slot;
   // run lists -> CIGAR text, records -> output arrays (pushop / finishop are part of the reference's timed path); st2 is in order
   HIPCHK(vsx_launch_cigar_text(pl->d_out.p, pl->d_pair_ids.p, (uint32_t) pl->pair_ids.size(), pl->d_runs.p, pl->runs_capacity,
                                pl->d_text.p, pl->text_capacity, pl->d_cursor.p + 1, pl->soa, st2));
@@ -1944,7 +1903,7 @@ static int fetch_core(vsx_plan * pl, const FetchDest & D)
   return VSX_OK;
 }
 
-// Ranked fetch (vsx_rank.hip): only the pairs the plan's filter kept, in report order, appended to a sink.
+// Ranked fetch: only the pairs the plan's filter kept, in report order, appended to a sink.
 struct RankedSink {
   std::vector<uint32_t> pair, undecided;
   std::vector<int16_t> score;
@@ -1959,8 +1918,8 @@ struct RankedSink {
 };
 
 // r06: the ranked fetch from the lists the traceback's epilogue wrote.  Kept pairs arrive in arbitrary order: their fields are gathered
-// as they lie, cross PCIe, and the HOST puts the few of them in report order -- per query (queries ascending = pair index ascending
-// across groups), identity descending, pair index ascending among equals: what the stable segmented sort produced.
+// as they lie, cross PCIe, and the HOST puts the few of them in report order -- per run of equal query keys (runs in pair order; the
+// pairs of a query are documented to be contiguous, so a run is a query), identity descending, pair index ascending among equals.
 static int fetch_ranked_lists(vsx_plan * pl, uint64_t first, const uint32_t * qkey, RankedSink & S, unsigned long long text_used)
 {
   vsx_ctx * ctx = pl->ctx;
@@ -2019,9 +1978,12 @@ static int fetch_ranked_lists(vsx_plan * pl, uint64_t first, const uint32_t * qk
       if (h_pair[j] >= n) return fail(VSX_EHIP, "vsx_align_pairs_ranked: a kept pair is out of range");
       if (h_vd[j] == 1u || (S.keep_weak && h_vd[j] == 2u)) order.push_back(j);
     }
+  // segment of each plan-local pair: a new one wherever the query key changes (a strict weak order for every key list)
+  std::vector<uint32_t> seg((size_t) n);
+  for (uint64_t k = 1; k < n; ++k) seg[k] = seg[k - 1] + (qkey[k] != qkey[k - 1] ? 1u : 0u);
   std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
     const uint32_t pa = h_pair[a], pb = h_pair[b];
-    if (qkey[pa] != qkey[pb]) return pa < pb;                 // (the pairs of a query are contiguous: another query = another segment)
+    if (seg[pa] != seg[pb]) return seg[pa] < seg[pb];
     if (h_id[a] != h_id[b]) return h_id[a] > h_id[b];
     return pa < pb;
   });
@@ -2052,124 +2014,15 @@ static int fetch_ranked_lists(vsx_plan * pl, uint64_t first, const uint32_t * qk
 // `first` = index of the plan's pair 0 in the caller's list; `qkey` = the caller's query index per pair (plan-local view)
 static int fetch_ranked_core(vsx_plan * pl, uint64_t first, const uint32_t * qkey, RankedSink & S)
 {
-  vsx_ctx * ctx = pl->ctx;
   unsigned long long used = 0, text_used = 0;
   int rc = settle(pl, used, text_used);
   if (rc != VSX_OK) return rc;
   const uint64_t n = pl->n_pairs;
   for (uint32_t k : pl->host_pairs) S.undecided.push_back((uint32_t) (first + k));
   if (n == 0) return VSX_OK;
-  hipStream_t st = ctx->stream_dn;             // the plan's kernels are done; the next slice may own `stream`
-  if (pl->filter.rank_counts) return fetch_ranked_lists(pl, first, qkey, S, text_used);
-
-  // query groups of the pair list (pairs of one query are contiguous)
-  std::vector<uint32_t> qstart;
-  for (uint64_t k = 0; k < n; ++k) if (k == 0 || qkey[k] != qkey[k - 1]) qstart.push_back((uint32_t) k);
-  const uint32_t G = (uint32_t) qstart.size();
-  qstart.push_back((uint32_t) n);
-
-  PoolBuf<uint32_t> d_flag, d_pos, d_qstart, d_seg, d_val_in, d_val_out;
-  PoolBuf<double> d_id, d_key_in, d_key_out;
-  PoolBuf<uint8_t> d_temp, d_rank;
-  HIPCHK(d_flag.alloc(&ctx->pool, n + 1));
-  HIPCHK(d_pos.alloc(&ctx->pool, n + 1));
-  HIPCHK(d_id.alloc(&ctx->pool, n));
-  HIPCHK(d_qstart.alloc(&ctx->pool, G + 1));
-  HIPCHK(d_seg.alloc(&ctx->pool, G + 1));
-  PoolBuf<uint32_t> d_refused;                 // [0] = count, then the GPU pairs whose 16-bit DP overflowed at run time
-  const uint32_t ngpu = (uint32_t) pl->pair_ids.size();
-  HIPCHK(d_refused.alloc(&ctx->pool, (size_t) ngpu + 1));
-  HIPCHK(hipMemcpyAsync(d_qstart.p, qstart.data(), (G + 1) * 4, hipMemcpyHostToDevice, st));
-  size_t tb = 0;
-  HIPCHK(vsx_rank_flag_scan(pl->filter, S.keep_weak, pl->d_out.p, pl->d_pair_ids.p, pl->d_pair_slot.p, pl->d_tasks.p, (uint32_t) pl->pair_ids.size(),
-                            (uint32_t) n, pl->d_runs.p, pl->runs_capacity, d_flag.p, d_pos.p, d_id.p, d_refused.p, nullptr, &tb, st));
-  HIPCHK(d_temp.alloc(&ctx->pool, tb + 16));
-  HIPCHK(vsx_rank_flag_scan(pl->filter, S.keep_weak, pl->d_out.p, pl->d_pair_ids.p, pl->d_pair_slot.p, pl->d_tasks.p, (uint32_t) pl->pair_ids.size(),
-                            (uint32_t) n, pl->d_runs.p, pl->runs_capacity, d_flag.p, d_pos.p, d_id.p, d_refused.p, d_temp.p, &tb, st));
-  uint32_t kept = 0, n_refused = 0;
-  HIPCHK(hipMemcpyAsync(&kept, d_pos.p + n, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&n_refused, d_refused.p, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (n_refused)
-    {
-      // the contract of vsx_ranked (include/vsx.h): a pair the 16-bit aligner refused -- before the launch (host_pairs above) or
-      // by the overflow rule inside it -- is `undecided`, never silently dropped; the caller's fallback aligns and filters it
-      if (n_refused > ngpu) return fail(VSX_EHIP, "vsx_align_pairs_ranked: refused-pair list is corrupt");
-      std::vector<uint32_t> rf(n_refused);
-      HIPCHK(hipMemcpy(rf.data(), d_refused.p + 1, (size_t) n_refused * 4, hipMemcpyDeviceToHost));
-      std::sort(rf.begin(), rf.end());         // the device appends in arbitrary order
-      for (uint32_t k : rf) S.undecided.push_back((uint32_t) (first + k));
-    }
-
-  const uint64_t k1 = std::max<uint32_t>(kept, 1);
-  // compact output arrays in one block: pair u32, id f64, text_off u64, 5 x 16 bit, verdict u8 (16-byte aligned sections)
-  const uint64_t width[9] = {4, 8, 8, 2, 2, 2, 2, 2, 1};
-  uint64_t off[9], at = 0;
-  for (int x = 0; x < 9; ++x) { off[x] = at; at += (k1 * width[x] + 15) & ~15ull; }
-  const uint64_t rank_bytes = at;
-  HIPCHK(d_rank.alloc(&ctx->pool, rank_bytes));
-  VsxRankedOut R;
-  R.pair = reinterpret_cast<uint32_t *>(d_rank.p + off[0]);
-  R.id = reinterpret_cast<double *>(d_rank.p + off[1]);
-  R.text_off = reinterpret_cast<uint64_t *>(d_rank.p + off[2]);
-  R.score = reinterpret_cast<int16_t *>(d_rank.p + off[3]);
-  R.aligned = reinterpret_cast<uint16_t *>(d_rank.p + off[4]);
-  R.matches = reinterpret_cast<uint16_t *>(d_rank.p + off[5]);
-  R.mismatches = reinterpret_cast<uint16_t *>(d_rank.p + off[6]);
-  R.gaps = reinterpret_cast<uint16_t *>(d_rank.p + off[7]);
-  R.verdict = d_rank.p + off[8];
-  if (kept)
-    {
-      HIPCHK(d_key_in.alloc(&ctx->pool, kept)); HIPCHK(d_key_out.alloc(&ctx->pool, kept));
-      HIPCHK(d_val_in.alloc(&ctx->pool, kept)); HIPCHK(d_val_out.alloc(&ctx->pool, kept));
-      size_t sb = 0;
-      HIPCHK(vsx_rank_sort_gather(d_flag.p, d_pos.p, d_id.p, (uint32_t) n, kept, d_qstart.p, G, d_key_in.p, d_key_out.p, d_val_in.p, d_val_out.p,
-                                  d_seg.p, pl->d_out.p, pl->soa.text_off, R, nullptr, &sb, st));
-      PoolBuf<uint8_t> d_temp2;
-      HIPCHK(d_temp2.alloc(&ctx->pool, sb + 16));
-      HIPCHK(vsx_rank_sort_gather(d_flag.p, d_pos.p, d_id.p, (uint32_t) n, kept, d_qstart.p, G, d_key_in.p, d_key_out.p, d_val_in.p, d_val_out.p,
-                                  d_seg.p, pl->d_out.p, pl->soa.text_off, R, d_temp2.p, &sb, st));
-      HIPCHK(hipStreamSynchronize(st));        // d_temp2 goes back to the pool at the end of this scope
-    }
-
-  // text: the whole device blob crosses (rejected pairs hold 4 bytes each), then only the kept strings are copied out
-  std::lock_guard<std::mutex> lk(ctx->stage_mu);
-  if ((rc = stage_reserve(ctx, rank_bytes + ((text_used + 15) & ~15ull))) != VSX_OK) return rc;
-  if (kept) HIPCHK(hipMemcpyAsync(ctx->stage, d_rank.p, rank_bytes, hipMemcpyDeviceToHost, st));
-  if (kept && text_used) HIPCHK(hipMemcpyAsync(ctx->stage + rank_bytes, pl->d_text.p, text_used, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (!kept) return VSX_OK;
-  const uint8_t * sg = ctx->stage;
-  const char * text = reinterpret_cast<const char *>(sg + rank_bytes);
-  const uint32_t * h_pair = reinterpret_cast<const uint32_t *>(sg + off[0]);
-  const double * h_id = reinterpret_cast<const double *>(sg + off[1]);
-  const uint64_t * h_toff = reinterpret_cast<const uint64_t *>(sg + off[2]);
-  const size_t base = S.pair.size();
-  S.pair.resize(base + kept); S.id.resize(base + kept); S.cigar_off.resize(base + kept);
-  S.score.resize(base + kept); S.aligned.resize(base + kept); S.matches.resize(base + kept);
-  S.mismatches.resize(base + kept); S.gaps.resize(base + kept); S.verdict.resize(base + kept);
-  std::memcpy(S.id.data() + base, h_id, kept * 8);
-  std::memcpy(S.score.data() + base, sg + off[3], kept * 2);
-  std::memcpy(S.aligned.data() + base, sg + off[4], kept * 2);
-  std::memcpy(S.matches.data() + base, sg + off[5], kept * 2);
-  std::memcpy(S.mismatches.data() + base, sg + off[6], kept * 2);
-  std::memcpy(S.gaps.data() + base, sg + off[7], kept * 2);
-  std::memcpy(S.verdict.data() + base, sg + off[8], kept);
-  // string lengths first (one realloc), then the copies
-  uint64_t need = 0;
-  std::vector<uint32_t> slen(kept);
-  for (uint32_t j = 0; j < kept; ++j) { slen[j] = (uint32_t) std::strlen(text + h_toff[j]) + 1; need += slen[j]; }
-  char * nb = (char *) std::realloc(S.blob, std::max<uint64_t>(S.blob_used + need, 1));
-  if (!nb) return fail(VSX_ENOMEM, "vsx_align_pairs_ranked: host allocation failed");
-  S.blob = nb;
-  for (uint32_t j = 0; j < kept; ++j)
-    {
-      S.pair[base + j] = (uint32_t) (first + h_pair[j]);
-      S.cigar_off[base + j] = S.blob_used;
-      std::memcpy(S.blob + S.blob_used, text + h_toff[j], slen[j]);
-      S.blob_used += slen[j];
-    }
-  return VSX_OK;
+  // (every ranked plan has its lists: vsx_align_pairs_ranked requires the filter, plan_set_ranked() follows it)
+  if (!pl->filter.rank_counts) return fail(VSX_EINVAL, "vsx_align_pairs_ranked: the plan has no ranking lists");
+  return fetch_ranked_lists(pl, first, qkey, S, text_used);
 }
 
 // result arrays for n pairs (the blob starts empty and grows with every fetched plan)
@@ -2290,7 +2143,7 @@ static int align_pairs_single(vsx_ctx * ctx, const vsx_seqset * queries, const v
   vsx_plan * pl = nullptr;
   int rc = vsx_plan_create(ctx, &pl, queries, targets, n_pairs, qidx, tidx, 0);
   if (rc != VSX_OK) return rc;
-  if (filter && ctx->ckpt) { rc = vsx_plan_set_filter(pl, filter); if (rc != VSX_OK) { vsx_plan_destroy(pl); return rc; } }
+  if (filter) { rc = vsx_plan_set_filter(pl, filter); if (rc != VSX_OK) { vsx_plan_destroy(pl); return rc; } }
   if (sink) { rc = plan_set_ranked(pl); if (rc != VSX_OK) { vsx_plan_destroy(pl); return rc; } }
   const double t1 = now();
   rc = vsx_plan_run(pl);
@@ -2366,7 +2219,7 @@ static int align_pairs_impl(vsx_ctx * ctx, const vsx_seqset * queries, const vsx
   std::vector<std::string> plan_msg(S);
   if (!sink)
     {
-      const int arc = results_alloc(out, n_pairs, filter && ctx->ckpt);
+      const int arc = results_alloc(out, n_pairs, filter != nullptr);
       if (arc != VSX_OK) return arc;
     }
   std::mutex mu;
@@ -2395,7 +2248,7 @@ static int align_pairs_impl(vsx_ctx * ctx, const vsx_seqset * queries, const vsx
         }
         vsx_plan * pl = nullptr;
         int rc = vsx_plan_create(ctx, &pl, queries, targets, cut[i + 1] - cut[i], qidx + cut[i], tidx + cut[i], slice_budget);
-        if (rc == VSX_OK && filter && ctx->ckpt) rc = vsx_plan_set_filter(pl, filter);
+        if (rc == VSX_OK && filter) rc = vsx_plan_set_filter(pl, filter);
         if (rc == VSX_OK && sink) rc = plan_set_ranked(pl);
         if (rc != VSX_OK) { plan_msg[i] = vsx_last_error(); if (pl) vsx_plan_destroy(pl); pl = nullptr; }
         if (timing) std::fprintf(stderr, "  slice %zu (%llu pairs): planned at %.1f ms\n", i, (unsigned long long) (cut[i + 1] - cut[i]), (now() - t_begin) * 1e3);
@@ -2488,7 +2341,6 @@ int vsx_align_pairs_ranked(vsx_ctx * ctx, const vsx_seqset * queries, const vsx_
   if (!ctx || !out || !queries || !targets || (n_pairs && (!qidx || !tidx))) return fail(VSX_EINVAL, "vsx_align_pairs_ranked: null argument");
   std::memset(out, 0, sizeof *out);
   if (!filter) return fail(VSX_EINVAL, "vsx_align_pairs_ranked: the ranking needs the accept filter");
-  if (!ctx->ckpt) return fail(VSX_EINVAL, "vsx_align_pairs_ranked: needs the checkpoint traceback (VSX_TRACEBACK=dirs is set)");
   RankedSink sink;
   sink.keep_weak = keep_weak ? 1 : 0;
   const int rc = align_pairs_impl(ctx, queries, targets, n_pairs, qidx, tidx, filter, nullptr, &sink);

@@ -13,26 +13,9 @@
 #define VSX_CODE_SLACK 64          // readable bytes before and after a sequence set's 4-bit codes
 #define VSX_CK_SLACK_DW 4096        // readable dwords before the first and after the last task's checkpoints of a chunk (vsx_traceback_tilt_kernel
                                    // loads the row-checkpoint pairs p0 - 1 .. p0 + 8 around a tile unclamped: affine addresses, immediate offsets)
-// TILT class: checkpoints leave the DP kernel through an LDS transposition, so that in HBM every pipeline lane owns CONTIGUOUS
-// 48-byte segments (8 steps of row checkpoints; a third of a column checkpoint at R = 16) while every store instruction still
-// writes 1 KB of full lines -- the traceback then reads whole segments instead of 12-16 bytes out of fifteen 128-byte lines per
-// tile (vsx_device.hip).  The step count of such a task is a multiple of 8.  MEASURED (r02, profiles/r02_ckt_ab.txt): the
-// traceback fetches 35 % fewer bytes (FETCH_SIZE 9.68e6 -> 6.26e6 KiB per launch) but runs only 1.7 % faster -- it is bound by
-// latency at 2.5 waves per SIMD, not by HBM -- while the DP kernel pays 5 % for the barriers and the extra LDS traffic:
-// 6 634 -> 6 384 GCUPS.  Kept as an A/B build (-DVSX_CKT=1), default OFF.
-#ifndef VSX_CKT
-#define VSX_CKT 0
-#endif
 // TILT class: byte query profile in LDS (primed scores are 0 .. 255) read ONE STEP AHEAD: a lane's column symbol of step t+1 is
 // its neighbour's symbol of step t, so the profile rows of the next step are requested while the current step's rows are computed
-// and the step never starts with an LDS round trip.  0 = int16 profile read at the top of the step (r01).
-#ifndef VSX_QPL
-#define VSX_QPL 1
-#endif
-// TILT class: the FEED2 record of the look-ahead kernels (vsx_device.hip); 0 = the r04 record (A/B)
-#ifndef VSX_FEED2
-#define VSX_FEED2 1
-#endif
+// and the step never starts with an LDS round trip; its column record is the FEED2 record (vsx_device.hip).
 // TILT class, R >= VSX_MID_MIN_ROWS rows per lane: the DP kernel stores a SECOND row checkpoint per step, after the middle row of
 // every pipeline position, and lays the column checkpoints out per half; the traceback's tiles are then R/2 rows high -- half the
 // recompute area per crossing and half the register state per lane (the R >= 18 tracebacks sat at 2 waves per SIMD on registers).
@@ -40,7 +23,7 @@
 #ifndef VSX_MID_MIN_ROWS
 #define VSX_MID_MIN_ROWS 18
 #endif
-#define VSX_MID(R_, TILT_) ((TILT_) && (R_) >= VSX_MID_MIN_ROWS && !VSX_CKT)
+#define VSX_MID(R_, TILT_) ((TILT_) && (R_) >= VSX_MID_MIN_ROWS)
 
 // Device-side constants derived from the 14 post-fixup penalties (reference search16_init,
 // core/align_simd.cpp:1282-1376 and the QR/R vectors at :1629-1649).  "pk" = the int16 value
@@ -88,7 +71,7 @@ struct VsxFilterDev {
   int64_t maxsubs, maxgaps, mincols, maxdiffs;
   // r06, ranked plans (vsx_align_pairs_ranked): the traceback's epilogue appends every accepted / weak pair (plan-local pair index + the
   // identity the filter compared) and every pair the 16-bit DP refused at run time to two lists -- the hand-written compaction that
-  // replaces the flag kernel + rocPRIM scan / scatter / segmented sort over ALL pairs of a plan (vsx_rank.hip).  rank_counts == nullptr: off.
+  // the host then orders (vsx_host.cpp fetch_ranked_lists).  rank_counts == nullptr: off.
   uint32_t * rank_counts;      // [0] kept, [1] refused
   uint32_t * kept_pair;
   double   * kept_id;
@@ -159,19 +142,9 @@ hipError_t vsx_launch_chimera_eval(const VsxChimItem * d_items, uint32_t nitems,
                                    const VsxPairOut * d_hits, const uint32_t * d_runs, uint64_t n_runs, VsxChimParams P,
                                    void * d_out, hipStream_t st);
 
-// vsx_rank.hip: keep flags + identities + exclusive scan (d_temp == NULL: only *temp_bytes is set) ...
+// vsx_rank.hip: the fields of the kept pairs, in the order of d_kept_pair, gathered into r
 hipError_t vsx_rank_gather_list(const uint32_t * d_kept_pair, const double * d_kept_id, uint32_t kept, const VsxPairOut * d_out,
                                 const uint64_t * d_text_off, VsxRankedOut r, hipStream_t st);
-hipError_t vsx_rank_flag_scan(VsxFilterDev F, int keep_weak, const VsxPairOut * d_out, const uint32_t * d_pair_ids,
-                              const uint32_t * d_pair_slot, const VsxTask * d_tasks, uint32_t ngpu_pairs, uint32_t n_pairs,
-                              const uint32_t * d_runs, uint64_t runs_capacity, uint32_t * d_flag, uint32_t * d_pos, double * d_id,
-                              uint32_t * d_refused /* [0] = count, then the pairs the DP refused at run time */,
-                              void * d_temp, size_t * temp_bytes, hipStream_t st);
-// ... then compaction, per-query stable sort by identity (descending) and the gather of the kept pairs' fields
-hipError_t vsx_rank_sort_gather(const uint32_t * d_flag, const uint32_t * d_pos, const double * d_id, uint32_t n_pairs, uint32_t kept,
-                                const uint32_t * d_qstart, uint32_t ngroups, double * d_key_in, double * d_key_out,
-                                uint32_t * d_val_in, uint32_t * d_val_out, uint32_t * d_seg, const VsxPairOut * d_out,
-                                const uint64_t * d_text_off, VsxRankedOut r, void * d_temp, size_t * temp_bytes, hipStream_t st);
 
 // vsx_tbtext.hip: run lists -> CIGAR text (pushop / finishop, align_simd.cpp:1013-1049) + records -> output arrays
 hipError_t vsx_launch_cigar_text(const VsxPairOut * d_out, const uint32_t * d_pair_ids, uint32_t npairs,
@@ -187,19 +160,11 @@ hipError_t vsx_launch_revcomp(uint8_t * d_codes, const uint64_t * d_src_off, con
 hipError_t vsx_launch_encode(const uint8_t * d_ascii, uint8_t * d_codes, uint64_t nbytes, hipStream_t st);
 hipError_t vsx_launch_purity(const uint8_t * d_codes, const uint64_t * d_off, const uint32_t * d_len,
                              uint64_t nseq, uint8_t * d_impure, hipStream_t st);
-// rows must be one of vsx_supported_rows(); generic != 0 selects the LDS score-table variant;
-// track == 0 selects the variant without overflow (H min/max) tracking
+// rows must be one of vsx_supported_rows(); track == 0 selects the variant without overflow (H min/max) tracking
 // nq = tasks per wave (1; 2 / 4 = the sparse-task classes of the TILT family: tasks of <= 4 / <= 2 targets in their first slots)
-hipError_t vsx_launch_forward(int rows, int generic, int track, int ckpt, int nq, int one /* every task single-strip */, VsxDevParams P, const VsxTask * d_tasks, uint32_t ntasks,
+hipError_t vsx_launch_forward(int rows, int track, int nq, int one /* every task single-strip */, VsxDevParams P, const VsxTask * d_tasks, uint32_t ntasks,
                               const uint8_t * d_qcodes, const uint8_t * d_tcodes,
                               uint32_t * d_dir, uint2 * d_strip, VsxSlotOut * d_slot, hipStream_t st);
-hipError_t vsx_launch_traceback(VsxDevParams P, const VsxTask * d_tasks, const uint32_t * d_pair_slot,
-                                const uint32_t * d_pair_ids, uint32_t npairs,
-                                const uint8_t * d_qcodes, const uint8_t * d_tcodes,
-                                const uint32_t * d_dir, const VsxSlotOut * d_slot,
-                                uint32_t * d_slab, const uint64_t * d_slab_off,
-                                uint32_t * d_runs, uint64_t runs_capacity, unsigned long long * d_cursor,
-                                VsxPairOut * d_out, hipStream_t st);
 // fast16: the tasks never saturate (planner's TRACK = 0 class) -> biased-u16 VOP2 arithmetic in the tile recompute
 hipError_t vsx_launch_traceback_ck(int rows, int fast16, VsxDevParams P, VsxFilterDev F, const VsxTask * d_tasks, const uint32_t * d_pair_slot,
                                    const uint32_t * d_pair_ids, uint32_t npairs,

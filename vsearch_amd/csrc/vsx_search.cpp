@@ -1675,8 +1675,6 @@ static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, 
             }
         // (r06: a consumer's plans follow one another, and vsx_plan_create gives such plans the context's largest idle block: only
         //  block 0 is ever used here, the other two are no longer levelled -- they would be reserved for nothing)
-        static const bool rotate_env = std::getenv("VSX_CK_ROTATE") && std::strcmp(std::getenv("VSX_CK_ROTATE"), "1") == 0;
-        if (rotate_env) want[1] = want[2] = want[0];
         if (timeline) std::fprintf(stderr, "  [%7.1f ms] stages joined\n", (now_s() - t_begin) * 1e3);
         for (vsx_ctx * c : all) if (c) (void) vsx_internal_scratch_reserve(c, want);
         if (timeline) std::fprintf(stderr, "  [%7.1f ms] scratch levelled\n", (now_s() - t_begin) * 1e3);
