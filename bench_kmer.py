@@ -168,7 +168,7 @@ def main():
                           "bytes": int(first["index_postings"]) * 2},
                 "increments_per_s": round(best["postings_streamed"] / (best["kernel_ms"] * 1e-3), 1),
                 "bytes_per_posting": round(bytes_streamed / max(1, best["postings_streamed"]), 3),
-                "roofline": {"kernel": "vsx_kmer_count_packed_kernel / vsx_kmer_count_kernel (VSX_KMER_PACKED=0)", "bound": "hbm", "achieved": round(gbps, 1), "peak": 8000.0,
+                "roofline": {"kernel": "vsx_kmer_count_packed_kernel / vsx_kmer_count_kernel", "bound": "hbm", "achieved": round(gbps, 1), "peak": 8000.0,
                              "unit": "GB/s", "frac": round(gbps / 8000.0, 4), "traffic": traffic,
                              "traffic_note": (pmc if traffic is None else
                                               {"per": "batch of all queries (the count kernel's launches of one vsx_kmer_count_batch call summed)",

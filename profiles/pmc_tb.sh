@@ -1,6 +1,5 @@
 #!/bin/bash
 # profiles/pmc_tb.sh [bench args] -- SQ counter passes over one kernels-only bench step; prints the traceback kernels' sums
-# (env such as VSX_TB_V1=1 selects the kernel)
 cd /tmp && export TMPDIR=/tmp
 for SET in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_LDS SQ_WAIT_INST_LDS" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM" \

@@ -2335,10 +2335,9 @@ extern "C" hipError_t vsx_launch_traceback_ck(int rows, int fast16, VsxDevParams
                                               VsxPairOut * out, hipStream_t st)
 {
   if (npairs == 0) return hipSuccess;
-  static const bool v1_env = std::getenv("VSX_TB_V1") != nullptr;          // A/B: the first kernel for the TILT class too
   int dev_now = 0;
   if (hipGetDevice(&dev_now) != hipSuccess) { (void) hipGetLastError(); dev_now = 64; }
-  const bool v2 = g_tb_v1_dev[dev_now < 0 || dev_now > 64 ? 64 : dev_now].load(std::memory_order_relaxed) == 0 && !v1_env;
+  const bool v2 = g_tb_v1_dev[dev_now < 0 || dev_now > 64 ? 64 : dev_now].load(std::memory_order_relaxed) == 0;
 #define TBCK(RR) case RR: return (fast16 && P.tilt != 0 && v2 && RR >= 4) ? launch_tbtilt<RR, VSX_MID(RR, true)>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st) \
                                  : (fast16 && P.tilt != 0) ? launch_tbck<RR, true, true, VSX_MID(RR, true)>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st) \
                                  : fast16 ? launch_tbck<RR, true>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st) \

@@ -91,12 +91,11 @@ struct DevBuf {
 // Scratch pool: hipMalloc/hipFree of the multi-GB checkpoint, slab and run buffers cost seconds per plan (page-table
 // set-up), far more than the kernels of a 500 k-pair stage.  A context keeps the blocks its finished plans give back and
 // hands them to the next plan (best fit, but never a block more than 4x + 1 MB larger than the request: a retired multi-GB
-// checkpoint block must not end up pinned under an 8-byte cursor).  VSX_POOL=0 disables it; vsx_destroy frees everything.
+// checkpoint block must not end up pinned under an 8-byte cursor).  vsx_destroy frees everything.
 struct PoolBlock { void * p; size_t bytes; };
 struct ScratchPool {
   std::vector<PoolBlock> free_blocks;
   std::mutex mu;
-  bool enabled = true;
   bool retired = false;                 // the owning context is gone (sequence sets may outlive it): nothing is kept any more
   ~ScratchPool() { for (PoolBlock & b : free_blocks) (void) hipFree(b.p); }
   hipError_t get(size_t bytes, void ** out, size_t * got)
@@ -152,7 +151,6 @@ struct ScratchPool {
   void put(void * p, size_t bytes)
   {
     if (!p) return;
-    if (!enabled) { (void) hipFree(p); return; }
     std::lock_guard<std::mutex> lk(mu);
     if (retired) { (void) hipFree(p); return; }
     free_blocks.push_back(PoolBlock {p, bytes});
@@ -682,7 +680,6 @@ int vsx_create(vsx_ctx ** out, const vsx_scoring * s, int device)
   auto * c = new vsx_ctx;
   c->device = device;
   c->sc = *s;
-  if (const char * mode = std::getenv("VSX_POOL")) c->pool.enabled = std::strcmp(mode, "0") != 0;
   if (const char * mode = std::getenv("VSX_TB_ARITH")) c->tb_packed = std::strcmp(mode, "packed") == 0;
 
   // search16_init, align_simd.cpp:1282-1376: scores must fit a CELL, each penalty SHRT_MAX/(1+CDEPTH)
@@ -754,8 +751,7 @@ int vsx_create(vsx_ctx ** out, const vsx_scoring * s, int device)
   // traces of one call: profiles/r03/r03v_e2e_trace*.csv).
   int prio_low = 0, prio_high = 0;
   (void) hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);            // numerically: high < low
-  static const bool flat_env = std::getenv("VSX_ALIGN_FLAT_PRIORITY") != nullptr;      // A/B
-  const int prio_dp = (!flat_env && prio_low - prio_high >= 2) ? prio_high + 1 : prio_high;
+  const int prio_dp = (prio_low - prio_high >= 2) ? prio_high + 1 : prio_high;
   // (r04 measured CU-masked streams -- a fixed share of the CUs for the traceback -- and rejected them: the DP kernel ran 2 x slower,
   //  profiles/r04/r04p_e2e_cumask_ab.txt; the VSX_TB_CUS switch is gone: masked streams also lose hipStreamNonBlocking and the priorities)
   if ((e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_dp)) != hipSuccess ||
@@ -1312,7 +1308,6 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
   // symbols short of 289 -- took 0.15 ms of DP and 0.61 ms of traceback, 11 % of the step's traceback time).  Any row count with
   // 16 R >= Q is valid for a query, so the tasks of a sparse class join the next denser class of the same kind.
   {
-    static const bool no_promote = std::getenv("VSX_NO_PROMOTE") != nullptr;      // A/B, tests
     struct Cls { int rows, track, tilt, nq; size_t count; };
     std::vector<Cls> cls;
     for (const ProtoTask & pt : protos)
@@ -1322,7 +1317,7 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
         if (!found) cls.push_back(Cls {pt.rows, pt.track, pt.tilt, pt.nq, 1});
       }
     std::vector<std::pair<size_t, int>> move;                                 // class index -> new rows
-    for (size_t a = 0; a < cls.size() && !no_promote; ++a)
+    for (size_t a = 0; a < cls.size(); ++a)
       {
         int best = 0;
         for (const Cls & c : cls)
@@ -2185,10 +2180,9 @@ static int align_pairs_impl(vsx_ctx * ctx, const vsx_seqset * queries, const vsx
   // (profiles/r04/r04m_e2e_timeline.txt) is GPU-bound from the first launch to the last kernel, so what the caller waits for beyond
   // the kernels is the planning of the first slice (2.7 ms for 100 k pairs) and the traceback + text + download of the last one;
   // both shrink with their slice, and the planner (15 ns per pair) outruns the GPU (35 ns per pair) by the second slice.
-  // VSX_PIPELINE_RAMP=0: the r03 schedule (half, full ..., half).
-  static const bool ramp = !(std::getenv("VSX_PIPELINE_RAMP") && std::strcmp(std::getenv("VSX_PIPELINE_RAMP"), "0") == 0);
+  // Lists shorter than three slices keep the r03 schedule (half, full ..., half).
   std::vector<uint64_t> sizes;
-  if (ramp && n_pairs >= 3 * slice_pairs)
+  if (n_pairs >= 3 * slice_pairs)
     {
       const uint64_t head[2] = {slice_pairs / 4, slice_pairs / 2};
       const uint64_t mid = n_pairs - 2 * (head[0] + head[1]);
@@ -2215,8 +2209,6 @@ static int align_pairs_impl(vsx_ctx * ctx, const vsx_seqset * queries, const vsx
   const size_t S = cut.size() - 1;
   const uint64_t slice_budget = 0;       // the context's shared checkpoint block (the plans execute in stream order)
   std::vector<vsx_plan *> plans(S, nullptr);
-  std::vector<int> plan_rc(S, VSX_OK);
-  std::vector<std::string> plan_msg(S);
   if (!sink)
     {
       const int arc = results_alloc(out, n_pairs, filter != nullptr);
@@ -2224,22 +2216,20 @@ static int align_pairs_impl(vsx_ctx * ctx, const vsx_seqset * queries, const vsx
     }
   std::mutex mu;
   std::condition_variable cv;
-  size_t consumed = 0;
-  std::vector<char> is_ready(S, 0);
+  size_t consumed = 0, planned = 0;      // slices [0, planned) have been planned; a failed one is the last and leaves plans[i] null
   bool stop = false;
   int plan_failed = VSX_OK;
   std::string plan_failed_msg;
-  static const size_t depth = std::getenv("VSX_PIPELINE_DEPTH") ? (size_t) std::max(1, std::min(6, std::atoi(std::getenv("VSX_PIPELINE_DEPTH")))) : 2;
-  // r06, measured and NOT adopted: VSX_PLANNERS=2 / 3 planner threads (slices i = k, k + n, ...; plans of one context may be made
-  // concurrently: pool, block and slot choices are locked, uploads share stream_up).  A planner needs 2.1-2.8 ms per slice where the
-  // GPU needs 5.3, so a second one only adds contention: 29.9 / 31.2 ms per 800 k-pair call with one, 30.6 / 35.4 with two, 30.8 with
-  // three (profiles/r06/r06r_e2e_planners_ab.txt).  What the call loses against its 25.4 ms of kernels is on the device: the traceback of
+  const size_t depth = 2;
+  // One planner thread, in slice order.  r06 measured two and three (plans of one context may be made concurrently: pool, block and
+  // slot choices are locked, uploads share stream_up): a planner needs 2.1-2.8 ms per slice where the GPU needs 5.3, so a second one
+  // only adds contention: 29.9 / 31.2 ms per 800 k-pair call with one, 30.6 / 35.4 with two, 30.8 with three
+  // (profiles/r06/r06r_e2e_planners_ab.txt).  What the call loses against its 25.4 ms of kernels is on the device: the traceback of
   // slice i runs starved beside the DP kernels of slices i + 1, i + 2 (a retiring DP wave frees 128 VGPRs, a traceback wave needs 168),
   // and the slice that reuses its checkpoint block waits for it.
-  static const size_t n_planners = std::getenv("VSX_PLANNERS") ? (size_t) std::max(1, std::min(4, std::atoi(std::getenv("VSX_PLANNERS")))) : 1;
-  auto planner_body = [&](size_t first_slice) {
+  std::thread planner([&]() {
     (void) hipSetDevice(ctx->device);
-    for (size_t i = first_slice; i < S; i += n_planners)
+    for (size_t i = 0; i < S; ++i)
       {
         {
           std::unique_lock<std::mutex> lk(mu);
@@ -2250,21 +2240,16 @@ static int align_pairs_impl(vsx_ctx * ctx, const vsx_seqset * queries, const vsx
         int rc = vsx_plan_create(ctx, &pl, queries, targets, cut[i + 1] - cut[i], qidx + cut[i], tidx + cut[i], slice_budget);
         if (rc == VSX_OK && filter) rc = vsx_plan_set_filter(pl, filter);
         if (rc == VSX_OK && sink) rc = plan_set_ranked(pl);
-        if (rc != VSX_OK) { plan_msg[i] = vsx_last_error(); if (pl) vsx_plan_destroy(pl); pl = nullptr; }
+        std::string err;
+        if (rc != VSX_OK) { err = vsx_last_error(); if (pl) vsx_plan_destroy(pl); pl = nullptr; }
         if (timing) std::fprintf(stderr, "  slice %zu (%llu pairs): planned at %.1f ms\n", i, (unsigned long long) (cut[i + 1] - cut[i]), (now() - t_begin) * 1e3);
         std::lock_guard<std::mutex> lk(mu);
-        plans[i] = pl; plan_rc[i] = rc; is_ready[i] = 1;
-        cv.notify_all();
-        if (rc != VSX_OK)                                          // (the consumer stops at this slice or, if the other planner then
-          {                                                        //  leaves an earlier one unplanned, at that one: plan_failed)
-            if (plan_failed == VSX_OK) { plan_failed = rc; plan_failed_msg = plan_msg[i]; }
-            stop = true;
-            return;
-          }
+        plans[i] = pl; planned = i + 1;
+        if (rc != VSX_OK) { plan_failed = rc; plan_failed_msg = err; }
+        cv.notify_all();                                           // (also wakes the consumer waiting on a failed plan)
+        if (rc != VSX_OK) return;
       }
-  };
-  std::vector<std::thread> planners;
-  for (size_t k = 0; k < std::min(n_planners, S); ++k) planners.emplace_back(planner_body, k);
+  });
   int rc = VSX_OK;
   std::string msg;
   size_t launched = 0;
@@ -2288,20 +2273,18 @@ static int align_pairs_impl(vsx_ctx * ctx, const vsx_seqset * queries, const vsx
     {
       {
         std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return is_ready[i] != 0 || plan_failed != VSX_OK; });
-        if (!is_ready[i]) { rc = plan_failed; msg = plan_failed_msg; break; }
+        cv.wait(lk, [&] { return i < planned; });
+        if (!plans[i]) { rc = plan_failed; msg = plan_failed_msg; break; }
       }
-      if (plan_rc[i] != VSX_OK) { rc = plan_rc[i]; msg = plan_msg[i]; break; }
       // odd slices launch their DP kernels on the second DP stream: a slice is ~3-6 rounds of resident waves, its last round drains
       // for about half a wave's lifetime, and a launch on the same stream would wait for that (inputs are complete: plan_create
       // has synchronised its uploads; the two checkpoint blocks alternate the same way)
-      static const bool alt_env = !(std::getenv("VSX_ALIGN_ALT_STREAM") && std::strcmp(std::getenv("VSX_ALIGN_ALT_STREAM"), "0") == 0);
-      plans[i]->alt_fwd = alt_env && (i & 1);
+      plans[i]->alt_fwd = (i & 1) != 0;
       rc = vsx_plan_run(plans[i]);                       // asynchronous: queued behind slice i-1 on the context's streams
       if (timing) std::fprintf(stderr, "  slice %zu: queued at %.1f ms\n", i, (now() - t_begin) * 1e3);
       if (rc != VSX_OK) { msg = vsx_last_error(); break; }
       launched = i + 1;
-      // `depth` slices stay queued behind the one being fetched (VSX_PIPELINE_DEPTH, default 2): the DP kernels of slice i+1 overlap
+      // `depth` slices stay queued behind the one being fetched: the DP kernels of slice i+1 overlap
       // the traceback of slice i, so the GPU needs the next launch in its queue before the previous slice has drained.  r04 A/B
       // (profiles/r04/r04q_e2e_depth_ab.txt): 3 or 4 queued slices are no better -- a traceback makes little progress beside the DP
       // kernels queued after it (its waves need 256 VGPRs, a retiring DP wave frees 128), so deeper queues only move the wait.
@@ -2314,7 +2297,7 @@ static int align_pairs_impl(vsx_ctx * ctx, const vsx_seqset * queries, const vsx
     stop = true;
   }
   cv.notify_all();
-  for (std::thread & t : planners) t.join();
+  planner.join();
   for (size_t i = 0; i < S; ++i)
     if (plans[i]) { vsx_plan_destroy(plans[i]); plans[i] = nullptr; }
   if (rc != VSX_OK)

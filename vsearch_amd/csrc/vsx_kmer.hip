@@ -268,10 +268,8 @@ __global__ void __launch_bounds__(BITS == 8 ? 512 : 1024) __attribute__((amdgpu_
 vsx_kmer_count_kernel(const uint4 * __restrict__ postings, const u64 * __restrict__ bucket_start, const uint2 * __restrict__ R,
                       u32 ntiles, u32 nseq, const u64 * __restrict__ qk_start, const u32 * __restrict__ qk, const u32 * __restrict__ minmatch,
                       const u32 * __restrict__ qlist, u32 slot_base, u32 nslots, uint2 * __restrict__ rec, u32 subcap,
-                      u32 * __restrict__ tile_count, int probe)
+                      u32 * __restrict__ tile_count)
 {
-  // probe (VSX_KMER_PROBE, measurements only -- results are wrong): bit 0 = no LDS atomics (the loads are still consumed),
-  // bit 1 = no postings loads (addresses synthesised), bit 2 = no final sweep
   constexpr int THREADS = (BITS == 8) ? 512 : 1024;
   constexpr int WAVES = THREADS / 64;
   constexpr int PER = 32 / BITS;                                  // counters per dword
@@ -335,11 +333,9 @@ vsx_kmer_count_kernel(const uint4 * __restrict__ postings, const u64 * __restric
         }
       // Wave w takes the buckets w, w + WAVES, ...; the loop below broadcasts lane j's range with v_readlane -- the streaming
       // loop touches the LDS with ds_add_u32 ONLY
-      u32 sink = 0;
       auto consume = [&](const uint4 & v, u32 tag) __attribute__((always_inline)) {
         const u32 w4[4] = {v.x, v.y, v.z, v.w};
-        if (probe & 1) sink ^= w4[0] + w4[1] + w4[2] + w4[3];
-        else if (TAG)
+        if (TAG)
           {
 #pragma unroll
             for (int d = 0; d < 4; ++d) if ((w4[d] >> 16) == tag) bump(w4[d] & 0xffffu);
@@ -349,10 +345,6 @@ vsx_kmer_count_kernel(const uint4 * __restrict__ postings, const u64 * __restric
 #pragma unroll
             for (int d = 0; d < 4; ++d) { bump(w4[d] & 0xffffu); bump(w4[d] >> 16); }
           }
-      };
-      auto unit = [&](u32 idx) __attribute__((always_inline)) -> uint4 {
-        if (probe & 2) { const u32 z = (idx * 2654435761u) & 0x7fff7fffu; return make_uint4(z, (z ^ 0x01230456u) & 0x7fff7fffu, (z ^ 0x10002000u) & 0x7fff7fffu, (z ^ 0x5a5a2b2bu) & 0x7fff7fffu); }
-        return postings[idx];
       };
       // first 64 units of KM_LOADS buckets per trip (a bucket of the bench shape has ~61 units); the loads of trip t + 1 are
       // issued before the atomics of trip t.  Longer buckets: their remaining units follow in a tail loop.
@@ -366,7 +358,7 @@ vsx_kmer_count_kernel(const uint4 * __restrict__ postings, const u64 * __restric
                 const u32 n = (u32) __builtin_amdgcn_readlane((int) mine_rng.y, j0 + u);
                 const u32 r0 = (u32) __builtin_amdgcn_readlane((int) mine_rng.x, j0 + u);
                 on[u] = (u32) lane < n;
-                if (on[u]) s4[u] = unit(r0 + (u32) lane);
+                if (on[u]) s4[u] = postings[r0 + (u32) lane];
               }
           }
       };
@@ -390,7 +382,7 @@ vsx_kmer_count_kernel(const uint4 * __restrict__ postings, const u64 * __restric
                   {
                     const u32 r0 = (u32) __builtin_amdgcn_readlane((int) mine_rng.x, j0 + u);
                     const u32 tg = TAG ? (u32) __builtin_amdgcn_readlane((int) mine_tag, j0 + u) : 0u;
-                    for (u32 i = 64u + (u32) lane; i < n; i += 64u) consume(unit(r0 + i), tg);
+                    for (u32 i = 64u + (u32) lane; i < n; i += 64u) consume(postings[r0 + i], tg);
                   }
               }
           if (more)
@@ -399,10 +391,8 @@ vsx_kmer_count_kernel(const uint4 * __restrict__ postings, const u64 * __restric
               for (int u = 0; u < KM_LOADS; ++u) { cur[u] = nxt[u]; con[u] = non[u]; }
             }
         }
-      if ((probe & 1) && sink == 0x9e3779b9u) cnt[NDW] = sink;       // keeps the probe's loads alive
     }
   __syncthreads();
-  if (probe & 4) { if (tid == 0) tile_count[region] = 0; return; }
   // ---- sweep: counters >= mm -> (sequence, count) records in the (query, tile) sub-region.  Hits are rare (a fraction of a per
   // cent of the counters), so a lane first tests whole dwords (SWAR for the byte counters); a wave-level prefix sum and one
   // exchange through LDS give every lane its position -- no atomic, the sub-region belongs to this block.
@@ -549,13 +539,12 @@ vsx_kmer_pk_walk_kernel(const u32 * __restrict__ keys, u64 n, u32 tile, u32 ntil
 }
 
 // Counting on the packed index.  PRE as in vsx_kmer_count_kernel (the 8-bit class reads its ranges from the pre-pass table).
-// PROBE (timing only, results are wrong): the 16-bit index read as if it were packed, 9/16 of every bucket's units.
-template <int BITS, bool PRE, bool PROBE = false>
+template <int BITS, bool PRE>
 __global__ void __launch_bounds__(BITS == 8 ? 512 : 1024) __attribute__((amdgpu_waves_per_eu(8, 8)))
 vsx_kmer_count_packed_kernel(const uint4 * __restrict__ postings, const u64 * __restrict__ bucket_start, const uint2 * __restrict__ R,
                              u32 ntiles, u32 nseq, const u64 * __restrict__ qk_start, const u32 * __restrict__ qk, const u32 * __restrict__ minmatch,
                              const u32 * __restrict__ qlist, u32 slot_base, u32 nslots, uint2 * __restrict__ rec, u32 subcap,
-                             u32 * __restrict__ tile_count, int probe)
+                             u32 * __restrict__ tile_count)
 {
   constexpr int THREADS = (BITS == 8) ? 512 : 1024;
   constexpr int WAVES = THREADS / 64;
@@ -588,14 +577,11 @@ vsx_kmer_count_packed_kernel(const uint4 * __restrict__ postings, const u64 * __
     if (BITS == 8) atomicAdd(&cnt[x >> 2], 1u << ((x & 3u) << 3));
     else atomicAdd(&cnt[x >> 1], 1u << ((x & 1u) << 4));
   };
-  u32 sink = 0;
   auto consume = [&](const uint4 & v) __attribute__((always_inline)) {
-    if (probe & 1) { sink ^= v.x + v.y + v.z + v.w; return; }
     u32 acc = v.x & 0xffffu;
-    if (PROBE) acc &= 0x7fffu;
     bump(acc);
-    acc += (v.x >> 16) & 0xffu; if (PROBE) acc &= 0x7fffu; bump(acc);
-    acc += v.x >> 24; if (PROBE) acc &= 0x7fffu; bump(acc);
+    acc += (v.x >> 16) & 0xffu; bump(acc);
+    acc += v.x >> 24; bump(acc);
     const u32 d3[3] = {v.y, v.z, v.w};
 #pragma unroll
     for (int e = 0; e < 3; ++e)
@@ -603,7 +589,6 @@ vsx_kmer_count_packed_kernel(const uint4 * __restrict__ postings, const u64 * __
       for (int b = 0; b < 4; ++b)
         {
           acc += (d3[e] >> (8 * b)) & 0xffu;
-          if (PROBE) acc &= 0x7fffu;
           bump(acc);
         }
   };
@@ -626,8 +611,7 @@ vsx_kmer_count_packed_kernel(const uint4 * __restrict__ postings, const u64 * __
           __syncthreads();
           mine = (lane < BPW) ? rng[wave + WAVES * lane] : make_uint2(0u, 0u);
         }
-      u32 n = mine.y;
-      if (PROBE) n = (n * 9u + 15u) >> 4;
+      const u32 n = mine.y;
       // position of each of the wave's buckets in its run of units
       u32 incl = n;
 #pragma unroll
@@ -678,9 +662,7 @@ vsx_kmer_count_packed_kernel(const uint4 * __restrict__ postings, const u64 * __
           if (o2) consume(b2);
         }
     }
-  if ((probe & 1) && sink == 0x9e3779b9u) cnt[NDW] = sink;
   __syncthreads();
-  if (probe & 4) { if (tid == 0) tile_count[region] = 0; return; }
   // the dummies have collected the hops and the padding (~20 increments each): cleared here, or nearly every dword that holds one
   // would look like a hit to the sweep's dword test (26 ms of 113 before this).  Dummy k = counter 251 + 252 k = the top byte of
   // dword 62 + 63 k (8-bit counters) / the top half of dword 125 + 126 k (16-bit)
@@ -909,17 +891,15 @@ extern "C" hipError_t vsx_kmer_launch_count(int bits, int tagged, const uint32_t
   // slots [slot_base, slot_base + nslots) of the batch; ranges / rec / tile_count belong to THESE slots (indexed from 0)
   // tagged: 0 = 16-bit postings, 1 = tagged postings (word lengths 9..15), 2 = packed postings
   if (nslots == 0 || nseq == 0) return hipSuccess;
-  static const int probe = std::getenv("VSX_KMER_PROBE") ? std::atoi(std::getenv("VSX_KMER_PROBE")) : 0;
+  // the 8-bit class of an untagged index reads its bucket ranges from the pre-pass table (vsx_kmer_launch_ranges)
+  if (bits == 8 && tagged != 1 && !ranges) return hipErrorInvalidValue;
 #define KM_ARGS (const uint4 *) postings, (const u64 *) bucket_start, (const uint2 *) ranges, ntiles, nseq, (const u64 *) qk_start, qk, minmatch, qlist, slot_base, \
-                nslots, (uint2 *) rec, subcap, tile_count, probe
-  if (tagged == 2 && bits == 8 && ranges) hipLaunchKernelGGL((vsx_kmer_count_packed_kernel<8, true>), dim3(nslots, ntiles), dim3(512), 0, st, KM_ARGS);
-  else if (tagged == 2 && bits == 8) hipLaunchKernelGGL((vsx_kmer_count_packed_kernel<8, false>), dim3(nslots, ntiles), dim3(512), 0, st, KM_ARGS);
+                nslots, (uint2 *) rec, subcap, tile_count
+  if (tagged == 2 && bits == 8) hipLaunchKernelGGL((vsx_kmer_count_packed_kernel<8, true>), dim3(nslots, ntiles), dim3(512), 0, st, KM_ARGS);
   else if (tagged == 2) hipLaunchKernelGGL((vsx_kmer_count_packed_kernel<16, false>), dim3(nslots, ntiles), dim3(1024), 0, st, KM_ARGS);
   else if (tagged && bits == 8) hipLaunchKernelGGL((vsx_kmer_count_kernel<8, false, true>), dim3(nslots, ntiles), dim3(512), 0, st, KM_ARGS);
   else if (tagged) hipLaunchKernelGGL((vsx_kmer_count_kernel<16, false, true>), dim3(nslots, ntiles), dim3(1024), 0, st, KM_ARGS);
-  else if (bits == 8 && ranges && (probe & 8)) hipLaunchKernelGGL((vsx_kmer_count_packed_kernel<8, true, true>), dim3(nslots, ntiles), dim3(512), 0, st, KM_ARGS);
-  else if (bits == 8 && ranges) hipLaunchKernelGGL((vsx_kmer_count_kernel<8, true>), dim3(nslots, ntiles), dim3(512), 0, st, KM_ARGS);
-  else if (bits == 8) hipLaunchKernelGGL((vsx_kmer_count_kernel<8, false>), dim3(nslots, ntiles), dim3(512), 0, st, KM_ARGS);
+  else if (bits == 8) hipLaunchKernelGGL((vsx_kmer_count_kernel<8, true>), dim3(nslots, ntiles), dim3(512), 0, st, KM_ARGS);
   else hipLaunchKernelGGL((vsx_kmer_count_kernel<16, false>), dim3(nslots, ntiles), dim3(1024), 0, st, KM_ARGS);
 #undef KM_ARGS
   return hipGetLastError();

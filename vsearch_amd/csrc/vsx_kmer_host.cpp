@@ -155,9 +155,7 @@ int vsx_kmer_index_create(vsx_ctx * ctx, const vsx_seqset * db, int w, VsxKmerIn
   std::unique_ptr<VsxKmerIndex> ix(new VsxKmerIndex);
   ix->ctx = ctx; ix->db = db; ix->device = vsx_internal_device(ctx); ix->st = vsx_internal_stream(ctx); ix->w = w;
   ix->tagged = w > 8;
-  // the whole-set index of a short word length takes the packed format (VSX_KMER_PACKED=0: the 16-bit format, A/B and tests)
-  static const bool packed_off = std::getenv("VSX_KMER_PACKED") && std::strcmp(std::getenv("VSX_KMER_PACKED"), "0") == 0;
-  ix->packed = !ix->tagged && !packed_off;
+  ix->packed = !ix->tagged;                          // the whole-set index of a short word length takes the packed format
   ix->prewarm = true;
   ix->make_stream();
   KCHK(hipSetDevice(ix->device));
@@ -346,33 +344,24 @@ int count_pass(VsxKmerIndex * ix, KmerScratch * sc, uint32_t nslots, uint32_t n8
   KCHK(sc->d_tilecnt.ensure((size_t) nslots * nt));
   KCHK(sc->d_sel_mn.ensure(nslots));
   KCHK(sc->d_sel_off.ensure(nslots));
-  static const bool no_pre_env = std::getenv("VSX_KMER_NO_RANGES") != nullptr;   // A/B: the blocks look their ranges up themselves
-  const bool no_pre = no_pre_env || ix->tagged;                                   // tagged indexes (word lengths 9..15) always do
+  const bool pre = n8 && !ix->tagged;                                             // the 8-bit class of an untagged index: ranges pre-pass
   const int tg = ix->tagged ? 1 : (ix->packed ? 2 : 0);                           // the postings format (vsx_kmer_launch_count)
-  if (n8 && !no_pre) KCHK(sc->d_ranges.ensure((size_t) n8 * nt * 256));
+  if (pre) KCHK(sc->d_ranges.ensure((size_t) n8 * nt * 256));
   KCHK(hipEventRecord(sc->e0, sc->st));
-  if (n8 && !no_pre)
+  if (pre)
     KCHK(vsx_kmer_launch_ranges(ix->d_start.p, nt, sc->d_qk_start.p, sc->d_qk.p, sc->d_minmatch.p, d_qlist, n8, sc->d_ranges.p, sc->st));
   // Counting kernels of concurrent batches take turns in arrival order: each fills the device on its own, so two at once only
   // finish BOTH late (the search's windows then reach the aligner in pairs and its last stage starts later); uploads, ranges,
-  // selection and downloads of the other batch still overlap.  VSX_KMER_TURNS=0: free-running (A/B).
-  static const bool turns = !(std::getenv("VSX_KMER_TURNS") && std::strcmp(std::getenv("VSX_KMER_TURNS"), "0") == 0);
-  std::unique_lock<std::mutex> turn(ix->turn_mu, std::defer_lock);
-  if (turns)
-    {
-      turn.lock();
-      if (ix->turn_ev) KCHK(hipStreamWaitEvent(sc->st, ix->turn_ev, 0));
-    }
-  KCHK(vsx_kmer_launch_count(8, tg, ix->d_post.p, ix->d_start.p, (n8 && !no_pre) ? sc->d_ranges.p : nullptr, nt, ix->nseq, n8, 0, sc->d_qk_start.p, sc->d_qk.p,
+  // selection and downloads of the other batch still overlap.
+  std::unique_lock<std::mutex> turn(ix->turn_mu);
+  if (ix->turn_ev) KCHK(hipStreamWaitEvent(sc->st, ix->turn_ev, 0));
+  KCHK(vsx_kmer_launch_count(8, tg, ix->d_post.p, ix->d_start.p, pre ? sc->d_ranges.p : nullptr, nt, ix->nseq, n8, 0, sc->d_qk_start.p, sc->d_qk.p,
                              sc->d_minmatch.p, d_qlist, sc->d_rec.p, subcap, sc->d_tilecnt.p, sc->st));
   KCHK(vsx_kmer_launch_count(16, tg, ix->d_post.p, ix->d_start.p, nullptr, nt, ix->nseq, nslots - n8, n8, sc->d_qk_start.p, sc->d_qk.p,
                              sc->d_minmatch.p, d_qlist, sc->d_rec.p + (size_t) n8 * nt * subcap, subcap, sc->d_tilecnt.p + (size_t) n8 * nt, sc->st));
-  if (turns)
-    {
-      KCHK(hipEventRecord(sc->e_turn, sc->st));
-      ix->turn_ev = sc->e_turn;
-      turn.unlock();
-    }
+  KCHK(hipEventRecord(sc->e_turn, sc->st));
+  ix->turn_ev = sc->e_turn;
+  turn.unlock();
   uint64_t capacity = std::max<uint64_t>(sc->d_dense.n, std::max<uint64_t>(1u << 20, (uint64_t) nslots * 128));
   unsigned long long produced = 0;
   for (int attempt = 0; attempt < 2; ++attempt)

@@ -1083,7 +1083,6 @@ int vsx_searcher_create(vsx_ctx * ctx, vsx_searcher ** out, const vsx_search_opt
   S->ma = (opts->maxaccepts == 0 || opts->maxaccepts > sc) ? sc : opts->maxaccepts;
   S->tophits = std::min<int64_t>(S->mr + S->ma + 8, sc);
   S->threads = opts->threads > 0 ? opts->threads : usable_cpus();
-  if (opts->threads <= 0 && std::getenv("VSX_SEARCH_THREADS")) S->threads = std::max(1, std::atoi(std::getenv("VSX_SEARCH_THREADS")));      // A/B only
 
   // soft masking: the set keeps a case bitmap for its device k-mer index (the alignment itself is case-blind)
   // (2 = DUST: the device masks the set, vsx_mask.hip, and the host copy takes the result over -- from here on a dust-masked
@@ -1284,16 +1283,14 @@ static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, 
   static const bool lazy_search = !(std::getenv("VSX_SEARCH_LAZY") && std::strcmp(std::getenv("VSX_SEARCH_LAZY"), "0") == 0);
   // Windows of queries; the k-mer stage of window i+1 (host word extraction, device counting, host ranking) runs on a
   // producer thread while this thread aligns window i (a query's hits do not depend on its window).  Large batches use
-  // smaller windows so that the two stages overlap; VSX_SEARCH_PIPELINE=0 = one thread, as before.
-  static const bool pipe_off = std::getenv("VSX_SEARCH_PIPELINE") && std::strcmp(std::getenv("VSX_SEARCH_PIPELINE"), "0") == 0;
+  // smaller windows so that the two stages overlap; small batches and a fixed opts.window run on this thread alone.
   static const uint64_t env_window = std::getenv("VSX_SEARCH_WINDOW") ? std::strtoull(std::getenv("VSX_SEARCH_WINDOW"), nullptr, 10) : 0;   // tests
-  const bool piped = !pipe_off && (env_window ? nq > env_window : (S->o.window <= 0 && nq > 32768));
+  const bool piped = env_window ? nq > env_window : (S->o.window <= 0 && nq > 32768);
   const uint64_t window = env_window ? env_window : (S->o.window > 0 ? (uint64_t) S->o.window : (piped ? 16384 : 65536));
   // window boundaries.  Piped: the first windows are small (the GPU starts after the first window's words: a quarter, then half
   // a window), the last two shrink again (half, then a quarter: the last alignment stage is the only thing nothing overlaps)
   std::vector<uint64_t> cut {0};
-  static const int env_taper = std::getenv("VSX_SEARCH_TAPER") ? std::atoi(std::getenv("VSX_SEARCH_TAPER")) : 0;      // A/B
-  const int taper = std::min(std::max(env_taper ? env_taper : 2, 1), 6);          // the tail: window / 2, / 4, ... / 2^taper
+  const int taper = 2;                                                            // the tail: window / 2, / 4
   const bool graded = piped && !env_window && S->o.window <= 0;
   uint64_t head_tail = window / 4 + window / 2;
   for (int k = 1; k <= taper; ++k) head_tail += window >> k;
@@ -1333,14 +1330,13 @@ static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, 
   KmerAcct kacct;
   const bool both = S->o.strand_both != 0;
   // does any host step read a minus-strand query as text? (host k-mer path; idprefix / idsuffix / selfid compare symbols;
-  // the '*' penalties send every pair to the linear-memory aligner; VSX_RC_TEXT=1 forces it for tests)
-  static const bool rc_text_env = std::getenv("VSX_RC_TEXT") != nullptr;
+  // the '*' penalties send every pair to the linear-memory aligner)
   const bool dust = S->qmode == 2 && !raw_queries;                // every strand of every query is DUST-masked on its own (search.cpp:294-303)
   // r06, --hardmask on the queries (search.cpp:294-303): the masked symbols of each strand become 'N' in the text the k-mer stage AND the
   // aligner read -- the window's strands then exist as (masked) text, which is what the device set is made from
   const bool hardq = (S->o.hardmask & 2) != 0 && S->qmode != 0 && !raw_queries;
   const bool per_strand = dust || hardq;          // every strand's words come from its own masked text
-  const bool need_rc_text = both && (!dev_kmer || S->o.idprefix > 0 || S->o.idsuffix > 0 || S->o.selfid != 0 || S->o.gap_infinite != 0 || rc_text_env || per_strand);
+  const bool need_rc_text = both && (!dev_kmer || S->o.idprefix > 0 || S->o.idsuffix > 0 || S->o.selfid != 0 || S->o.gap_infinite != 0 || per_strand);
 
   struct Window {
     uint64_t w0 = 0, wn = 0, ns = 0, mn = 0, hi = 0;
@@ -1593,11 +1589,10 @@ static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, 
           if (!s1.put(prepare_words(cut[wi]))) break;
         s1.finish();
       });
-      // three rank workers (VSX_SEARCH_RANKERS): one window's host work (CSR, uploads, record download, ranking) runs under another's counting
+      // three rank workers on the device k-mer path: one window's host work (CSR, uploads, record download, ranking) runs under another's counting
       // kernel (vsx_kmer_count_batch leases a scratch set and a stream per call); windows may reach the aligner out of order,
       // a query's hits do not depend on it
-      static const int env_rankers = std::getenv("VSX_SEARCH_RANKERS") ? std::atoi(std::getenv("VSX_SEARCH_RANKERS")) : 0;   // A/B
-      const int n_rank = dev_kmer ? std::min(std::max(env_rankers ? env_rankers : 3, 1), 4) : 1;
+      const int n_rank = dev_kmer ? 3 : 1;
       std::atomic<int> rank_live {n_rank};
       auto rank_worker = [&]() {
         for (;;)
@@ -1615,16 +1610,12 @@ static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, 
       for (int k = 0; k < n_rank; ++k) stage_rank.emplace_back(rank_worker);
       // two consumers, each with its own aligner context on the device (a window's plans, fetches and replays are a chain of
       // short round trips: ~20 ms of wall time for ~5 ms of kernels, so two windows in flight keep the stage off the critical
-      // path); VSX_SEARCH_CONSUMERS=1 keeps one (A/B, tests).  Windows are independent: a query's hits live in its own slot.
+      // path).  Windows are independent: a query's hits live in its own slot.
       // (r03: three -- a window's align stage is ~12 ms of latency for ~4 ms of kernels while the counting kernels share the device,
       //  and the last window otherwise waits for one of two busy consumers: 147 -> 142 ms per 100 k queries)
-      static const int n_consumers = std::min(3, std::max(1, std::getenv("VSX_SEARCH_CONSUMERS") ? std::atoi(std::getenv("VSX_SEARCH_CONSUMERS")) : 3));
       for (vsx_ctx ** extra : {&S->ctx2, &S->ctx3})
-        {
-          if ((extra == &S->ctx2 && n_consumers < 2) || (extra == &S->ctx3 && n_consumers < 3) || *extra) continue;
-          const int crc = vsx_create(extra, &S->scoring, vsx_internal_device(S->ctx));
-          if (crc != VSX_OK) *extra = nullptr;                     // (no further context: carry on with fewer consumers)
-        }
+        if (!*extra && vsx_create(extra, &S->scoring, vsx_internal_device(S->ctx)) != VSX_OK)
+          *extra = nullptr;                                        // (no further context: carry on with fewer consumers)
       int rc = VSX_OK;
       std::string msg;
       std::mutex rc_mu;
@@ -1649,8 +1640,8 @@ static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, 
       for (vsx_ctx * c : {S->ctx, S->ctx2, S->ctx3})
         if (c) { uint64_t drop[2]; vsx_internal_scratch_requests(c, drop, 1); }      // (requests are counted per call: the levelling below)
       std::thread consumer2, consumer3;
-      if (n_consumers >= 2 && S->ctx2) consumer2 = std::thread(consumer, S->ctx2);
-      if (n_consumers >= 3 && S->ctx3) consumer3 = std::thread(consumer, S->ctx3);
+      if (S->ctx2) consumer2 = std::thread(consumer, S->ctx2);
+      if (S->ctx3) consumer3 = std::thread(consumer, S->ctx3);
       consumer(S->ctx);
       if (consumer2.joinable()) consumer2.join();
       if (consumer3.joinable()) consumer3.join();
@@ -1822,12 +1813,8 @@ static int ap_enumerate(const vsx_searcher * S, int32_t acceptall, const uint32_
   return VSX_OK;
 }
 
-static bool ap_device_decides(const vsx_searcher * S, int32_t acceptall) { return !(acceptall || S->o.gap_infinite || S->o.cluster_unoise); }
-static bool ap_ranked(const vsx_searcher * S, int32_t acceptall)
-{
-  static const bool rank_off = std::getenv("VSX_RANK") && std::strcmp(std::getenv("VSX_RANK"), "host") == 0;     // A/B, tests
-  return ap_device_decides(S, acceptall) && !rank_off;
-}
+// the device decides (and ranks) unless every pair's record is wanted (acceptall) or the host filters (gap_infinite, unoise)
+static bool ap_ranked(const vsx_searcher * S, int32_t acceptall) { return !(acceptall || S->o.gap_infinite || S->o.cluster_unoise); }
 
 // stage B: the block's pairs through the aligner.  Ranked path (vsx_rank.hip): the device filters, orders (id desc, target asc per
 // query: allpairs_hit_compare :116-138) and compacts; only accepted pairs come back.  Otherwise every pair's record, with the verdicts.
@@ -1844,8 +1831,7 @@ static int ap_align(vsx_searcher * S, int32_t acceptall, const ApList & L, ApAli
     }
   else
     {
-      rc = vsx_align_pairs_filtered(S->ctx, S->dbset, S->dbset, L.n_list, L.pq_buf.get(), L.pt_buf.get(),
-                                    ap_device_decides(S, acceptall) ? &flt : nullptr, &A.res);
+      rc = vsx_align_pairs_filtered(S->ctx, S->dbset, S->dbset, L.n_list, L.pq_buf.get(), L.pt_buf.get(), nullptr, &A.res);
       A.have_res = rc == VSX_OK;
     }
   A.t_align = now_s() - t0;
@@ -2174,8 +2160,7 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
       size_t free_b = 0, total_b = 0;
       if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void) hipGetLastError(); free_b = 0; }
       want[0] = std::min<uint64_t>(want[0], (uint64_t) free_b / 4);
-      static const bool no_reserve = std::getenv("VSX_CLUSTER_RESERVE") && std::strcmp(std::getenv("VSX_CLUSTER_RESERVE"), "0") == 0;      // A/B
-      if (want[0] >= (16ull << 20) && !no_reserve) (void) vsx_internal_scratch_reserve(S->ctx, want);
+      if (want[0] >= (16ull << 20)) (void) vsx_internal_scratch_reserve(S->ctx, want);
     }
   IncIndex inc;
   inc.post.assign(nk, {});
@@ -2233,7 +2218,6 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
   int pre_rc = VSX_OK;
   std::string pre_err;
   std::vector<uint32_t> main_list;                       // the centroids the main index stands for (a snapshot; see the helper below)
-  static const bool prefetch_main = !(std::getenv("VSX_CLUSTER_PREFETCH") && std::strcmp(std::getenv("VSX_CLUSTER_PREFETCH"), "0") == 0);
   std::thread pre_thread;
   std::vector<std::vector<uint64_t>> pre_seen;
   auto words_of_round = [&](uint64_t a0, std::vector<std::vector<uint32_t>> & dst, std::vector<std::vector<uint64_t>> & seen, int threads) {
@@ -2312,7 +2296,7 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
           if (s0 + round < n)
             {
               const uint64_t a0 = s0 + round;
-              const bool main_safe = prefetch_main && main_n > 0 && (centroid_list.size() + wn - main_n) <= main_n / 8 + 2 * round;
+              const bool main_safe = main_n > 0 && (centroid_list.size() + wn - main_n) <= main_n / 8 + 2 * round;
               pre_s0 = a0;
               pre_main_s0 = main_safe ? a0 : UINT64_MAX;
               pre_thread = std::thread([&, a0, main_safe]() {
@@ -2406,22 +2390,11 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
       std::vector<uint32_t> sq, stg;
       int near_rc = VSX_OK;
       std::string near_err;
-      // the speculative alignments of the fix-up depend on the counts alone as well: with a second aligner context of the device the
-      // helper aligns them as soon as it has paired them up, beside the staged search (whose stages are chains of short round trips
-      // that leave the device idle most of the time); VSX_CLUSTER_SPEC_OVERLAP=0 / 1 overrides the default below (0: after the search, on
-      // the first context, as in r04)
-#ifndef VSX_CLUSTER_SPEC_OVERLAP_DEFAULT
-#define VSX_CLUSTER_SPEC_OVERLAP_DEFAULT 0
-#endif
+      // (the speculative alignments of the fix-up follow the staged search on the same context: aligned by the helper on a second
+      //  context beside the search they measured level in r05)
       vsx_results spec;
       std::memset(&spec, 0, sizeof spec);
-      struct SpecGuard { vsx_results & r; ~SpecGuard() { vsx_results_free(&r); } } spec_guard {spec};     // (declared before the joiner below:
-                                                                                                          //  freed after the helper has ended)
-      bool spec_done = false;
-      double spec_s = 0;
-      static const bool spec_overlap = VSX_CLUSTER_SPEC_OVERLAP_DEFAULT ? !(std::getenv("VSX_CLUSTER_SPEC_OVERLAP") && std::strcmp(std::getenv("VSX_CLUSTER_SPEC_OVERLAP"), "0") == 0)
-                                                                        : (std::getenv("VSX_CLUSTER_SPEC_OVERLAP") && std::strcmp(std::getenv("VSX_CLUSTER_SPEC_OVERLAP"), "1") == 0);
-      static const bool near_overlap = !(std::getenv("VSX_CLUSTER_NEAR_OVERLAP") && std::strcmp(std::getenv("VSX_CLUSTER_NEAR_OVERLAP"), "0") == 0);   // A/B
+      struct SpecGuard { vsx_results & r; ~SpecGuard() { vsx_results_free(&r); } } spec_guard {spec};
       const bool near_on_device = dev_kmer && fallback.empty();
       auto near_device = [&]() {
         // the same counting problem on the device: members of the round against an index of the round
@@ -2431,7 +2404,7 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
         std::vector<std::vector<Cand>> nc(wn);
         std::vector<uint64_t> none;
         if (near_rc == VSX_OK) near_rc = device_rank(S, rix.get(), &round_list, wn, kmers, 0xffffffffu, 1024, false, nc, none, kacct,
-                                                     (near_on_device && near_overlap) ? std::max(1, S->threads / 2) : 0);      // (beside the staged search: half the budget)
+                                                     std::max(1, S->threads / 2));      // (beside the staged search: half the budget)
         if (near_rc != VSX_OK) { near_err = vsx_last_error(); return; }
         for (uint64_t i = 0; i < wn; ++i)
           for (const Cand & c : nc[i])                              // ascending target
@@ -2447,32 +2420,18 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
                 }
               near[i].push_back(nr);
             }
-        if (spec_overlap && S->ctx2 != nullptr && !sq.empty())
-          {
-            const double ta = now_s();
-            near_rc = vsx_align_pairs(S->ctx2, S->dbset, S->dbset, sq.size(), sq.data(), stg.data(), &spec);
-            spec_s = now_s() - ta;
-            if (near_rc != VSX_OK) { near_err = vsx_last_error(); return; }
-            spec_done = true;
-          }
       };
       std::thread near_thread;
       struct NearJoiner { std::thread & t; ~NearJoiner() { if (t.joinable()) t.join(); } } near_joiner {near_thread};
-      if (near_on_device && near_overlap)
-        {
-          if (spec_overlap && S->ctx2 == nullptr && vsx_create(&S->ctx2, &S->scoring, vsx_internal_device(S->ctx)) != VSX_OK)
-            S->ctx2 = nullptr;                                       // (no second context: the alignments follow the search, as before)
-          near_thread = std::thread(near_device);
-        }
+      if (near_on_device) near_thread = std::thread(near_device);
 
       // ---- phase 1b: staged GPU search (queries and targets both live in the database sequence set) ----
-      // (lazy first batches as in vsx_search_batch are an A/B here, VSX_CLUSTER_LAZY=1: a round's plans are latency-bound, and a
-      //  member whose best centroid fails pays one more stage)
-      static const bool cluster_lazy = std::getenv("VSX_CLUSTER_LAZY") && std::strcmp(std::getenv("VSX_CLUSTER_LAZY"), "1") == 0;
+      // (no lazy first batches as in vsx_search_batch: a round's plans are latency-bound, and a member whose best centroid fails
+      //  pays one more stage -- measured slower in r05)
       const double ts0 = now_s();
       int rc = run_stages(*S, st, [&](uint64_t k) { return seq_of(s0 + k); }, [&](uint64_t k) { return seq_of(s0 + k); },
                           [&](uint64_t k) { return (int64_t) S->len[s0 + k]; },
-                          [&](uint64_t k) { return (uint32_t) (s0 + k); }, [&](uint64_t k) { return S->meta_of(s0 + k); }, S->dbset, acct, nullptr, cluster_lazy);
+                          [&](uint64_t k) { return (uint32_t) (s0 + k); }, [&](uint64_t k) { return S->meta_of(s0 + k); }, S->dbset, acct, nullptr, false);
       if (rc != VSX_OK) return rc;
       tm_stages += now_s() - ts0;
 
@@ -2481,8 +2440,7 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
       t0 = now_s();
       if (near_on_device)
         {
-          if (near_thread.joinable()) near_thread.join();
-          else near_device();
+          near_thread.join();
           if (near_rc != VSX_OK) { vsx_internal_set_error(near_err.c_str()); return near_rc; }
         }
       else
@@ -2514,13 +2472,7 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
       }
       t_kmer += now_s() - t0;
       tm_near += now_s() - t0;
-      if (spec_done)
-        {
-          acct.t_align += spec_s;              // (wall time of the helper's call; it ran beside the search)
-          tm_spec += spec_s;
-          acct.pairs += sq.size();
-        }
-      else if (!sq.empty())
+      if (!sq.empty())
         {
           t0 = now_s();
           rc = vsx_align_pairs(S->ctx, S->dbset, S->dbset, sq.size(), sq.data(), stg.data(), &spec);
@@ -2656,24 +2608,14 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
       // (the round's host state -- 16 384 candidate lists, hit lists, word lists, near lists -- released here so that it shows in the accounting)
       // r06: the round's host state -- 16 384 candidate lists, hit lists, word lists, near lists: ~80 000 heap blocks -- is released on a
       // helper thread beside the next round; on the main thread it was 7.6 ms per round, 0.93 s of a 5.9 s run at 2 M sequences, and in
-      // nobody's accounting (profiles/r06/r06g_cluster_phases.txt).  VSX_CLUSTER_REAPER=0: on this thread (A/B).
+      // nobody's accounting (profiles/r06/r06g_cluster_phases.txt).
       const double tf0 = now_s();
       if (near_thread.joinable()) near_thread.join();
-      static const bool reaper_on = !(std::getenv("VSX_CLUSTER_REAPER") && std::strcmp(std::getenv("VSX_CLUSTER_REAPER"), "0") == 0);
       if (reaper.joinable()) reaper.join();
-      if (reaper_on)
-        {
-          auto * dead_st = new std::vector<QState>(std::move(st));
-          auto * dead_km = new std::vector<std::vector<uint32_t>>(std::move(kmers));
-          auto * dead_near = new std::vector<std::vector<Near>>(std::move(near));
-          reaper = std::thread([dead_st, dead_km, dead_near]() { delete dead_st; delete dead_km; delete dead_near; });
-        }
-      else
-        {
-          std::vector<QState>().swap(st);
-          std::vector<std::vector<uint32_t>>().swap(kmers);
-          std::vector<std::vector<Near>>().swap(near);
-        }
+      auto * dead_st = new std::vector<QState>(std::move(st));
+      auto * dead_km = new std::vector<std::vector<uint32_t>>(std::move(kmers));
+      auto * dead_near = new std::vector<std::vector<Near>>(std::move(near));
+      reaper = std::thread([dead_st, dead_km, dead_near]() { delete dead_st; delete dead_km; delete dead_near; });
       tm_free += now_s() - tf0;
     }
   if (reaper.joinable()) reaper.join();
