@@ -31,6 +31,8 @@ SEARCH_SYMBOLS = ["vsx_search_opts_default", "vsx_searcher_create", "vsx_searche
                   "vsx_multi_search_batch", "vsx_multi_allpairs",
                   "vsx_chimera_opts_default", "vsx_uchime_ref", "vsx_chimera_last_stats",
                   "vsx_chimera_denovo_opts_default", "vsx_uchime_denovo", "vsx_chimera_denovo_last_stats"]
+# include/vsx_merge.h (a list of its own: SYMBOLS stays exactly what include/vsx.h declares; build() checks both)
+MERGE_SYMBOLS = ["vsx_merge_opts_default", "vsx_merge_pairs", "vsx_merge_out_free", "vsx_merge_last_stats"]
 
 
 class Candidates(C.Structure):
@@ -91,6 +93,36 @@ class ChimeraDenovoStats(C.Structure):
                 ("queries_reevaluated", C.c_uint64), ("parts", C.c_uint64), ("pairs_searched", C.c_uint64),
                 ("pairs_aligned", C.c_uint64), ("sentinel_pairs", C.c_uint64), ("queries_kernel", C.c_uint64),
                 ("queries_host", C.c_uint64)]
+
+
+class MergeOpts(C.Structure):
+    """vsx_merge_opts (include/vsx_merge.h): the Parameters fields the merge core reads"""
+    _fields_ = [("fastq_ascii", C.c_int64), ("fastq_qmin", C.c_int64), ("fastq_qmax", C.c_int64), ("fastq_qminout", C.c_int64),
+                ("fastq_qmaxout", C.c_int64), ("fastq_minovlen", C.c_int64), ("fastq_maxdiffs", C.c_int64),
+                ("fastq_maxdiffpct", C.c_double), ("fastq_minmergelen", C.c_int64), ("fastq_maxmergelen", C.c_int64),
+                ("fastq_maxee", C.c_double), ("fastq_truncqual", C.c_int64), ("fastq_maxns", C.c_int64),
+                ("fastq_minlen", C.c_int64), ("fastq_maxlen", C.c_int64), ("fastq_allowmergestagger", C.c_int32),
+                ("pad", C.c_int32), ("window", C.c_int64)]
+
+
+class MergeRecord(C.Structure):
+    """vsx_merge_record (include/vsx_merge.h)"""
+    _fields_ = [("merged", C.c_int32), ("reason", C.c_int32), ("fwd_trunc", C.c_int32), ("rev_trunc", C.c_int32),
+                ("merged_length", C.c_int32), ("overlap_length", C.c_int32), ("fwd_errors", C.c_int32), ("rev_errors", C.c_int32),
+                ("ee_merged", C.c_double), ("ee_fwd", C.c_double), ("ee_rev", C.c_double), ("blob_off", C.c_uint64)]
+
+
+class MergeOut(C.Structure):
+    """vsx_merge_out (include/vsx_merge.h)"""
+    _fields_ = [("n", C.c_uint64), ("rec", C.POINTER(MergeRecord)), ("seq_blob", C.POINTER(C.c_char)),
+                ("qual_blob", C.POINTER(C.c_char)), ("blob_bytes", C.c_uint64)]
+
+
+class MergeStats(C.Structure):
+    """vsx_merge_stats (include/vsx_merge.h)"""
+    _fields_ = [("seconds_stage", C.c_double), ("seconds_kernel", C.c_double), ("seconds_unpack", C.c_double),
+                ("seconds_total", C.c_double), ("pairs", C.c_uint64), ("windows", C.c_uint64), ("diagonals_scored", C.c_uint64),
+                ("pairs_host", C.c_uint64)]
 
 
 class SeqMeta(C.Structure):
@@ -259,6 +291,14 @@ def load():
     lib.vsx_msa_out_free.restype = None
     lib.vsx_lma_align.argtypes = [C.POINTER(Scoring), C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64] + \
         [C.POINTER(C.c_int64)] * 5 + [C.POINTER(vp)]
+    lib.vsx_merge_opts_default.argtypes = [C.POINTER(MergeOpts)]
+    lib.vsx_merge_opts_default.restype = None
+    lib.vsx_merge_pairs.argtypes = [vp, C.POINTER(MergeOpts), C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp,
+                                    C.POINTER(MergeOut)]
+    lib.vsx_merge_out_free.argtypes = [C.POINTER(MergeOut)]
+    lib.vsx_merge_out_free.restype = None
+    lib.vsx_merge_last_stats.argtypes = [C.POINTER(MergeStats)]
+    lib.vsx_merge_last_stats.restype = None
     _lib = lib
     return lib
 
