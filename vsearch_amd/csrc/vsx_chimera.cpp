@@ -16,10 +16,10 @@
 //      chimera_eval_host below, which is also what VSX_CHIMERA=host runs for every query (A/B and the tests' checker).
 #include "../../include/vsx_search.h"
 #include "vsx_internal.h"
+#include "vsx_private.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -27,17 +27,11 @@
 
 #pragma clang fp contract(off)
 
-extern "C" void vsx_internal_set_error(const char * msg);
-extern "C" int vsx_internal_device(const vsx_ctx * ctx);
-extern "C" hipStream_t vsx_internal_stream(const vsx_ctx * ctx);
-extern "C" void vsx_internal_seqset_device(const vsx_seqset * s, const uint8_t ** codes, const uint64_t ** off, const uint32_t ** len, uint64_t * n);
-extern "C" vsx_ctx * vsx_internal_searcher_ctx(const vsx_searcher * S);
-extern "C" const vsx_search_opts * vsx_internal_searcher_opts(const vsx_searcher * S);
-extern "C" const vsx_scoring * vsx_internal_searcher_scoring(const vsx_searcher * S);
-extern "C" const vsx_seqset * vsx_internal_searcher_dbset(const vsx_searcher * S);
-extern "C" int vsx_internal_search_parts(vsx_searcher * S, int64_t tophits, uint64_t nq, const char * qblob, uint64_t qbytes,
-                                         const uint64_t * qoff, const uint32_t * qlen, vsx_hits * out);
-extern "C" void vsx_internal_searcher_text(const vsx_searcher * S, const char ** blob, const uint64_t ** off, const uint32_t ** len);
+using vsxp::fail;
+using vsxp::now_s;
+using vsxp::map4;
+using vsxp::ambiguous4;
+using vsxp::DevBuf;
 
 namespace {
 
@@ -46,25 +40,6 @@ thread_local vsx_chimera_stats g_stats {};
 constexpr int kParts = 4;            // chimera_info->parts for uchime (:302-304)
 constexpr int kWindow = 32;          // `window` (:110)
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-int cfail(int code, const std::string & msg) { vsx_internal_set_error(msg.c_str()); return code; }
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// chrmap_4bit (utils/maps.cpp): the codes the device encoder writes into a sequence set
-uint8_t map4(unsigned char c)
-{
-  switch (c | 0x20)
-    {
-    case 'a': return 1;  case 'b': return 14; case 'c': return 2;  case 'd': return 13;
-    case 'g': return 4;  case 'h': return 11; case 'k': return 12; case 'm': return 3;
-    case 'n': return 15; case 'r': return 5;  case 's': return 6;  case 't': return 8;
-    case 'u': return 8;  case 'v': return 7;  case 'w': return 9;  case 'y': return 10;
-    default: return 0;
-    }
-}
-
-bool ambiguous4(uint8_t c) { return c != 1 && c != 2 && c != 4 && c != 8; }     // chrmap_ambiguous_4bit
 
 void unscored(vsx_chimera_result * r, int status, uint32_t pa, uint32_t pb)
 {
@@ -306,27 +281,12 @@ void vsx_internal_chimera_eval_host(const uint8_t * q, int L, int nc, const uint
 
 namespace {
 
-// device buffers of one call, grown as windows need them (a hipFree synchronises the whole device)
-template <class T>
-struct GrowBuf {
-  T * p = nullptr;
-  size_t cap = 0;
-  ~GrowBuf() { if (p) (void) hipFree(p); }
-  hipError_t reserve(size_t n)
-  {
-    if (n <= cap) return hipSuccess;
-    if (p) { const hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
-    n = std::max<size_t>(n, cap * 3 / 2 + 1);
-    const hipError_t e = hipMalloc(&p, n * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-};
+// device buffers of one call, replaced when a window needs more (a hipFree synchronises the whole device)
 struct CallBufs {
-  GrowBuf<VsxPairOut> hits;
-  GrowBuf<uint32_t> runs;
-  GrowBuf<VsxChimItem> items;
-  GrowBuf<vsx_chimera_result> out;
+  DevBuf<VsxPairOut> hits;
+  DevBuf<uint32_t> runs;
+  DevBuf<VsxChimItem> items;
+  DevBuf<vsx_chimera_result> out;
 };
 
 // one query of steps 4-5: its index in the query set of the plan, its text, its candidate parents and where its record goes
@@ -339,8 +299,6 @@ struct EvalJob {
   vsx_chimera_result * out;
 };
 struct EvalAcct { double t_align = 0, t_eval = 0; uint64_t pairs = 0, sentinels = 0, kernel = 0, host = 0; };
-
-#define CHIP(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return cfail(VSX_EHIP, std::string(who) + ": " + hipGetErrorString(e_)); } while (0)
 
 // 4. whole queries against their candidates: one plan of (job.q in qset, candidate in the database set) pairs; 5. selection + scoring
 // on the kernel, or on the host restatement (long query, sentinel pair, host_all).  A job with < 2 candidates, or shorter than the
@@ -374,9 +332,9 @@ int align_and_eval(vsx_searcher * S, const VsxChimParams & P, CallBufs & B, bool
   if (rc == VSX_OK) rc = vsx_plan_sync(g.p, nullptr);
   if (rc != VSX_OK) return rc;
   const uint64_t npairs = qidx.size();
-  CHIP(hipSetDevice(vsx_internal_device(ctx)));
-  GrowBuf<VsxPairOut> & d_hits = B.hits;
-  CHIP(d_hits.reserve(npairs));
+  VSX_HIP_AS(who, hipSetDevice(vsx_internal_device(ctx)));
+  DevBuf<VsxPairOut> & d_hits = B.hits;
+  VSX_HIP_AS(who, d_hits.ensure(npairs));
   rc = vsx_plan_export_hits(g.p, d_hits.p, npairs * sizeof(VsxPairOut));
   if (rc != VSX_OK) return rc;
   uint64_t nruns = 0;
@@ -391,11 +349,11 @@ int align_and_eval(vsx_searcher * S, const VsxChimParams & P, CallBufs & B, bool
       if (rc == VSX_OK) rc = vsx_plan_export_runs(g.p, nullptr, 0, &nruns);
       if (rc != VSX_OK) return rc;
     }
-  GrowBuf<uint32_t> & d_runs = B.runs;
-  CHIP(d_runs.reserve(std::max<uint64_t>(nruns, 1)));
+  DevBuf<uint32_t> & d_runs = B.runs;
+  VSX_HIP_AS(who, d_runs.ensure(std::max<uint64_t>(nruns, 1)));
   if (nruns) { rc = vsx_plan_export_runs(g.p, d_runs.p, nruns * 4, &nruns); if (rc != VSX_OK) return rc; }
   std::vector<VsxPairOut> h_hits(npairs);
-  CHIP(hipMemcpy(h_hits.data(), d_hits.p, npairs * sizeof(VsxPairOut), hipMemcpyDeviceToHost));
+  VSX_HIP_AS(who, hipMemcpy(h_hits.data(), d_hits.p, npairs * sizeof(VsxPairOut), hipMemcpyDeviceToHost));
   const double t2 = now_s();
   A.t_align += t2 - t1;
   A.pairs += npairs;
@@ -404,7 +362,7 @@ int align_and_eval(vsx_searcher * S, const VsxChimParams & P, CallBufs & B, bool
   // fails the call the same way whichever route a query takes (the kernel's own bound check only keeps it inside the buffer)
   for (uint64_t p = 0; p < npairs; ++p)
     if (h_hits[p].score != VSX_SCORE_SENTINEL && h_hits[p].run_off + h_hits[p].nruns > nruns)
-      return cfail(VSX_EHIP, std::string(who) + ": run words out of range");
+      return fail(VSX_EHIP, "%s: run words out of range", who);
 
   // 5. route: kernel, or host restatement (long query, sentinel pair, VSX_CHIMERA=host)
   std::vector<VsxChimItem> items;
@@ -435,22 +393,22 @@ int align_and_eval(vsx_searcher * S, const VsxChimParams & P, CallBufs & B, bool
       vsx_internal_seqset_device(qset, &qc, &qo, &ql, &dummy);
       vsx_internal_seqset_device(dbset, &tc, &to, &tl, &dummy);
       hipStream_t st = vsx_internal_stream(ctx);
-      GrowBuf<VsxChimItem> & d_items = B.items;
-      GrowBuf<vsx_chimera_result> & d_out = B.out;
-      CHIP(d_items.reserve(items.size()));
-      CHIP(d_out.reserve(items.size()));
-      CHIP(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(VsxChimItem), hipMemcpyHostToDevice, st));
-      CHIP(vsx_launch_chimera_eval(d_items.p, (uint32_t) items.size(), qc, qo, ql, tc, to, tl, d_hits.p, d_runs.p, nruns, P, d_out.p, st));
+      DevBuf<VsxChimItem> & d_items = B.items;
+      DevBuf<vsx_chimera_result> & d_out = B.out;
+      VSX_HIP_AS(who, d_items.ensure(items.size()));
+      VSX_HIP_AS(who, d_out.ensure(items.size()));
+      VSX_HIP_AS(who, hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(VsxChimItem), hipMemcpyHostToDevice, st));
+      VSX_HIP_AS(who, vsx_launch_chimera_eval(d_items.p, (uint32_t) items.size(), qc, qo, ql, tc, to, tl, d_hits.p, d_runs.p, nruns, P, d_out.p, st));
       std::vector<vsx_chimera_result> res(items.size());
-      CHIP(hipMemcpyAsync(res.data(), d_out.p, res.size() * sizeof(vsx_chimera_result), hipMemcpyDeviceToHost, st));
-      CHIP(hipStreamSynchronize(st));
+      VSX_HIP_AS(who, hipMemcpyAsync(res.data(), d_out.p, res.size() * sizeof(vsx_chimera_result), hipMemcpyDeviceToHost, st));
+      VSX_HIP_AS(who, hipStreamSynchronize(st));
       for (size_t x = 0; x < items.size(); ++x) *jobs[item_job[x]].out = res[items[x].out];
       A.kernel += items.size();
     }
   if (!host_q.empty())
     {
       std::vector<uint32_t> h_runs(nruns);
-      if (nruns) CHIP(hipMemcpy(h_runs.data(), d_runs.p, nruns * 4, hipMemcpyDeviceToHost));
+      if (nruns) VSX_HIP_AS(who, hipMemcpy(h_runs.data(), d_runs.p, nruns * 4, hipMemcpyDeviceToHost));
       const vsx_scoring * sc = vsx_internal_searcher_scoring(S);
       std::vector<uint8_t> qcode;
       std::vector<std::vector<uint8_t>> tcode;
@@ -584,18 +542,6 @@ int run_window(vsx_searcher * S, const vsx_chimera_opts & O, CallBufs & B, bool 
 }
 
 }  // namespace
-
-// the de novo part search in vsx_search.cpp (searcher internals)
-struct VsxDenovo;
-int vsx_internal_denovo_create(vsx_searcher * S, VsxDenovo ** out);
-void vsx_internal_denovo_destroy(VsxDenovo * D);
-int vsx_internal_denovo_window(VsxDenovo * D, uint64_t s0, uint64_t wn, const std::vector<uint64_t> & poff, const std::vector<uint32_t> & plen,
-                               const std::vector<uint32_t> & pmember, double * t_rank, double * t_members);
-void vsx_internal_denovo_merge(VsxDenovo * D, uint64_t p, const uint8_t * present, std::vector<uint32_t> & targets);
-int vsx_internal_denovo_search(VsxDenovo * D, const std::vector<uint32_t> & parts, std::vector<std::vector<uint32_t>> & accepted,
-                               uint64_t * pairs, uint64_t * sentinels);
-void vsx_internal_denovo_commit(VsxDenovo * D, const std::vector<uint32_t> & seqnos);
-bool vsx_internal_searcher_has_abundances(const vsx_searcher * S);
 
 namespace {
 
@@ -751,14 +697,14 @@ int vsx_uchime_ref(vsx_searcher * S, const vsx_chimera_opts * O, uint64_t n, con
 {
   g_stats = vsx_chimera_stats {};
   const double t0 = now_s();
-  if (!S || !O || (n && (!qblob || !qoff || !qlen || !out))) return cfail(VSX_EINVAL, "vsx_uchime_ref: null argument");
+  if (!S || !O || (n && (!qblob || !qoff || !qlen || !out))) return fail(VSX_EINVAL, "vsx_uchime_ref: null argument");
   const vsx_search_opts & so = *vsx_internal_searcher_opts(S);
   if (so.id != 0.55 || so.weak_id != 0.55 || so.maxaccepts != 4 || so.maxrejects != 16 || so.strand_both || so.cluster_unoise || so.self)
-    return cfail(VSX_EINVAL, "vsx_uchime_ref: the searcher was not created with the detection parameters (vsx_chimera_opts_default: "
+    return fail(VSX_EINVAL, "vsx_uchime_ref: the searcher was not created with the detection parameters (vsx_chimera_opts_default: "
                              "id = weak_id = 0.55, maxaccepts 4, maxrejects 16, plus strand)");
-  if (O->mindiffs < 0 || !(O->xn > 0.0) || !(O->dn >= 0.0)) return cfail(VSX_EINVAL, "vsx_uchime_ref: xn must be > 0, dn >= 0, mindiffs >= 0");
+  if (O->mindiffs < 0 || !(O->xn > 0.0) || !(O->dn >= 0.0)) return fail(VSX_EINVAL, "vsx_uchime_ref: xn must be > 0, dn >= 0, mindiffs >= 0");
   for (uint64_t k = 0; k < n; ++k)
-    if (qoff[k] + qlen[k] > qbytes) return cfail(VSX_EINVAL, "vsx_uchime_ref: query exceeds the blob");
+    if (qoff[k] + qlen[k] > qbytes) return fail(VSX_EINVAL, "vsx_uchime_ref: query exceeds the blob");
   const char * env = std::getenv("VSX_CHIMERA");
   const bool host_all = env && std::strcmp(env, "host") == 0;
   const uint64_t window = O->window > 0 ? (uint64_t) O->window : 16384;
@@ -790,20 +736,20 @@ int vsx_uchime_denovo(vsx_searcher * S, const vsx_chimera_denovo_opts * O, vsx_c
 {
   g_dstats = vsx_chimera_denovo_stats {};
   const double t0 = now_s();
-  if (!O) return cfail(VSX_EINVAL, "vsx_uchime_denovo: null options");
-  if (O->variant < 1 || O->variant > 3) return cfail(VSX_EINVAL, "vsx_uchime_denovo: variant must be 1 (uchime), 2 (uchime2) or 3 (uchime3)");
-  if (!(O->abskew >= 1.0)) return cfail(VSX_EINVAL, "vsx_uchime_denovo: abskew must be >= 1.0");
+  if (!O) return fail(VSX_EINVAL, "vsx_uchime_denovo: null options");
+  if (O->variant < 1 || O->variant > 3) return fail(VSX_EINVAL, "vsx_uchime_denovo: variant must be 1 (uchime), 2 (uchime2) or 3 (uchime3)");
+  if (!(O->abskew >= 1.0)) return fail(VSX_EINVAL, "vsx_uchime_denovo: abskew must be >= 1.0");
   if (O->base.mindiffs < 0 || !(O->base.xn > 0.0) || !(O->base.dn >= 0.0))
-    return cfail(VSX_EINVAL, "vsx_uchime_denovo: xn must be > 0, dn >= 0, mindiffs >= 0");
-  if (!S || !out) return cfail(VSX_EINVAL, "vsx_uchime_denovo: null argument");
+    return fail(VSX_EINVAL, "vsx_uchime_denovo: xn must be > 0, dn >= 0, mindiffs >= 0");
+  if (!S || !out) return fail(VSX_EINVAL, "vsx_uchime_denovo: null argument");
   const vsx_search_opts & so = *vsx_internal_searcher_opts(S);
-  if (so.strand_both) return cfail(VSX_EINVAL, "vsx_uchime_denovo: --strand both is not provided (the reference refuses it)");
+  if (so.strand_both) return fail(VSX_EINVAL, "vsx_uchime_denovo: --strand both is not provided (the reference refuses it)");
   if (so.id != 0.55 || so.weak_id != 0.55 || so.maxaccepts != 4 || so.maxrejects != 16 || so.cluster_unoise || so.self != 1 ||
       so.selfid != 1 || so.maxsizeratio != 1.0 / O->abskew || (so.qmask != 0 && so.qmask != so.soft_mask + 1))
-    return cfail(VSX_EINVAL, "vsx_uchime_denovo: the searcher was not created with the detection parameters (vsx_chimera_denovo_opts_default: "
+    return fail(VSX_EINVAL, "vsx_uchime_denovo: the searcher was not created with the detection parameters (vsx_chimera_denovo_opts_default: "
                              "id = weak_id = 0.55, maxaccepts 4, maxrejects 16, self = selfid = 1, maxsizeratio = 1 / abskew, qmask as soft_mask)");
-  if (!vsx_internal_searcher_has_abundances(S)) return cfail(VSX_EINVAL, "vsx_uchime_denovo: the searcher has no abundances (vsx_searcher_set_meta)");
-  if (so.wordlength > 8) return cfail(VSX_EINVAL, "vsx_uchime_denovo: word lengths above 8 are not provided");
+  if (!vsx_internal_searcher_has_abundances(S)) return fail(VSX_EINVAL, "vsx_uchime_denovo: the searcher has no abundances (vsx_searcher_set_meta)");
+  if (so.wordlength > 8) return fail(VSX_EINVAL, "vsx_uchime_denovo: word lengths above 8 are not provided");
   const char * text;
   const uint64_t * off;
   const uint32_t * len;

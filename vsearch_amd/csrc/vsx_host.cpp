@@ -9,21 +9,11 @@
 // and turns run lists into CIGAR text.
 #include "../../include/vsx.h"
 #include "vsx_internal.h"
+#include "vsx_private.h"
 
 #include <hip/hip_runtime.h>
-#include <cstdlib>
-// VSX_POISON=1 (debugging aid, r04): every device block this library hands out is filled with 0xA5 first, so a read of memory nobody
-// has written gives the same junk in every run instead of whatever an earlier plan, index or process left there
-extern "C" uint64_t vsx_internal_memory_pressure(int device);
-extern "C" void vsx_internal_poison(void * p, size_t bytes)
-{
-  static const bool on = std::getenv("VSX_POISON") != nullptr;
-  if (on && p && bytes) { (void) hipMemset(p, 0xA5, bytes); (void) hipDeviceSynchronize(); }
-}
-
 #include <algorithm>
 #include <cinttypes>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,28 +30,12 @@ extern "C" void vsx_internal_poison(void * p, size_t bytes)
 #include <string>
 #include <vector>
 
+using vsxp::fail;
+using vsxp::DevBuf;
+
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const char * fmt, ...)
-{
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIPCHK(call)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return fail(e_ == hipErrorOutOfMemory ? VSX_ENOMEM : VSX_EHIP, "%s failed: %s (%s:%d)", \
-                  #call, hipGetErrorString(e_), __FILE__, __LINE__);                        \
-  } while (0)
 
 inline int sat16(int x) { return x > 32767 ? 32767 : (x < -32768 ? -32768 : x); }
 
@@ -69,24 +43,6 @@ inline bool fits(int64_t q, int64_t d)      // search16_fits, core/align_simd.cp
 {
   return (q + d <= VSX_MAX_SEQLEN_SUM) && (q * d <= VSX_MAX_SEQLEN_PRODUCT);
 }
-
-template <typename T>
-struct DevBuf {
-  T * p = nullptr;
-  size_t n = 0;
-  ~DevBuf() { release(); }
-  void release() { if (p) { (void) hipFree(p); p = nullptr; n = 0; } }
-  hipError_t alloc(size_t count)
-  {
-    release();
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T));
-    if (e == hipSuccess) { n = count; vsx_internal_poison(p, count * sizeof(T)); }
-    return e;
-  }
-  hipError_t ensure(size_t count) { return (count <= n && p) ? hipSuccess : alloc(count); }
-};
-
 
 // Scratch pool: hipMalloc/hipFree of the multi-GB checkpoint, slab and run buffers cost seconds per plan (page-table
 // set-up), far more than the kernels of a 500 k-pair stage.  A context keeps the blocks its finished plans give back and
@@ -125,7 +81,7 @@ struct ScratchPool {
         // multi-GB blocks (seconds apiece) and the warm-call promise of the pools would vanish silently.
         size_t free_b = 0, total_b = 0;
         int dev = 0;
-        const size_t need = bytes + ((size_t) 6 << 30);
+        const size_t need = bytes + VSX_DEVICE_RESERVE_BYTES;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < need && hipGetDevice(&dev) == hipSuccess)
           {
             static std::atomic<bool> said {false};
@@ -136,15 +92,8 @@ struct ScratchPool {
           }
         (void) hipGetLastError();
       }
-    hipError_t e = hipMalloc(out, bytes);
-    if (e == hipErrorOutOfMemory) { trim(); (void) hipGetLastError(); e = hipMalloc(out, bytes); }
-    if (e == hipErrorOutOfMemory)
-      {
-        // r05: the idle blocks of the OTHER contexts of this device (a searcher's consumers, a context that ran one huge plan earlier)
-        int dev = 0;
-        (void) hipGetLastError();
-        if (hipGetDevice(&dev) == hipSuccess && vsx_internal_memory_pressure(dev) > 0) e = hipMalloc(out, bytes);
-      }
+    // (an out-of-memory answer makes every context of the device, this pool's own included, free what is idle, and is asked again)
+    const hipError_t e = vsxp::device_malloc(out, bytes);
     if (e == hipSuccess) { *got = bytes; vsx_internal_poison(*out, std::min<size_t>(bytes, (size_t) 256 << 20)); }
     return e;
   }
@@ -360,7 +309,6 @@ struct Chunk {
 
 }  // namespace
 
-extern "C" int vsx_internal_usable_cpus(void);
 // per device: 0 = not tested yet, 1 = v_pk_maximum3_f16 is the integer maximum on [0, 0x7BFF] (vsx_create's self-test), 2 = it is not
 // r05j same-box A/B, 25 000 queries x 32 candidates, two runs each (profiles/r05/r05j_pairprof_first_contact.txt): DP 400 x 400 16.53 -> 14.45 ms,
 // 300 x 300 9.96 -> 8.68, 250 x 1000 22.12 -> 20.39, 150 x 1000 16.04 -> 14.50.  Default ON (it engages only where a query has >= 4 eligible tasks)
@@ -529,6 +477,11 @@ struct vsx_plan {
 
 extern "C" {
 
+void vsx_internal_poison(void * p, size_t bytes)
+{
+  static const bool on = std::getenv("VSX_POISON") != nullptr;
+  if (on && p && bytes) { (void) hipMemset(p, 0xA5, bytes); (void) hipDeviceSynchronize(); }
+}
 // the host worker pool for vsx_search.cpp (fn(0) runs on the caller, which also helps with queued jobs while it waits)
 void vsx_internal_run_threads(int nth, void (*fn)(int, void *), void * arg) { run_threads(nth, [&](int t) { fn(t, arg); }); }
 // shared with vsx_search.cpp: one thread-local error slot for the whole library
@@ -672,10 +625,10 @@ int vsx_create(vsx_ctx ** out, const vsx_scoring * s, int device)
     }
   if (device < 0 || device >= ndev) return fail(VSX_EINVAL, "vsx_create: device %d out of range (0..%d)", device, ndev - 1);
   hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, device));
+  VSX_HIP(hipGetDeviceProperties(&prop, device));
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(VSX_ENODEVICE, "vsx_create: device %d is %s, libvsx is built for gfx950 only", device, prop.gcnArchName);
-  HIPCHK(hipSetDevice(device));
+  VSX_HIP(hipSetDevice(device));
 
   auto * c = new vsx_ctx;
   c->device = device;
@@ -879,7 +832,7 @@ static int seqset_common(vsx_ctx * ctx, vsx_seqset ** out, uint64_t n, const voi
   for (uint64_t i = 0; i < n; ++i)
     if (offsets[i] + lengths[i] > blob_bytes)
       return fail(VSX_EINVAL, "vsx_seqset_create: sequence %" PRIu64 " exceeds the blob", i);
-  HIPCHK(hipSetDevice(ctx->device));
+  VSX_HIP(hipSetDevice(ctx->device));
   auto * s = new vsx_seqset;
   s->ctx = ctx;
   s->device = ctx->device;
@@ -964,8 +917,8 @@ const uint8_t * vsx_internal_seqset_lower(const vsx_seqset * s) { return s ? s->
 int vsx_internal_seqset_lower_download(const vsx_seqset * s, uint8_t * dst, uint64_t nbytes)
 {
   if (!s || !s->d_lower.p || nbytes > s->lower_bytes) return fail(VSX_EINVAL, "vsx_internal_seqset_lower_download: no case bitmap of that size");
-  HIPCHK(hipSetDevice(s->device));
-  if (nbytes) HIPCHK(hipMemcpy(dst, s->d_lower.p, nbytes, hipMemcpyDeviceToHost));
+  VSX_HIP(hipSetDevice(s->device));
+  if (nbytes) VSX_HIP(hipMemcpy(dst, s->d_lower.p, nbytes, hipMemcpyDeviceToHost));
   return VSX_OK;
 }
 
@@ -1001,15 +954,15 @@ static int ensure_impure(const vsx_seqset * s)
   std::lock_guard<std::mutex> lk(s->impure_mu);
   if (s->have_impure) return VSX_OK;
   vsx_ctx * ctx = s->ctx;
-  HIPCHK(hipSetDevice(ctx->device));
+  VSX_HIP(hipSetDevice(ctx->device));
   // (r06, ADVICE r05: the flags come from the scratch pool -- hipMalloc / hipFree synchronise the WHOLE device, and a search's plans are
   //  made while the counting kernel of the next window runs: 15-42 ms per window, profiles/r06/r06a_search_timeline.txt)
   PoolBuf<uint8_t> d_flags;
-  HIPCHK(d_flags.alloc(s->pool_ref ? s->pool_ref.get() : nullptr, s->n));
-  HIPCHK(vsx_launch_purity(s->codes(), s->d_off.p, s->d_len.p, s->n, d_flags.p, ctx->stream));
+  VSX_HIP(d_flags.alloc(s->pool_ref ? s->pool_ref.get() : nullptr, s->n));
+  VSX_HIP(vsx_launch_purity(s->codes(), s->d_off.p, s->d_len.p, s->n, d_flags.p, ctx->stream));
   s->impure.assign(s->n, 0);
-  if (s->n) HIPCHK(hipMemcpyAsync(s->impure.data(), d_flags.p, s->n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (s->n) VSX_HIP(hipMemcpyAsync(s->impure.data(), d_flags.p, s->n, hipMemcpyDeviceToHost, ctx->stream));
+  VSX_HIP(hipStreamSynchronize(ctx->stream));
   s->have_impure = true;
   return VSX_OK;
 }
@@ -1102,7 +1055,7 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
       if (bad[(size_t) t] != UINT64_MAX)
         return fail(VSX_EINVAL, "vsx_plan_create: pair %" PRIu64 " references a sequence out of range", bad[(size_t) t]);
   }
-  HIPCHK(hipSetDevice(ctx->device));
+  VSX_HIP(hipSetDevice(ctx->device));
   // r05, pair-profile classes (vsx_forward_kernel PAIR): groups of four whole-wave tasks of ONE pure-ACGT query with pure-ACGT targets
   // run as a workgroup that shares a pair-indexed dword profile (5 instead of 6 instructions per lane-row).  Worth it only for queries
   // with many targets (--allpairs_global); needs the purity of both sets.  VSX_PAIRPROF=0 / 1 overrides the default below
@@ -1386,7 +1339,7 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
     {
       size_t free_b = 0, total_b = 0;
       const double tb0 = now();
-      HIPCHK(hipMemGetInfo(&free_b, &total_b));
+      VSX_HIP(hipMemGetInfo(&free_b, &total_b));
       t_budget = now() - tb0;
       free_b += ctx->pool.idle_bytes() + ctx->shared_dir[pl->dir_slot].bytes();   // blocks this context can hand straight back / already holds
       dir_budget_bytes = std::min<uint64_t>((uint64_t) (free_b * 0.4), 128ull << 30);
@@ -1546,13 +1499,13 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
     }
   const size_t ngp = pl->pair_ids.size();
   pl->runs_capacity = std::min<uint64_t>(worst_runs, std::max<uint64_t>(16ull << 20, 48ull * ngp)) + 1;
-  HIPCHK(pl->d_tasks.alloc(&ctx->pool, pl->tasks.size()));
-  HIPCHK(pl->d_pair_slot.alloc(&ctx->pool, ngp));
-  HIPCHK(pl->d_pair_ids.alloc(&ctx->pool, ngp));
-  HIPCHK(pl->d_slab_off.alloc(&ctx->pool, ngp));
-  HIPCHK(pl->d_slot.alloc(&ctx->pool, pl->tasks.size() * VSX_TASK_SLOTS));
-  HIPCHK(pl->d_out.alloc(&ctx->pool, n_pairs));
-  HIPCHK(pl->d_cursor.alloc(&ctx->pool, 2));
+  VSX_HIP(pl->d_tasks.alloc(&ctx->pool, pl->tasks.size()));
+  VSX_HIP(pl->d_pair_slot.alloc(&ctx->pool, ngp));
+  VSX_HIP(pl->d_pair_ids.alloc(&ctx->pool, ngp));
+  VSX_HIP(pl->d_slab_off.alloc(&ctx->pool, ngp));
+  VSX_HIP(pl->d_slot.alloc(&ctx->pool, pl->tasks.size() * VSX_TASK_SLOTS));
+  VSX_HIP(pl->d_out.alloc(&ctx->pool, n_pairs));
+  VSX_HIP(pl->d_cursor.alloc(&ctx->pool, 2));
   {
     // output arrays, 16-byte aligned sections of one block: score, aligned, matches, mismatches, gaps (2 B), verdict (1 B), text offset (8 B)
     const uint64_t np = std::max<uint64_t>(n_pairs, 1);
@@ -1560,7 +1513,7 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
     uint64_t at = 0;
     for (int x = 0; x < 7; ++x) { pl->soa_off[x] = at; at += (np * width[x] + 15) & ~15ull; }
     pl->soa_bytes = at;
-    HIPCHK(pl->d_soa.alloc(&ctx->pool, at));
+    VSX_HIP(pl->d_soa.alloc(&ctx->pool, at));
     uint8_t * b = pl->d_soa.p;
     pl->soa.score = reinterpret_cast<int16_t *>(b + pl->soa_off[0]);
     pl->soa.aligned = reinterpret_cast<uint16_t *>(b + pl->soa_off[1]);
@@ -1574,7 +1527,7 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
     std::lock_guard<std::mutex> lk(ctx->stage_mu);
     if (!ctx->cursor_slots.empty()) { pl->h_cursor = ctx->cursor_slots.back(); ctx->cursor_slots.pop_back(); }
   }
-  if (!pl->h_cursor) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&pl->h_cursor), 64, hipHostMallocDefault));
+  if (!pl->h_cursor) VSX_HIP(hipHostMalloc(reinterpret_cast<void **>(&pl->h_cursor), 64, hipHostMallocDefault));
   // one checkpoint buffer, reused chunk after chunk: overlapping chunk k's traceback with chunk k+1's DP bought nothing
   // (both are issue-bound), while a second buffer doubled a multi-second hipMalloc
   for (int k = 0; k < 2; ++k)
@@ -1583,31 +1536,31 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
       uint64_t seen = ctx->req_hwm[k].load();
       while (need > seen && !ctx->req_hwm[k].compare_exchange_weak(seen, need)) { }
     }
-  HIPCHK(pl->d_dir[0].alloc(ctx->shared_dir[pl->dir_slot], &ctx->pool, max_dir));
-  HIPCHK(pl->d_strip.alloc(&ctx->pool, max_strip));
-  HIPCHK(pl->d_slab.alloc(ctx->shared_slab, &ctx->pool, max_slab));
-  HIPCHK(pl->d_runs.alloc(&ctx->pool, pl->runs_capacity));
+  VSX_HIP(pl->d_dir[0].alloc(ctx->shared_dir[pl->dir_slot], &ctx->pool, max_dir));
+  VSX_HIP(pl->d_strip.alloc(&ctx->pool, max_strip));
+  VSX_HIP(pl->d_slab.alloc(ctx->shared_slab, &ctx->pool, max_slab));
+  VSX_HIP(pl->d_runs.alloc(&ctx->pool, pl->runs_capacity));
   // text: <= 6 bytes per run (5 digits + op) + NUL + padding per pair in the worst case; typical alignments need ~2 per run
   pl->text_capacity = std::min<uint64_t>(6 * worst_runs + 8 * (uint64_t) ngp, std::max<uint64_t>(32ull << 20, 128ull * ngp)) + 16;
-  HIPCHK(pl->d_text.alloc(&ctx->pool, pl->text_capacity));
+  VSX_HIP(pl->d_text.alloc(&ctx->pool, pl->text_capacity));
   if (!pl->tasks.empty())
-    HIPCHK(hipMemcpyAsync(pl->d_tasks.p, pl->tasks.data(), pl->tasks.size() * sizeof(VsxTask), hipMemcpyHostToDevice, ctx->stream_up));
+    VSX_HIP(hipMemcpyAsync(pl->d_tasks.p, pl->tasks.data(), pl->tasks.size() * sizeof(VsxTask), hipMemcpyHostToDevice, ctx->stream_up));
   if (ngp)
     {
-      HIPCHK(hipMemcpyAsync(pl->d_pair_slot.p, pl->pair_slot.data(), ngp * 4, hipMemcpyHostToDevice, ctx->stream_up));
-      HIPCHK(hipMemcpyAsync(pl->d_pair_ids.p, pl->pair_ids.data(), ngp * 4, hipMemcpyHostToDevice, ctx->stream_up));
-      HIPCHK(hipMemcpyAsync(pl->d_slab_off.p, pl->slab_off.data(), ngp * 8, hipMemcpyHostToDevice, ctx->stream_up));
+      VSX_HIP(hipMemcpyAsync(pl->d_pair_slot.p, pl->pair_slot.data(), ngp * 4, hipMemcpyHostToDevice, ctx->stream_up));
+      VSX_HIP(hipMemcpyAsync(pl->d_pair_ids.p, pl->pair_ids.data(), ngp * 4, hipMemcpyHostToDevice, ctx->stream_up));
+      VSX_HIP(hipMemcpyAsync(pl->d_slab_off.p, pl->slab_off.data(), ngp * 8, hipMemcpyHostToDevice, ctx->stream_up));
     }
-  HIPCHK(hipEventCreate(&pl->ev_begin));
-  HIPCHK(hipEventCreate(&pl->ev_end));
+  VSX_HIP(hipEventCreate(&pl->ev_begin));
+  VSX_HIP(hipEventCreate(&pl->ev_end));
   for (Chunk & c : pl->chunks)
     {
-      HIPCHK(hipEventCreate(&c.e0));
-      HIPCHK(hipEventCreate(&c.e1));
-      HIPCHK(hipEventCreate(&c.e1b));
-      HIPCHK(hipEventCreate(&c.e2));
+      VSX_HIP(hipEventCreate(&c.e0));
+      VSX_HIP(hipEventCreate(&c.e1));
+      VSX_HIP(hipEventCreate(&c.e1b));
+      VSX_HIP(hipEventCreate(&c.e2));
     }
-  HIPCHK(hipStreamSynchronize(ctx->stream_up));
+  VSX_HIP(hipStreamSynchronize(ctx->stream_up));
   if (timing)
     std::fprintf(stderr, "vsx_plan_create: %llu pairs, %zu tasks: classify %.2f ms, group %.2f ms (budget query %.2f), tasks %.2f ms, device buffers + upload %.2f ms\n",
                  (unsigned long long) n_pairs, pl->tasks.size(), (tc1 - tc0) * 1e3, (tc2 - tc1) * 1e3, t_budget * 1e3, (tc3 - tc2) * 1e3, (now() - tc3) * 1e3);
@@ -1635,11 +1588,11 @@ static int plan_set_ranked(vsx_plan * pl)
   if (!pl->filter.enabled) return VSX_OK;
   vsx_ctx * ctx = pl->ctx;
   const size_t n = (size_t) pl->n_pairs;
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(pl->d_rank_counts.alloc(&ctx->pool, 2));
-  HIPCHK(pl->d_kept_pair.alloc(&ctx->pool, n + 1));
-  HIPCHK(pl->d_kept_id.alloc(&ctx->pool, n + 1));
-  HIPCHK(pl->d_refused_pair.alloc(&ctx->pool, n + 1));
+  VSX_HIP(hipSetDevice(ctx->device));
+  VSX_HIP(pl->d_rank_counts.alloc(&ctx->pool, 2));
+  VSX_HIP(pl->d_kept_pair.alloc(&ctx->pool, n + 1));
+  VSX_HIP(pl->d_kept_id.alloc(&ctx->pool, n + 1));
+  VSX_HIP(pl->d_refused_pair.alloc(&ctx->pool, n + 1));
   pl->filter.rank_counts = pl->d_rank_counts.p;
   pl->filter.kept_pair = pl->d_kept_pair.p;
   pl->filter.kept_id = pl->d_kept_id.p;
@@ -1651,33 +1604,33 @@ int vsx_plan_run(vsx_plan * pl)
 {
   if (!pl) return fail(VSX_EINVAL, "vsx_plan_run: null plan");
   vsx_ctx * ctx = pl->ctx;
-  HIPCHK(hipSetDevice(ctx->device));
+  VSX_HIP(hipSetDevice(ctx->device));
   hipStream_t st = pl->alt_fwd ? ctx->stream_b : ctx->stream, st2 = ctx->stream2;
   const int slot = pl->dir_slot;
-  HIPCHK(hipMemsetAsync(pl->d_cursor.p, 0, 2 * sizeof(unsigned long long), st));
-  if (pl->filter.rank_counts) HIPCHK(hipMemsetAsync(pl->d_rank_counts.p, 0, 2 * sizeof(uint32_t), st));      // (every run: settle() may run a plan twice)
-  HIPCHK(hipEventRecord(pl->ev_begin, st));
+  VSX_HIP(hipMemsetAsync(pl->d_cursor.p, 0, 2 * sizeof(unsigned long long), st));
+  if (pl->filter.rank_counts) VSX_HIP(hipMemsetAsync(pl->d_rank_counts.p, 0, 2 * sizeof(uint32_t), st));      // (every run: settle() may run a plan twice)
+  VSX_HIP(hipEventRecord(pl->ev_begin, st));
   // DP kernels on `st`, tracebacks + text on `st2`.  A plan's DP waits only for the last traceback that read ITS checkpoint
   // block (the context alternates two), so it overlaps the previous plan's traceback; inside a plan the chunks share the block.
   for (size_t k = 0; k < pl->chunks.size(); ++k)
     {
       Chunk & c = pl->chunks[k];
       uint32_t * dir = pl->d_dir[0].p;
-      if (k >= 1) HIPCHK(hipStreamWaitEvent(st, pl->chunks[k - 1].e2, 0));      // buffer reuse: the previous traceback is done
-      else if (ctx->ev_tb_used[slot]) HIPCHK(hipStreamWaitEvent(st, ctx->ev_tb[slot], 0));
-      HIPCHK(hipEventRecord(c.e0, st));
+      if (k >= 1) VSX_HIP(hipStreamWaitEvent(st, pl->chunks[k - 1].e2, 0));      // buffer reuse: the previous traceback is done
+      else if (ctx->ev_tb_used[slot]) VSX_HIP(hipStreamWaitEvent(st, ctx->ev_tb[slot], 0));
+      VSX_HIP(hipEventRecord(c.e0, st));
       for (const Launch & L : c.launches)
         {
           VsxDevParams Pf = L.tilt ? ctx->Pt : ctx->P;
           Pf.max3 = (L.tilt == 2) ? 1 : 0;
           static const bool one_off = std::getenv("VSX_ONESTRIP") && std::strcmp(std::getenv("VSX_ONESTRIP"), "0") == 0;      // A/B, tests: the general kernels
-          HIPCHK(vsx_launch_forward(L.rows, L.track, L.nq, (L.multi || (one_off && L.nq != 8)) ? 0 : 1, Pf, pl->d_tasks.p + L.first, L.count,
+          VSX_HIP(vsx_launch_forward(L.rows, L.track, L.nq, (L.multi || (one_off && L.nq != 8)) ? 0 : 1, Pf, pl->d_tasks.p + L.first, L.count,
                                     pl->Q->codes(), pl->T->codes(), dir, pl->d_strip.p,
                                     pl->d_slot.p + (size_t) L.first * VSX_TASK_SLOTS, st));
         }
-      HIPCHK(hipEventRecord(c.e1, st));
-      HIPCHK(hipStreamWaitEvent(st2, c.e1, 0));
-      HIPCHK(hipEventRecord(c.e1b, st2));
+      VSX_HIP(hipEventRecord(c.e1, st));
+      VSX_HIP(hipStreamWaitEvent(st2, c.e1, 0));
+      VSX_HIP(hipEventRecord(c.e1b, st2));
       for (size_t li = 0; li < c.launches.size();)      // the recompute traceback is specialised on R like the DP kernel
         {
           const Launch & L = c.launches[li];
@@ -1689,22 +1642,22 @@ int vsx_plan_run(vsx_plan * pl)
                  c.launches[lj].track == L.track && c.launches[lj].tilt == L.tilt) { pair_count += c.launches[lj].pair_count; ++lj; }
           VsxDevParams Pb = L.tilt ? ctx->Pt : ctx->P;
           Pb.max3 = (L.tilt == 2) ? 1 : 0;         // the checkpoints of the MAX3 class carry its bias
-          HIPCHK(vsx_launch_traceback_ck(L.rows, L.track == 0 ? 1 : 0, Pb, pl->filter, pl->d_tasks.p, pl->d_pair_slot.p + L.pair_first,
+          VSX_HIP(vsx_launch_traceback_ck(L.rows, L.track == 0 ? 1 : 0, Pb, pl->filter, pl->d_tasks.p, pl->d_pair_slot.p + L.pair_first,
                                          pl->d_pair_ids.p + L.pair_first, pair_count, pl->Q->codes(), pl->T->codes(),
                                          dir, pl->d_slot.p, pl->d_slab.p, pl->d_slab_off.p + L.pair_first,
                                          pl->d_runs.p, pl->runs_capacity, pl->d_cursor.p, pl->d_out.p, st2));
           li = lj;
         }
-      HIPCHK(hipEventRecord(c.e2, st2));
+      VSX_HIP(hipEventRecord(c.e2, st2));
     }
-  if (pl->chunks.empty()) HIPCHK(hipStreamWaitEvent(st2, pl->ev_begin, 0));          // (the cursor memset precedes the text kernel)
-  HIPCHK(hipEventRecord(ctx->ev_tb[slot], st2));
+  if (pl->chunks.empty()) VSX_HIP(hipStreamWaitEvent(st2, pl->ev_begin, 0));          // (the cursor memset precedes the text kernel)
+  VSX_HIP(hipEventRecord(ctx->ev_tb[slot], st2));
   ctx->ev_tb_used[slot] = true;
   // run lists -> CIGAR text, records -> output arrays (pushop / finishop are part of the reference's timed path); st2 is in order
-  HIPCHK(vsx_launch_cigar_text(pl->d_out.p, pl->d_pair_ids.p, (uint32_t) pl->pair_ids.size(), pl->d_runs.p, pl->runs_capacity,
+  VSX_HIP(vsx_launch_cigar_text(pl->d_out.p, pl->d_pair_ids.p, (uint32_t) pl->pair_ids.size(), pl->d_runs.p, pl->runs_capacity,
                                pl->d_text.p, pl->text_capacity, pl->d_cursor.p + 1, pl->soa, st2));
-  HIPCHK(hipMemcpyAsync(pl->h_cursor, pl->d_cursor.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st2));
-  HIPCHK(hipEventRecord(pl->ev_end, st2));
+  VSX_HIP(hipMemcpyAsync(pl->h_cursor, pl->d_cursor.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st2));
+  VSX_HIP(hipEventRecord(pl->ev_end, st2));
   pl->ran = true;
   pl->host_patched = false;            // the exported records of host-answered pairs point behind THIS run's device runs
   return VSX_OK;
@@ -1714,22 +1667,22 @@ int vsx_plan_sync(vsx_plan * pl, vsx_timing * tm)
 {
   if (!pl) return fail(VSX_EINVAL, "vsx_plan_sync: null plan");
   if (!pl->ran) return fail(VSX_EINVAL, "vsx_plan_sync: plan has not been run");
-  HIPCHK(hipSetDevice(pl->ctx->device));
-  HIPCHK(hipEventSynchronize(pl->ev_end));
+  VSX_HIP(hipSetDevice(pl->ctx->device));
+  VSX_HIP(hipEventSynchronize(pl->ev_end));
   if (tm)
     {
       *tm = vsx_timing {};
       for (Chunk & c : pl->chunks)
         {
           float a = 0, b = 0;
-          HIPCHK(hipEventElapsedTime(&a, c.e0, c.e1));
-          HIPCHK(hipEventElapsedTime(&b, c.e1b, c.e2));
+          VSX_HIP(hipEventElapsedTime(&a, c.e0, c.e1));
+          VSX_HIP(hipEventElapsedTime(&b, c.e1b, c.e2));
           tm->forward_ms += a;
           tm->traceback_ms += b;
           tm->forward_launches += (uint32_t) c.launches.size();
           tm->traceback_launches += 1;
         }
-      HIPCHK(hipEventElapsedTime(&tm->total_ms, pl->ev_begin, pl->ev_end));
+      VSX_HIP(hipEventElapsedTime(&tm->total_ms, pl->ev_begin, pl->ev_end));
       tm->cells = pl->cells;
       tm->dir_bytes = pl->dir_bytes_total;
     }
@@ -1784,14 +1737,14 @@ static int settle(vsx_plan * pl, unsigned long long & used, unsigned long long &
   if (!pl->ran) { int rc = vsx_plan_run(pl); if (rc != VSX_OK) return rc; }
   int rc = vsx_plan_sync(pl, nullptr);
   if (rc != VSX_OK) return rc;
-  HIPCHK(hipSetDevice(ctx->device));
+  VSX_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   used = pl->h_cursor[0]; text_used = pl->h_cursor[1];
   if (used > pl->runs_capacity)
     {
       // the dense run buffer was sized for typical alignments; size it exactly and run again
       pl->runs_capacity = used + 1;
-      HIPCHK(pl->d_runs.alloc(&pl->ctx->pool, pl->runs_capacity));
+      VSX_HIP(pl->d_runs.alloc(&pl->ctx->pool, pl->runs_capacity));
       if ((rc = vsx_plan_run(pl)) != VSX_OK) return rc;
       if ((rc = vsx_plan_sync(pl, nullptr)) != VSX_OK) return rc;
       used = pl->h_cursor[0]; text_used = pl->h_cursor[1];
@@ -1801,12 +1754,12 @@ static int settle(vsx_plan * pl, unsigned long long & used, unsigned long long &
     {
       // same for the text: only the formatting kernel runs again
       pl->text_capacity = text_used + 16;
-      HIPCHK(pl->d_text.alloc(&pl->ctx->pool, pl->text_capacity));
-      HIPCHK(hipMemsetAsync(pl->d_cursor.p + 1, 0, sizeof(unsigned long long), st));
-      HIPCHK(vsx_launch_cigar_text(pl->d_out.p, pl->d_pair_ids.p, (uint32_t) pl->pair_ids.size(), pl->d_runs.p, pl->runs_capacity,
+      VSX_HIP(pl->d_text.alloc(&pl->ctx->pool, pl->text_capacity));
+      VSX_HIP(hipMemsetAsync(pl->d_cursor.p + 1, 0, sizeof(unsigned long long), st));
+      VSX_HIP(vsx_launch_cigar_text(pl->d_out.p, pl->d_pair_ids.p, (uint32_t) pl->pair_ids.size(), pl->d_runs.p, pl->runs_capacity,
                                    pl->d_text.p, pl->text_capacity, pl->d_cursor.p + 1, pl->soa, st));
-      HIPCHK(hipMemcpyAsync(pl->h_cursor, pl->d_cursor.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
+      VSX_HIP(hipMemcpyAsync(pl->h_cursor, pl->d_cursor.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      VSX_HIP(hipStreamSynchronize(st));
       text_used = pl->h_cursor[1];
       if (text_used > pl->text_capacity) return fail(VSX_EHIP, "vsx_plan_fetch: text buffer overflow after resize");
     }
@@ -1921,15 +1874,15 @@ static int fetch_ranked_lists(vsx_plan * pl, uint64_t first, const uint32_t * qk
   hipStream_t st = ctx->stream_dn;
   const uint64_t n = pl->n_pairs;
   uint32_t counts[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(counts, pl->d_rank_counts.p, sizeof counts, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  VSX_HIP(hipMemcpyAsync(counts, pl->d_rank_counts.p, sizeof counts, hipMemcpyDeviceToHost, st));
+  VSX_HIP(hipStreamSynchronize(st));
   const uint32_t kept = counts[0], n_refused = counts[1];
   if (kept > n || n_refused > n) return fail(VSX_EHIP, "vsx_align_pairs_ranked: the kept / refused lists are corrupt");
   if (n_refused)
     {
       // (include/vsx.h: a pair the 16-bit aligner refused is `undecided`, never silently dropped)
       std::vector<uint32_t> rf(n_refused);
-      HIPCHK(hipMemcpy(rf.data(), pl->d_refused_pair.p, (size_t) n_refused * 4, hipMemcpyDeviceToHost));
+      VSX_HIP(hipMemcpy(rf.data(), pl->d_refused_pair.p, (size_t) n_refused * 4, hipMemcpyDeviceToHost));
       std::sort(rf.begin(), rf.end());
       for (uint32_t k : rf) S.undecided.push_back((uint32_t) (first + k));
     }
@@ -1939,7 +1892,7 @@ static int fetch_ranked_lists(vsx_plan * pl, uint64_t first, const uint32_t * qk
   for (int x = 0; x < 9; ++x) { off[x] = at; at += ((uint64_t) kept * width[x] + 15) & ~15ull; }
   const uint64_t rank_bytes = at;
   PoolBuf<uint8_t> d_rank;
-  HIPCHK(d_rank.alloc(&ctx->pool, rank_bytes));
+  VSX_HIP(d_rank.alloc(&ctx->pool, rank_bytes));
   VsxRankedOut R;
   R.pair = reinterpret_cast<uint32_t *>(d_rank.p + off[0]);
   R.id = reinterpret_cast<double *>(d_rank.p + off[1]);
@@ -1950,13 +1903,13 @@ static int fetch_ranked_lists(vsx_plan * pl, uint64_t first, const uint32_t * qk
   R.mismatches = reinterpret_cast<uint16_t *>(d_rank.p + off[6]);
   R.gaps = reinterpret_cast<uint16_t *>(d_rank.p + off[7]);
   R.verdict = d_rank.p + off[8];
-  HIPCHK(vsx_rank_gather_list(pl->d_kept_pair.p, pl->d_kept_id.p, kept, pl->d_out.p, pl->soa.text_off, R, st));
+  VSX_HIP(vsx_rank_gather_list(pl->d_kept_pair.p, pl->d_kept_id.p, kept, pl->d_out.p, pl->soa.text_off, R, st));
   std::lock_guard<std::mutex> lk(ctx->stage_mu);
   int rc = stage_reserve(ctx, rank_bytes + ((text_used + 15) & ~15ull));
   if (rc != VSX_OK) return rc;
-  HIPCHK(hipMemcpyAsync(ctx->stage, d_rank.p, rank_bytes, hipMemcpyDeviceToHost, st));
-  if (text_used) HIPCHK(hipMemcpyAsync(ctx->stage + rank_bytes, pl->d_text.p, text_used, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  VSX_HIP(hipMemcpyAsync(ctx->stage, d_rank.p, rank_bytes, hipMemcpyDeviceToHost, st));
+  if (text_used) VSX_HIP(hipMemcpyAsync(ctx->stage + rank_bytes, pl->d_text.p, text_used, hipMemcpyDeviceToHost, st));
+  VSX_HIP(hipStreamSynchronize(st));
   const uint8_t * sg = ctx->stage;
   const char * text = reinterpret_cast<const char *>(sg + rank_bytes);
   const uint32_t * h_pair = reinterpret_cast<const uint32_t *>(sg + off[0]);
@@ -2062,25 +2015,25 @@ int vsx_plan_export_hits(vsx_plan * pl, void * d_dst, uint64_t dst_bytes)
   if (!pl || !d_dst) return fail(VSX_EINVAL, "vsx_plan_export_hits: null argument");
   if (!pl->ran) return fail(VSX_EINVAL, "vsx_plan_export_hits: plan has not been run");
   if (dst_bytes < pl->n_pairs * sizeof(VsxPairOut)) return fail(VSX_EINVAL, "vsx_plan_export_hits: destination too small");
-  HIPCHK(hipSetDevice(pl->ctx->device));
+  VSX_HIP(hipSetDevice(pl->ctx->device));
   hipStream_t st = pl->ctx->stream;
-  HIPCHK(hipEventSynchronize(pl->ev_end));          // the records are written on the traceback stream
+  VSX_HIP(hipEventSynchronize(pl->ev_end));          // the records are written on the traceback stream
   if (!pl->host_patched)
     {
       // pairs answered without DP live on the host: patch them into the device array once; their CIGARs (the Q == 0 closed
       // form, one 'I' run) follow the device runs in the exported run buffer (vsx_plan_export_runs)
-      HIPCHK(hipEventSynchronize(pl->ev_end));
+      VSX_HIP(hipEventSynchronize(pl->ev_end));
       const uint64_t used = pl->h_cursor[0];
       for (size_t h = 0, hc = 0; h < pl->host_pairs.size(); ++h)
         {
           VsxPairOut o = pl->host_out[h];
           if (hc < pl->host_cigar_pair.size() && pl->host_cigar_pair[hc] == pl->host_pairs[h]) { o.nruns = 1; o.run_off = used + hc; ++hc; }
-          HIPCHK(hipMemcpy(pl->d_out.p + pl->host_pairs[h], &o, sizeof(VsxPairOut), hipMemcpyHostToDevice));
+          VSX_HIP(hipMemcpy(pl->d_out.p + pl->host_pairs[h], &o, sizeof(VsxPairOut), hipMemcpyHostToDevice));
         }
       pl->host_patched = true;
     }
-  HIPCHK(hipMemcpyAsync(d_dst, pl->d_out.p, pl->n_pairs * sizeof(VsxPairOut), hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
+  VSX_HIP(hipMemcpyAsync(d_dst, pl->d_out.p, pl->n_pairs * sizeof(VsxPairOut), hipMemcpyDeviceToDevice, st));
+  VSX_HIP(hipStreamSynchronize(st));
   return VSX_OK;
 }
 
@@ -2088,17 +2041,17 @@ int vsx_plan_export_runs(vsx_plan * pl, void * d_dst, uint64_t dst_bytes, uint64
 {
   if (!pl || !n_runs) return fail(VSX_EINVAL, "vsx_plan_export_runs: null argument");
   if (!pl->ran) return fail(VSX_EINVAL, "vsx_plan_export_runs: plan has not been run");
-  HIPCHK(hipSetDevice(pl->ctx->device));
-  HIPCHK(hipEventSynchronize(pl->ev_end));
+  VSX_HIP(hipSetDevice(pl->ctx->device));
+  VSX_HIP(hipEventSynchronize(pl->ev_end));
   const uint64_t used = pl->h_cursor[0];
   if (used > pl->runs_capacity) return fail(VSX_EINVAL, "vsx_plan_export_runs: the run buffer overflowed; call vsx_plan_fetch first (it resizes and re-runs)");
   const uint64_t extra = pl->host_cigar_run.size();          // run words of the pairs answered on the host, behind the device's
   *n_runs = used + extra;
   if (!d_dst) return VSX_OK;                     // size query
   if (dst_bytes < (used + extra) * 4) return fail(VSX_EINVAL, "vsx_plan_export_runs: destination too small");
-  if (used) HIPCHK(hipMemcpyAsync(d_dst, pl->d_runs.p, used * 4, hipMemcpyDeviceToDevice, pl->ctx->stream));
-  if (extra) HIPCHK(hipMemcpyAsync(static_cast<uint32_t *>(d_dst) + used, pl->host_cigar_run.data(), extra * 4, hipMemcpyHostToDevice, pl->ctx->stream));
-  HIPCHK(hipStreamSynchronize(pl->ctx->stream));
+  if (used) VSX_HIP(hipMemcpyAsync(d_dst, pl->d_runs.p, used * 4, hipMemcpyDeviceToDevice, pl->ctx->stream));
+  if (extra) VSX_HIP(hipMemcpyAsync(static_cast<uint32_t *>(d_dst) + used, pl->host_cigar_run.data(), extra * 4, hipMemcpyHostToDevice, pl->ctx->stream));
+  VSX_HIP(hipStreamSynchronize(pl->ctx->stream));
   return VSX_OK;
 }
 

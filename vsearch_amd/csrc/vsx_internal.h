@@ -1,4 +1,6 @@
-// vsx_internal.h -- shared between the HIP kernels (vsx_device.hip) and the host layer (vsx_host.cpp).
+// vsx_internal.h -- PODs and kernel launchers shared between the HIP files (vsx_device.hip, vsx_tbtext.hip, vsx_rank.hip, vsx_kmer.hip,
+// vsx_mask.hip, vsx_chimera.hip) and the host files that drive them; includable from device code.  What only host files share
+// (the vsx_internal_* functions, the error / buffer helpers) is in vsx_private.h.
 #ifndef VSX_INTERNAL_H
 #define VSX_INTERNAL_H
 
@@ -207,6 +209,15 @@ hipError_t vsx_kmer_launch_select(const void * rec, uint32_t subcap, uint32_t nt
                                   uint32_t keep, void * dense, unsigned long long * cursor, uint64_t capacity,
                                   void * sel_m_n, uint64_t * sel_off, hipStream_t st);
 uint32_t vsx_kmer_tile_shift(void);
+// packed postings (word lengths 3..8, whole-set index: sorted byte-gap postings, see vsx_kmer.hip)
+hipError_t vsx_kmer_packed_tile(int fill, const uint8_t * codes, const uint64_t * off, const uint32_t * len, uint32_t first_seq,
+                                uint32_t nseq_tile, int w, const uint8_t * lower_bits, const uint64_t * slot_of, uint64_t n_slots,
+                                uint32_t * keys_a, uint32_t * keys_b, void * temp, size_t * temp_bytes, uint32_t tile, uint32_t ntiles,
+                                uint32_t * bucket_count, const uint64_t * bucket_start, uint32_t * postings, hipStream_t st);
+uint32_t vsx_kmer_packed_tile_seqs(void);
+hipError_t vsx_kmer_launch_select_packed(const void * rec, uint32_t subcap, uint32_t ntiles, const uint32_t * tile_count, uint32_t nslots,
+                                         uint32_t keep, void * dense, unsigned long long * cursor, uint64_t capacity,
+                                         void * sel_m_n, uint64_t * sel_off, hipStream_t st);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 // vsx_kmer_host.cpp -- builds and drives the device k-mer index (kernels: vsx_kmer.hip).
 #include "vsx_kmer.h"
 #include "vsx_internal.h"
+#include "vsx_private.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -10,88 +11,22 @@
 #include <condition_variable>
 #include <memory>
 #include <mutex>
-#include <string>
 
-extern "C" void vsx_internal_set_error(const char * msg);
-extern "C" int vsx_internal_device(const vsx_ctx * ctx);
-extern "C" hipStream_t vsx_internal_stream(const vsx_ctx * ctx);
-extern "C" void vsx_internal_seqset_device(const vsx_seqset * s, const uint8_t ** codes, const uint64_t ** off,
-                                           const uint32_t ** len, uint64_t * n);
-// the set's case bitmap (soft masking) or NULL: an index over a set that has one leaves out every word over a lower-case symbol
-extern "C" const uint8_t * vsx_internal_seqset_lower(const vsx_seqset * s);
-extern "C" const uint32_t * vsx_internal_seqset_host_lengths(const vsx_seqset * s);
-
-// vsx_kmer.hip, packed postings (see there)
-extern "C" hipError_t vsx_kmer_packed_tile(int fill, const uint8_t * codes, const uint64_t * off, const uint32_t * len, uint32_t first_seq,
-                                           uint32_t nseq_tile, int w, const uint8_t * lower_bits, const uint64_t * slot_of, uint64_t n_slots,
-                                           uint32_t * keys_a, uint32_t * keys_b, void * temp, size_t * temp_bytes, uint32_t tile, uint32_t ntiles,
-                                           uint32_t * bucket_count, const uint64_t * bucket_start, uint32_t * postings, hipStream_t st);
-extern "C" uint32_t vsx_kmer_packed_tile_seqs(void);
 #include "vsx_kmer_pack.h"
-extern "C" hipError_t vsx_kmer_launch_select_packed(const void * rec, uint32_t subcap, uint32_t ntiles, const uint32_t * tile_count, uint32_t nslots,
-                                                    uint32_t keep, void * dense, unsigned long long * cursor, uint64_t capacity,
-                                                    void * sel_m_n, uint64_t * sel_off, hipStream_t st);
 
-extern "C" void vsx_internal_poison(void * p, size_t bytes);
-extern "C" uint64_t vsx_internal_memory_pressure(int device);
-#ifndef VSX_DEVICE_RESERVE_BYTES
-#define VSX_DEVICE_RESERVE_BYTES ((size_t) 6 << 30)      // what stays free for the runtime itself (kernel scratch of every queue, code objects)
-#endif      // vsx_host.cpp: every context of the device frees what no plan holds
-namespace {
-
-int kfail(int code, const char * what, hipError_t e)
-{
-  std::string m = std::string(what) + ": " + hipGetErrorString(e);
-  vsx_internal_set_error(m.c_str());
-  return code;
-}
-
-template <typename T> struct Buf {
-  T * p = nullptr;
-  size_t n = 0;
-  ~Buf() { if (p) (void) hipFree(p); }
-  hipError_t alloc(size_t count)
-  {
-    if (p) { (void) hipFree(p); p = nullptr; n = 0; }
-    const size_t want = std::max<size_t>(count, 1) * sizeof(T);
-    if (want >= ((size_t) 16 << 20))
-      {
-        // a device filled to the brim fails LATER and worse than a refused hipMalloc: the runtime cannot allocate a queue's kernel scratch
-        // and aborts the process (HSA_STATUS_ERROR_OUT_OF_RESOURCES, profiles/r05/r05b_config5_share_abort.txt).  Keep a reserve.
-        size_t free_b = 0, total_b = 0;
-        int dev = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < want + VSX_DEVICE_RESERVE_BYTES && hipGetDevice(&dev) == hipSuccess)
-          (void) vsx_internal_memory_pressure(dev);
-        (void) hipGetLastError();
-      }
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipErrorOutOfMemory)
-      {
-        // (r05) the aligner contexts of this device may sit on idle checkpoint blocks of an earlier, much larger plan: ask for them
-        int dev = 0;
-        (void) hipGetLastError();
-        if (hipGetDevice(&dev) == hipSuccess && vsx_internal_memory_pressure(dev) > 0)
-          e = hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T));
-      }
-    if (e == hipSuccess) { n = count; vsx_internal_poison(p, std::max<size_t>(count, 1) * sizeof(T)); }
-    return e;
-  }
-  hipError_t ensure(size_t count) { return (p && count <= n) ? hipSuccess : alloc(count); }
-};
-
-}  // namespace
+using vsxp::DevBuf;
 
 // Per-call state of a counting batch.  The index itself is read-only between rebuilds, so several batches may count against
 // it at once, each with its own scratch and stream: the search runs two windows' k-mer stages concurrently, one's host work
 // (CSR, uploads, record download, ranking) under the other's counting kernel.
 struct KmerScratch {
   hipStream_t st = nullptr;
-  Buf<uint64_t> d_qk_start;
-  Buf<uint32_t> d_qk, d_minmatch;
-  Buf<uint64_t> d_rec, d_dense, d_sel_mn, d_sel_off;    // uint2 records (target, count); (kept, seen) per slot
-  Buf<uint64_t> d_ranges;                                // uint2 (first unit, units) per (tile, slot, word): 8-bit class
-  Buf<uint32_t> d_tilecnt;                               // records per (slot, tile)
-  Buf<unsigned long long> d_cursor;
+  DevBuf<uint64_t> d_qk_start;
+  DevBuf<uint32_t> d_qk, d_minmatch;
+  DevBuf<uint64_t> d_rec, d_dense, d_sel_mn, d_sel_off;    // uint2 records (target, count); (kept, seen) per slot
+  DevBuf<uint64_t> d_ranges;                                // uint2 (first unit, units) per (tile, slot, word): 8-bit class
+  DevBuf<uint32_t> d_tilecnt;                               // records per (slot, tile)
+  DevBuf<unsigned long long> d_cursor;
   hipEvent_t e0 = nullptr, e1 = nullptr, e_turn = nullptr;   // timing; e_turn = this batch's counting kernels are done
   uint64_t records = 0;
   bool busy = false;
@@ -115,8 +50,8 @@ struct VsxKmerIndex {
   bool prewarm = false;           // a search index: make the spare scratch sets behind the first batch (vsx_kmer_count_batch)
   uint32_t nseq = 0, ntiles = 0;
   uint64_t nbuckets = 0;
-  Buf<uint64_t> d_start;          // nbuckets + 1
-  Buf<uint32_t> d_post, d_count, d_list;
+  DevBuf<uint64_t> d_start;          // nbuckets + 1
+  DevBuf<uint32_t> d_post, d_count, d_list;
   std::vector<uint32_t> h_count;
   std::vector<uint64_t> h_start;
   // per-batch scratch sets (at most VSX_KMER_SCRATCH_MAX), handed out under the lock
@@ -145,8 +80,6 @@ struct VsxKmerIndex {
   }
 };
 
-#define KCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return kfail(e_ == hipErrorOutOfMemory ? VSX_ENOMEM : VSX_EHIP, #x, e_); } while (0)
-
 int vsx_kmer_index_create(vsx_ctx * ctx, const vsx_seqset * db, int w, VsxKmerIndex ** out)
 {
   if (!ctx || !db || !out) { vsx_internal_set_error("vsx_kmer_index_create: null argument"); return VSX_EINVAL; }
@@ -158,9 +91,9 @@ int vsx_kmer_index_create(vsx_ctx * ctx, const vsx_seqset * db, int w, VsxKmerIn
   ix->packed = !ix->tagged;                          // the whole-set index of a short word length takes the packed format
   ix->prewarm = true;
   ix->make_stream();
-  KCHK(hipSetDevice(ix->device));
-  KCHK(hipEventCreate(&ix->e0));
-  KCHK(hipEventCreate(&ix->e1));
+  VSX_HIP(hipSetDevice(ix->device));
+  VSX_HIP(hipEventCreate(&ix->e0));
+  VSX_HIP(hipEventCreate(&ix->e1));
   const int rc = vsx_kmer_index_rebuild(ix.get(), nullptr, 0);
   if (rc != VSX_OK) return rc;
   *out = ix.release();
@@ -175,9 +108,9 @@ int vsx_kmer_index_create_empty(vsx_ctx * ctx, const vsx_seqset * db, int w, Vsx
   std::unique_ptr<VsxKmerIndex> ix(new VsxKmerIndex);
   ix->ctx = ctx; ix->db = db; ix->device = vsx_internal_device(ctx); ix->st = vsx_internal_stream(ctx); ix->w = w;
   ix->make_stream();
-  KCHK(hipSetDevice(ix->device));
-  KCHK(hipEventCreate(&ix->e0));
-  KCHK(hipEventCreate(&ix->e1));
+  VSX_HIP(hipSetDevice(ix->device));
+  VSX_HIP(hipEventCreate(&ix->e0));
+  VSX_HIP(hipEventCreate(&ix->e1));
   *out = ix.release();
   return VSX_OK;
 }
@@ -191,7 +124,7 @@ int vsx_kmer_index_rebuild(VsxKmerIndex * ix, const uint32_t * list, uint64_t n_
   vsx_internal_seqset_device(ix->db, &codes, &off, &len, &n_all);
   const uint64_t n = list ? n_list : n_all;
   if (n >= (1ull << 31)) { vsx_internal_set_error("vsx_kmer_index_rebuild: too many sequences"); return VSX_EINVAL; }
-  KCHK(hipSetDevice(ix->device));
+  VSX_HIP(hipSetDevice(ix->device));
   const int w = ix->w;
   const uint32_t shift = vsx_kmer_tile_shift();
   if (ix->tagged && list) { vsx_internal_set_error("vsx_kmer_index_rebuild: subset indexes exist for word lengths 3..8 only"); return VSX_EINVAL; }
@@ -207,18 +140,18 @@ int vsx_kmer_index_rebuild(VsxKmerIndex * ix, const uint32_t * list, uint64_t n_
   const uint32_t * d_list = nullptr;
   if (list)
     {
-      KCHK(ix->d_list.ensure(n));
-      KCHK(hipMemcpyAsync(ix->d_list.p, list, n * 4, hipMemcpyHostToDevice, ix->st));
+      VSX_HIP(ix->d_list.ensure(n));
+      VSX_HIP(hipMemcpyAsync(ix->d_list.p, list, n * 4, hipMemcpyHostToDevice, ix->st));
       d_list = ix->d_list.p;
     }
-  KCHK(ix->d_count.ensure(ix->nbuckets));
-  KCHK(ix->d_start.ensure(ix->nbuckets + 1));
-  KCHK(hipEventRecord(ix->e0, ix->st));
-  KCHK(hipMemsetAsync(ix->d_count.p, 0, ix->nbuckets * 4, ix->st));
+  VSX_HIP(ix->d_count.ensure(ix->nbuckets));
+  VSX_HIP(ix->d_start.ensure(ix->nbuckets + 1));
+  VSX_HIP(hipEventRecord(ix->e0, ix->st));
+  VSX_HIP(hipMemsetAsync(ix->d_count.p, 0, ix->nbuckets * 4, ix->st));
   // tagged build (word lengths 9..15): per tile keys -> sort -> runs; scratch for the largest tile
   // (packed build, word lengths 3..8: the same per-tile scheme with 32-bit keys, vsx_kmer_packed_tile)
-  Buf<uint64_t> d_slot, d_keys_a, d_keys_b;                       // packed: the key buffers hold 32-bit keys (half used)
-  Buf<uint8_t> d_sort_temp;
+  DevBuf<uint64_t> d_slot, d_keys_a, d_keys_b;                       // packed: the key buffers hold 32-bit keys (half used)
+  DevBuf<uint8_t> d_sort_temp;
   std::vector<uint64_t> slot_of;
   size_t sort_bytes = 0;
   const bool sorted_build = ix->tagged || ix->packed;
@@ -227,11 +160,11 @@ int vsx_kmer_index_rebuild(VsxKmerIndex * ix, const uint32_t * list, uint64_t n_
       {
         const uint64_t first = (uint64_t) t * tile_seqs, last = std::min<uint64_t>(n, first + tile_seqs);
         if (ix->packed)
-          KCHK(vsx_kmer_packed_tile(fill, codes, off, len, (uint32_t) first, (uint32_t) (last - first), w, vsx_internal_seqset_lower(ix->db), d_slot.p,
+          VSX_HIP(vsx_kmer_packed_tile(fill, codes, off, len, (uint32_t) first, (uint32_t) (last - first), w, vsx_internal_seqset_lower(ix->db), d_slot.p,
                                     slot_of[last] - slot_of[first], reinterpret_cast<uint32_t *>(d_keys_a.p), reinterpret_cast<uint32_t *>(d_keys_b.p),
                                     d_sort_temp.p, &sort_bytes, t, ix->ntiles, ix->d_count.p, ix->d_start.p, ix->d_post.p, ix->st));
         else
-        KCHK(vsx_kmer_tagged_tile(fill, codes, off, len, (uint32_t) first, (uint32_t) (last - first), w, vsx_internal_seqset_lower(ix->db), d_slot.p,
+        VSX_HIP(vsx_kmer_tagged_tile(fill, codes, off, len, (uint32_t) first, (uint32_t) (last - first), w, vsx_internal_seqset_lower(ix->db), d_slot.p,
                                   slot_of[last] - slot_of[first], d_keys_a.p, d_keys_b.p, d_sort_temp.p, &sort_bytes, t, ix->ntiles, ix->d_count.p,
                                   ix->d_start.p, ix->d_post.p, ix->st));
       }
@@ -248,27 +181,27 @@ int vsx_kmer_index_rebuild(VsxKmerIndex * ix, const uint32_t * list, uint64_t n_
           const uint64_t first = (uint64_t) t * tile_seqs, last = std::min<uint64_t>(n, first + tile_seqs);
           widest = std::max(widest, slot_of[last] - slot_of[first]);
         }
-      KCHK(d_slot.alloc(n + 1));
-      KCHK(hipMemcpyAsync(d_slot.p, slot_of.data(), (n + 1) * 8, hipMemcpyHostToDevice, ix->st));
-      KCHK(d_keys_a.alloc(std::max<uint64_t>(widest, 1)));
-      KCHK(d_keys_b.alloc(std::max<uint64_t>(widest, 1)));
+      VSX_HIP(d_slot.alloc(n + 1));
+      VSX_HIP(hipMemcpyAsync(d_slot.p, slot_of.data(), (n + 1) * 8, hipMemcpyHostToDevice, ix->st));
+      VSX_HIP(d_keys_a.alloc(std::max<uint64_t>(widest, 1)));
+      VSX_HIP(d_keys_b.alloc(std::max<uint64_t>(widest, 1)));
       if (ix->packed)
-        KCHK(vsx_kmer_packed_tile(0, nullptr, nullptr, nullptr, 0, 0, w, nullptr, nullptr, widest, reinterpret_cast<uint32_t *>(d_keys_a.p),
+        VSX_HIP(vsx_kmer_packed_tile(0, nullptr, nullptr, nullptr, 0, 0, w, nullptr, nullptr, widest, reinterpret_cast<uint32_t *>(d_keys_a.p),
                                   reinterpret_cast<uint32_t *>(d_keys_b.p), nullptr, &sort_bytes, 0, ix->ntiles, nullptr, nullptr, nullptr, ix->st));
       else
-      KCHK(vsx_kmer_tagged_tile(0, nullptr, nullptr, nullptr, 0, 0, w, nullptr, nullptr, widest, d_keys_a.p, d_keys_b.p, nullptr, &sort_bytes, 0, ix->ntiles,
+      VSX_HIP(vsx_kmer_tagged_tile(0, nullptr, nullptr, nullptr, 0, 0, w, nullptr, nullptr, widest, d_keys_a.p, d_keys_b.p, nullptr, &sort_bytes, 0, ix->ntiles,
                                 nullptr, nullptr, nullptr, ix->st));
-      KCHK(d_sort_temp.alloc(sort_bytes + 16));
+      VSX_HIP(d_sort_temp.alloc(sort_bytes + 16));
       const int prc = tagged_pass(0);
       if (prc != VSX_OK) return prc;
     }
   else
-  KCHK(vsx_kmer_launch_sweep(0, codes, off, len, d_list, ix->nseq, w, ix->ntiles, ix->d_count.p, nullptr, nullptr, vsx_internal_seqset_lower(ix->db), ix->st));
+  VSX_HIP(vsx_kmer_launch_sweep(0, codes, off, len, d_list, ix->nseq, w, ix->ntiles, ix->d_count.p, nullptr, nullptr, vsx_internal_seqset_lower(ix->db), ix->st));
   // bucket table: exclusive prefix sum on the host (4^w x ntiles entries: 8 MB for 1 M sequences, w = 8)
   std::vector<uint32_t> & cnt = ix->h_count;
   cnt.resize(ix->nbuckets);
-  KCHK(hipMemcpyAsync(cnt.data(), ix->d_count.p, ix->nbuckets * 4, hipMemcpyDeviceToHost, ix->st));
-  KCHK(hipStreamSynchronize(ix->st));
+  VSX_HIP(hipMemcpyAsync(cnt.data(), ix->d_count.p, ix->nbuckets * 4, hipMemcpyDeviceToHost, ix->st));
+  VSX_HIP(hipStreamSynchronize(ix->st));
   std::vector<uint64_t> & start = ix->h_start;
   start.resize(ix->nbuckets + 1);
   uint64_t acc = 0;
@@ -300,22 +233,22 @@ int vsx_kmer_index_rebuild(VsxKmerIndex * ix, const uint32_t * list, uint64_t n_
   }
   start[ix->nbuckets] = acc;
   if (acc >= (1ull << 32)) { vsx_internal_set_error("vsx_kmer_index_rebuild: more than 64 GB of postings (32-bit unit addresses)"); return VSX_EINVAL; }
-  KCHK(ix->d_post.ensure(acc * 4));                    // dwords
+  VSX_HIP(ix->d_post.ensure(acc * 4));                    // dwords
   if (acc && !ix->packed)                                  // (the packed walk writes whole units)
-    KCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ix->d_post.p), (int) (ix->tagged ? 0xFFFF8000u : 0x80008000u), acc * 4, ix->st));
-  KCHK(hipMemcpyAsync(ix->d_start.p, start.data(), (ix->nbuckets + 1) * 8, hipMemcpyHostToDevice, ix->st));
-  KCHK(hipMemsetAsync(ix->d_count.p, 0, ix->nbuckets * 4, ix->st));
+    VSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ix->d_post.p), (int) (ix->tagged ? 0xFFFF8000u : 0x80008000u), acc * 4, ix->st));
+  VSX_HIP(hipMemcpyAsync(ix->d_start.p, start.data(), (ix->nbuckets + 1) * 8, hipMemcpyHostToDevice, ix->st));
+  VSX_HIP(hipMemsetAsync(ix->d_count.p, 0, ix->nbuckets * 4, ix->st));
   if (sorted_build)
     {
       const int prc = tagged_pass(1);
       if (prc != VSX_OK) return prc;
     }
   else
-  KCHK(vsx_kmer_launch_sweep(1, codes, off, len, d_list, ix->nseq, w, ix->ntiles, ix->d_count.p, ix->d_start.p, ix->d_post.p, vsx_internal_seqset_lower(ix->db), ix->st));
-  KCHK(hipEventRecord(ix->e1, ix->st));
-  KCHK(hipStreamSynchronize(ix->st));
+  VSX_HIP(vsx_kmer_launch_sweep(1, codes, off, len, d_list, ix->nseq, w, ix->ntiles, ix->d_count.p, ix->d_start.p, ix->d_post.p, vsx_internal_seqset_lower(ix->db), ix->st));
+  VSX_HIP(hipEventRecord(ix->e1, ix->st));
+  VSX_HIP(hipStreamSynchronize(ix->st));
   float ms = 0;
-  KCHK(hipEventElapsedTime(&ms, ix->e0, ix->e1));
+  VSX_HIP(hipEventElapsedTime(&ms, ix->e0, ix->e1));
   ix->stats.build_ms = ms;
   ix->stats.postings = entries;
   ix->stats.index_bytes = acc * 16 + (ix->nbuckets + 1) * 8;
@@ -340,53 +273,53 @@ int count_pass(VsxKmerIndex * ix, KmerScratch * sc, uint32_t nslots, uint32_t n8
                uint32_t keep, VsxKmerResult & out, std::vector<uint32_t> & overflow, uint32_t & overflow_max, float & ms_total)
 {
   const uint32_t nt = ix->ntiles;
-  KCHK(sc->d_rec.ensure((size_t) nslots * nt * subcap));
-  KCHK(sc->d_tilecnt.ensure((size_t) nslots * nt));
-  KCHK(sc->d_sel_mn.ensure(nslots));
-  KCHK(sc->d_sel_off.ensure(nslots));
+  VSX_HIP(sc->d_rec.ensure((size_t) nslots * nt * subcap));
+  VSX_HIP(sc->d_tilecnt.ensure((size_t) nslots * nt));
+  VSX_HIP(sc->d_sel_mn.ensure(nslots));
+  VSX_HIP(sc->d_sel_off.ensure(nslots));
   const bool pre = n8 && !ix->tagged;                                             // the 8-bit class of an untagged index: ranges pre-pass
   const int tg = ix->tagged ? 1 : (ix->packed ? 2 : 0);                           // the postings format (vsx_kmer_launch_count)
-  if (pre) KCHK(sc->d_ranges.ensure((size_t) n8 * nt * 256));
-  KCHK(hipEventRecord(sc->e0, sc->st));
+  if (pre) VSX_HIP(sc->d_ranges.ensure((size_t) n8 * nt * 256));
+  VSX_HIP(hipEventRecord(sc->e0, sc->st));
   if (pre)
-    KCHK(vsx_kmer_launch_ranges(ix->d_start.p, nt, sc->d_qk_start.p, sc->d_qk.p, sc->d_minmatch.p, d_qlist, n8, sc->d_ranges.p, sc->st));
+    VSX_HIP(vsx_kmer_launch_ranges(ix->d_start.p, nt, sc->d_qk_start.p, sc->d_qk.p, sc->d_minmatch.p, d_qlist, n8, sc->d_ranges.p, sc->st));
   // Counting kernels of concurrent batches take turns in arrival order: each fills the device on its own, so two at once only
   // finish BOTH late (the search's windows then reach the aligner in pairs and its last stage starts later); uploads, ranges,
   // selection and downloads of the other batch still overlap.
   std::unique_lock<std::mutex> turn(ix->turn_mu);
-  if (ix->turn_ev) KCHK(hipStreamWaitEvent(sc->st, ix->turn_ev, 0));
-  KCHK(vsx_kmer_launch_count(8, tg, ix->d_post.p, ix->d_start.p, pre ? sc->d_ranges.p : nullptr, nt, ix->nseq, n8, 0, sc->d_qk_start.p, sc->d_qk.p,
+  if (ix->turn_ev) VSX_HIP(hipStreamWaitEvent(sc->st, ix->turn_ev, 0));
+  VSX_HIP(vsx_kmer_launch_count(8, tg, ix->d_post.p, ix->d_start.p, pre ? sc->d_ranges.p : nullptr, nt, ix->nseq, n8, 0, sc->d_qk_start.p, sc->d_qk.p,
                              sc->d_minmatch.p, d_qlist, sc->d_rec.p, subcap, sc->d_tilecnt.p, sc->st));
-  KCHK(vsx_kmer_launch_count(16, tg, ix->d_post.p, ix->d_start.p, nullptr, nt, ix->nseq, nslots - n8, n8, sc->d_qk_start.p, sc->d_qk.p,
+  VSX_HIP(vsx_kmer_launch_count(16, tg, ix->d_post.p, ix->d_start.p, nullptr, nt, ix->nseq, nslots - n8, n8, sc->d_qk_start.p, sc->d_qk.p,
                              sc->d_minmatch.p, d_qlist, sc->d_rec.p + (size_t) n8 * nt * subcap, subcap, sc->d_tilecnt.p + (size_t) n8 * nt, sc->st));
-  KCHK(hipEventRecord(sc->e_turn, sc->st));
+  VSX_HIP(hipEventRecord(sc->e_turn, sc->st));
   ix->turn_ev = sc->e_turn;
   turn.unlock();
   uint64_t capacity = std::max<uint64_t>(sc->d_dense.n, std::max<uint64_t>(1u << 20, (uint64_t) nslots * 128));
   unsigned long long produced = 0;
   for (int attempt = 0; attempt < 2; ++attempt)
     {
-      KCHK(sc->d_dense.ensure(capacity));
-      KCHK(hipMemsetAsync(sc->d_cursor.p, 0, sizeof(unsigned long long), sc->st));
-      KCHK((ix->packed ? vsx_kmer_launch_select_packed : vsx_kmer_launch_select)(sc->d_rec.p, subcap, nt, sc->d_tilecnt.p, nslots, keep, sc->d_dense.p,
+      VSX_HIP(sc->d_dense.ensure(capacity));
+      VSX_HIP(hipMemsetAsync(sc->d_cursor.p, 0, sizeof(unsigned long long), sc->st));
+      VSX_HIP((ix->packed ? vsx_kmer_launch_select_packed : vsx_kmer_launch_select)(sc->d_rec.p, subcap, nt, sc->d_tilecnt.p, nslots, keep, sc->d_dense.p,
                                                                                   sc->d_cursor.p, sc->d_dense.n, sc->d_sel_mn.p, sc->d_sel_off.p, sc->st));
-      KCHK(hipEventRecord(sc->e1, sc->st));
-      KCHK(hipMemcpyAsync(&produced, sc->d_cursor.p, sizeof produced, hipMemcpyDeviceToHost, sc->st));
-      KCHK(hipStreamSynchronize(sc->st));
+      VSX_HIP(hipEventRecord(sc->e1, sc->st));
+      VSX_HIP(hipMemcpyAsync(&produced, sc->d_cursor.p, sizeof produced, hipMemcpyDeviceToHost, sc->st));
+      VSX_HIP(hipStreamSynchronize(sc->st));
       if (produced <= sc->d_dense.n) break;
       capacity = produced;
       if (attempt == 1) { vsx_internal_set_error("vsx_kmer_count_batch: selection buffer overflow"); return VSX_EHIP; }
     }
   float ms = 0;
-  KCHK(hipEventElapsedTime(&ms, sc->e0, sc->e1));
+  VSX_HIP(hipEventElapsedTime(&ms, sc->e0, sc->e1));
   ms_total += ms;
   std::vector<uint64_t> mn(nslots), off(nslots);
-  KCHK(hipMemcpy(mn.data(), sc->d_sel_mn.p, (size_t) nslots * 8, hipMemcpyDeviceToHost));
-  KCHK(hipMemcpy(off.data(), sc->d_sel_off.p, (size_t) nslots * 8, hipMemcpyDeviceToHost));
+  VSX_HIP(hipMemcpy(mn.data(), sc->d_sel_mn.p, (size_t) nslots * 8, hipMemcpyDeviceToHost));
+  VSX_HIP(hipMemcpy(off.data(), sc->d_sel_off.p, (size_t) nslots * 8, hipMemcpyDeviceToHost));
   // the dense buffer is already grouped by slot: append it wholesale and record each query's range
   const size_t before = out.rec.size();
   out.rec.resize(before + produced);
-  if (produced) KCHK(hipMemcpy(out.rec.data() + before, sc->d_dense.p, produced * 8, hipMemcpyDeviceToHost));
+  if (produced) VSX_HIP(hipMemcpy(out.rec.data() + before, sc->d_dense.p, produced * 8, hipMemcpyDeviceToHost));
   for (uint32_t s = 0; s < nslots; ++s)
     {
       const uint32_t m = (uint32_t) (mn[s] & 0xffffffffu), n = (uint32_t) (mn[s] >> 32);
@@ -431,7 +364,7 @@ int vsx_kmer_count_batch(VsxKmerIndex * ix, uint64_t nq, const uint64_t * qk_sta
   if (!ix || (nq && (!qk_start || !minmatch))) { vsx_internal_set_error("vsx_kmer_count_batch: null argument"); return VSX_EINVAL; }
   if (nq == 0 || ix->nseq == 0) return VSX_OK;
   if (nq >= (1ull << 22)) { vsx_internal_set_error("vsx_kmer_count_batch: at most 4 M queries per batch"); return VSX_EINVAL; }
-  KCHK(hipSetDevice(ix->device));
+  VSX_HIP(hipSetDevice(ix->device));
   // a free scratch set, or a new one, or wait for one
   ScratchLease lease {ix, nullptr};
   {
@@ -462,12 +395,12 @@ int vsx_kmer_count_batch(VsxKmerIndex * ix, uint64_t nq, const uint64_t * qk_sta
       else streamed_bytes = increments * (ix->tagged ? 4 : 2);
     }
   sc->records = 0;
-  KCHK(sc->d_qk_start.ensure(nq + 1));
-  KCHK(sc->d_qk.ensure(nk));
-  KCHK(sc->d_minmatch.ensure(nq));
-  KCHK(hipMemcpyAsync(sc->d_qk_start.p, qk_start, (nq + 1) * 8, hipMemcpyHostToDevice, sc->st));
-  if (nk) KCHK(hipMemcpyAsync(sc->d_qk.p, qk, nk * 4, hipMemcpyHostToDevice, sc->st));
-  KCHK(hipMemcpyAsync(sc->d_minmatch.p, minmatch, nq * 4, hipMemcpyHostToDevice, sc->st));
+  VSX_HIP(sc->d_qk_start.ensure(nq + 1));
+  VSX_HIP(sc->d_qk.ensure(nk));
+  VSX_HIP(sc->d_minmatch.ensure(nq));
+  VSX_HIP(hipMemcpyAsync(sc->d_qk_start.p, qk_start, (nq + 1) * 8, hipMemcpyHostToDevice, sc->st));
+  if (nk) VSX_HIP(hipMemcpyAsync(sc->d_qk.p, qk, nk * 4, hipMemcpyHostToDevice, sc->st));
+  VSX_HIP(hipMemcpyAsync(sc->d_minmatch.p, minmatch, nq * 4, hipMemcpyHostToDevice, sc->st));
   float ms = 0;
   std::vector<uint32_t> overflow;
   uint32_t overflow_max = 0;
@@ -508,14 +441,14 @@ int vsx_kmer_count_batch(VsxKmerIndex * ix, uint64_t nq, const uint64_t * qk_sta
   auto run_subset = [&](const std::vector<uint32_t> * subset, uint32_t subcap, std::vector<uint32_t> & over, uint32_t & over_max) -> int {
     std::vector<uint32_t> ordered;
     uint32_t n8 = 0;
-    Buf<uint32_t> d_list;
+    DevBuf<uint32_t> d_list;
     const uint32_t n = subset ? (uint32_t) subset->size() : (uint32_t) nq;
     const std::vector<uint32_t> * list = subset;
     if (by_class(subset, ordered, n8)) list = &ordered;
     if (list)
       {
-        KCHK(d_list.alloc(list->size()));
-        KCHK(hipMemcpyAsync(d_list.p, list->data(), list->size() * 4, hipMemcpyHostToDevice, sc->st));
+        VSX_HIP(d_list.alloc(list->size()));
+        VSX_HIP(hipMemcpyAsync(d_list.p, list->data(), list->size() * 4, hipMemcpyHostToDevice, sc->st));
       }
     return count_pass(ix, sc, n, n8, list ? d_list.p : nullptr, list, subcap, keep, out, over, over_max, ms);
   };

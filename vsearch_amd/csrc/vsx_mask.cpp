@@ -12,7 +12,7 @@
 // The result is TEXT with the reference's case convention, so the rest of the library treats a dust-masked set exactly like
 // a soft-masked one (vsx_search_opts.soft_mask).  The device version (vsx_mask.hip) produces the same intervals as bits.
 #include "../../include/vsx_search.h"
-#include "vsx_internal.h"
+#include "vsx_private.h"
 
 #include <algorithm>
 #include <atomic>
@@ -20,9 +20,6 @@
 #include <string>
 #include <thread>
 #include <vector>
-
-extern "C" void vsx_internal_set_error(const char * msg);
-extern "C" int vsx_internal_usable_cpus(void);
 
 namespace {
 
@@ -122,8 +119,8 @@ extern "C" {
 
 int vsx_dust_mask(char * blob, uint64_t n, const uint64_t * offsets, const uint32_t * lengths, int32_t threads)
 {
-  if (n && (!blob || !offsets || !lengths)) { vsx_internal_set_error("vsx_dust_mask: null argument"); return VSX_EINVAL; }
-  int nth = threads > 0 ? threads : vsx_internal_usable_cpus();
+  if (n && (!blob || !offsets || !lengths)) return vsxp::fail(VSX_EINVAL, "vsx_dust_mask: null argument");
+  int nth = threads > 0 ? threads : vsxp::usable_cpus();
   if ((uint64_t) nth > n / 64 + 1) nth = (int) (n / 64 + 1);
   std::atomic<uint64_t> next {0};
   auto work = [&]() {

@@ -13,7 +13,6 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -23,23 +22,18 @@
 #include <vector>
 
 #include "vsx_merge_internal.h"
+#include "vsx_private.h"
 
 #pragma clang fp contract(off)
 
-extern "C" void vsx_internal_set_error(const char * msg);
-extern "C" int vsx_internal_device(const vsx_ctx * ctx);
-extern "C" hipError_t vsx_launch_merge(const VsxMergeItem * d_items, uint32_t n_items, const uint8_t * d_blob, VsxMergeParams P,
-                                       VsxMergeDevRec * d_recs, uint8_t * d_oseq, uint8_t * d_oqual, hipStream_t st);
+using vsxp::fail;
+using vsxp::now_s;
+using vsxp::DevBuf;
+using vsxp::PinnedBuf;
 
 namespace {
 
 thread_local vsx_merge_stats g_stats {};
-
-int mfail(int code, const std::string & msg) { vsx_internal_set_error(msg.c_str()); return code; }
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-#define MHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-  return mfail(e_ == hipErrorOutOfMemory ? VSX_ENOMEM : VSX_EHIP, std::string("vsx_merge_pairs: ") + #call + ": " + hipGetErrorString(e_)); } while (0)
 
 // ---- tables ---------------------------------------------------------------------------------------------------------------
 struct Tables {
@@ -258,33 +252,24 @@ int quality_failure(const vsx_merge_opts & o, const QualError & e)
     std::snprintf(msg, sizeof msg, "vsx_merge_pairs: FASTQ quality value (%d) below qmin (%lld)", e.value, (long long) o.fastq_qmin);
   else
     std::snprintf(msg, sizeof msg, "vsx_merge_pairs: FASTQ quality value (%d) above qmax (%lld)", e.value, (long long) o.fastq_qmax);
-  return mfail(VSX_EINVAL, msg);
+  return fail(VSX_EINVAL, "%s", msg);
 }
 
 // ---- the window pipeline ----------------------------------------------------------------------------------------------------
 struct Slot {
   hipStream_t st = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  uint8_t * h_in = nullptr, * h_out = nullptr, * d_in = nullptr, * d_out = nullptr;     // in: items + blob; out: recs + seq + qual
-  uint64_t in_cap = 0, out_cap = 0;
+  PinnedBuf<uint8_t> h_in, h_out;                            // in: items + blob; out: recs + seq + qual
+  DevBuf<uint8_t> d_in, d_out;                               // (each as large as its pinned twin)
   uint64_t w0 = 0, n = 0, blob_off = 0, out_bytes = 0;       // the window in flight
   bool busy = false;
   ~Slot()
   {
     if (st) (void) hipStreamSynchronize(st);
-    if (h_in) (void) hipHostFree(h_in);
-    if (h_out) (void) hipHostFree(h_out);
-    if (d_in) (void) hipFree(d_in);
-    if (d_out) (void) hipFree(d_out);
     if (ev0) (void) hipEventDestroy(ev0);
     if (ev1) (void) hipEventDestroy(ev1);
     if (st) (void) hipStreamDestroy(st);
   }
-};
-
-struct DevTables {
-  void * p = nullptr;
-  ~DevTables() { if (p) (void) hipFree(p); }
 };
 
 uint64_t align16(uint64_t v) { return (v + 15) & ~(uint64_t) 15; }
@@ -297,25 +282,19 @@ struct Inputs {
 
 int reserve_slot(Slot & s, uint64_t in_bytes, uint64_t out_bytes)
 {
-  if (in_bytes > s.in_cap)
+  if (!s.d_in.p || in_bytes > s.d_in.n)
     {
-      if (s.h_in) (void) hipHostFree(s.h_in);
-      if (s.d_in) (void) hipFree(s.d_in);
-      s.h_in = nullptr; s.d_in = nullptr; s.in_cap = 0;
+      s.h_in.release(); s.d_in.release();
       const uint64_t want = in_bytes + (in_bytes >> 3);
-      MHIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_in), want, hipHostMallocDefault));
-      MHIP(hipMalloc(reinterpret_cast<void **>(&s.d_in), want));
-      s.in_cap = want;
+      VSX_HIP_AS("vsx_merge_pairs", s.h_in.alloc(want));
+      VSX_HIP_AS("vsx_merge_pairs", s.d_in.alloc(want));
     }
-  if (out_bytes > s.out_cap)
+  if (!s.d_out.p || out_bytes > s.d_out.n)
     {
-      if (s.h_out) (void) hipHostFree(s.h_out);
-      if (s.d_out) (void) hipFree(s.d_out);
-      s.h_out = nullptr; s.d_out = nullptr; s.out_cap = 0;
+      s.h_out.release(); s.d_out.release();
       const uint64_t want = out_bytes + (out_bytes >> 3);
-      MHIP(hipHostMalloc(reinterpret_cast<void **>(&s.h_out), want, hipHostMallocDefault));
-      MHIP(hipMalloc(reinterpret_cast<void **>(&s.d_out), want));
-      s.out_cap = want;
+      VSX_HIP_AS("vsx_merge_pairs", s.h_out.alloc(want));
+      VSX_HIP_AS("vsx_merge_pairs", s.d_out.alloc(want));
     }
   return VSX_OK;
 }
@@ -333,8 +312,8 @@ int submit_window(Slot & s, const Inputs & in, const VsxMergeParams & P, uint64_
   outb = align16(outb);
   const int rc = reserve_slot(s, items_bytes + blob + 16, recs_bytes + 2 * outb + 16);
   if (rc != VSX_OK) return rc;
-  VsxMergeItem * items = reinterpret_cast<VsxMergeItem *>(s.h_in);
-  uint8_t * hb = s.h_in + items_bytes;
+  VsxMergeItem * items = reinterpret_cast<VsxMergeItem *>(s.h_in.p);
+  uint8_t * hb = s.h_in.p + items_bytes;
   uint64_t bo = 0, oo = 0;
   for (uint64_t k = w0; k < w0 + n; ++k)
     {
@@ -349,12 +328,12 @@ int submit_window(Slot & s, const Inputs & in, const VsxMergeParams & P, uint64_
       oo += (uint64_t) F + R;
     }
   s.w0 = w0; s.n = n; s.blob_off = items_bytes; s.out_bytes = recs_bytes + 2 * outb;
-  MHIP(hipMemcpyAsync(s.d_in, s.h_in, items_bytes + blob, hipMemcpyHostToDevice, s.st));
-  MHIP(hipEventRecord(s.ev0, s.st));
-  MHIP(vsx_launch_merge(reinterpret_cast<const VsxMergeItem *>(s.d_in), (uint32_t) n, s.d_in + items_bytes, P,
-                        reinterpret_cast<VsxMergeDevRec *>(s.d_out), s.d_out + recs_bytes, s.d_out + recs_bytes + outb, s.st));
-  MHIP(hipEventRecord(s.ev1, s.st));
-  MHIP(hipMemcpyAsync(s.h_out, s.d_out, s.out_bytes, hipMemcpyDeviceToHost, s.st));
+  VSX_HIP_AS("vsx_merge_pairs", hipMemcpyAsync(s.d_in.p, s.h_in.p, items_bytes + blob, hipMemcpyHostToDevice, s.st));
+  VSX_HIP_AS("vsx_merge_pairs", hipEventRecord(s.ev0, s.st));
+  VSX_HIP_AS("vsx_merge_pairs", vsx_launch_merge(reinterpret_cast<const VsxMergeItem *>(s.d_in.p), (uint32_t) n, s.d_in.p + items_bytes, P,
+                        reinterpret_cast<VsxMergeDevRec *>(s.d_out.p), s.d_out.p + recs_bytes, s.d_out.p + recs_bytes + outb, s.st));
+  VSX_HIP_AS("vsx_merge_pairs", hipEventRecord(s.ev1, s.st));
+  VSX_HIP_AS("vsx_merge_pairs", hipMemcpyAsync(s.h_out.p, s.d_out.p, s.out_bytes, hipMemcpyDeviceToHost, s.st));
   s.busy = true;
   g_stats.seconds_stage += now_s() - t0;
   return VSX_OK;
@@ -364,16 +343,16 @@ int submit_window(Slot & s, const Inputs & in, const VsxMergeParams & P, uint64_
 int collect_window(Slot & s, const Inputs & in, const HostParams & H, const Tables & T, OutBuilder & ob)
 {
   const double t0 = now_s();
-  MHIP(hipStreamSynchronize(s.st));
+  VSX_HIP_AS("vsx_merge_pairs", hipStreamSynchronize(s.st));
   s.busy = false;
   float ms = 0.f;
-  MHIP(hipEventElapsedTime(&ms, s.ev0, s.ev1));
+  VSX_HIP_AS("vsx_merge_pairs", hipEventElapsedTime(&ms, s.ev0, s.ev1));
   g_stats.seconds_kernel += ms * 1e-3;
-  const VsxMergeItem * items = reinterpret_cast<const VsxMergeItem *>(s.h_in);
-  const VsxMergeDevRec * recs = reinterpret_cast<const VsxMergeDevRec *>(s.h_out);
+  const VsxMergeItem * items = reinterpret_cast<const VsxMergeItem *>(s.h_in.p);
+  const VsxMergeDevRec * recs = reinterpret_cast<const VsxMergeDevRec *>(s.h_out.p);
   const uint64_t recs_bytes = align16(s.n * sizeof(VsxMergeDevRec));
   const uint64_t outb = (s.out_bytes - recs_bytes) / 2;
-  const char * oseq = reinterpret_cast<const char *>(s.h_out + recs_bytes), * oqual = oseq + outb;
+  const char * oseq = reinterpret_cast<const char *>(s.h_out.p + recs_bytes), * oqual = oseq + outb;
   std::string mseq, mqual;
   for (uint64_t j = 0; j < s.n; ++j)
     {
@@ -387,13 +366,13 @@ int collect_window(Slot & s, const Inputs & in, const HostParams & H, const Tabl
             return quality_failure(H.o, e);
           ++g_stats.pairs_host;
           g_stats.diagonals_scored += (uint64_t) d.ndiag;
-          if (!ob.put(k, d, mseq.data(), mqual.data())) return mfail(VSX_ENOMEM, "vsx_merge_pairs: out of memory");
+          if (!ob.put(k, d, mseq.data(), mqual.data())) return fail(VSX_ENOMEM, "vsx_merge_pairs: out of memory");
           continue;
         }
       const VsxMergeDevRec & d = recs[j];
       if (d.qerr) { QualError e; e.kind = d.qerr; e.value = d.qerr_value; return quality_failure(H.o, e); }
       g_stats.diagonals_scored += (uint64_t) d.ndiag;
-      if (!ob.put(k, d, oseq + items[j].out_off, oqual + items[j].out_off)) return mfail(VSX_ENOMEM, "vsx_merge_pairs: out of memory");
+      if (!ob.put(k, d, oseq + items[j].out_off, oqual + items[j].out_off)) return fail(VSX_ENOMEM, "vsx_merge_pairs: out of memory");
     }
   g_stats.seconds_unpack += now_s() - t0;
   return VSX_OK;
@@ -439,11 +418,11 @@ int vsx_merge_pairs(vsx_ctx * ctx, const vsx_merge_opts * opts, uint64_t n,
   g_stats = vsx_merge_stats {};
   const double t_begin = now_s();
   if (!opts || !out || (n && (!fwd_seq || !fwd_qual || !fwd_off || !fwd_len || !rev_seq || !rev_qual || !rev_off || !rev_len)))
-    return mfail(VSX_EINVAL, "vsx_merge_pairs: null argument");
+    return fail(VSX_EINVAL, "vsx_merge_pairs: null argument");
   std::memset(out, 0, sizeof *out);
   const char * env = std::getenv("VSX_MERGE");
   const bool host_all = env && std::strcmp(env, "host") == 0;
-  if (!ctx && !host_all) return mfail(VSX_EINVAL, "vsx_merge_pairs: no context (only VSX_MERGE=host runs without one)");
+  if (!ctx && !host_all) return fail(VSX_EINVAL, "vsx_merge_pairs: no context (only VSX_MERGE=host runs without one)");
 
   HostParams H;
   H.o = *opts;
@@ -455,10 +434,10 @@ int vsx_merge_pairs(vsx_ctx * ctx, const vsx_merge_opts * opts, uint64_t n,
   if (o.fastq_ascii < 0 || o.fastq_ascii > 127 || o.fastq_qmin > o.fastq_qmax || o.fastq_qminout > o.fastq_qmaxout ||
       o.fastq_ascii + o.fastq_qmin < 0 || o.fastq_ascii + o.fastq_qmax > 127 ||
       o.fastq_ascii + o.fastq_qminout < 0 || o.fastq_ascii + o.fastq_qmaxout > 127)
-    return mfail(VSX_EINVAL, "vsx_merge_pairs: the quality offset plus qmin / qmax / qminout / qmaxout must lie within 0..127");
+    return fail(VSX_EINVAL, "vsx_merge_pairs: the quality offset plus qmin / qmax / qminout / qmaxout must lie within 0..127");
   for (uint64_t k = 0; k < n; ++k)
     if (fwd_off[k] + fwd_len[k] > fwd_bytes || rev_off[k] + rev_len[k] > rev_bytes)
-      return mfail(VSX_EINVAL, "vsx_merge_pairs: a read exceeds its blob");
+      return fail(VSX_EINVAL, "vsx_merge_pairs: a read exceeds its blob");
 
   Tables T;
   build_tables(o, T);
@@ -466,7 +445,7 @@ int vsx_merge_pairs(vsx_ctx * ctx, const vsx_merge_opts * opts, uint64_t n,
               reinterpret_cast<const uint8_t *>(rev_seq), reinterpret_cast<const uint8_t *>(rev_qual), fwd_off, rev_off, fwd_len, rev_len };
   OutBuilder ob;
   ob.rec = static_cast<vsx_merge_record *>(std::calloc(std::max<uint64_t>(n, 1), sizeof(vsx_merge_record)));
-  if (!ob.rec || !ob.room(1)) return mfail(VSX_ENOMEM, "vsx_merge_pairs: out of memory");
+  if (!ob.rec || !ob.room(1)) return fail(VSX_ENOMEM, "vsx_merge_pairs: out of memory");
   g_stats.pairs = n;
 
   if (host_all)
@@ -480,13 +459,13 @@ int vsx_merge_pairs(vsx_ctx * ctx, const vsx_merge_opts * opts, uint64_t n,
                                d, mseq, mqual, e))
             return quality_failure(o, e);
           g_stats.diagonals_scored += (uint64_t) d.ndiag;
-          if (!ob.put(k, d, mseq.data(), mqual.data())) return mfail(VSX_ENOMEM, "vsx_merge_pairs: out of memory");
+          if (!ob.put(k, d, mseq.data(), mqual.data())) return fail(VSX_ENOMEM, "vsx_merge_pairs: out of memory");
         }
       g_stats.pairs_host = n;
     }
   else
     {
-      MHIP(hipSetDevice(vsx_internal_device(ctx)));
+      VSX_HIP_AS("vsx_merge_pairs", hipSetDevice(vsx_internal_device(ctx)));
       // device tables: the square over the symbols this call can meet
       const int tlo = (int) std::min(o.fastq_ascii + o.fastq_qmin, o.fastq_ascii), thi = (int) std::max(o.fastq_ascii + o.fastq_qmax, o.fastq_ascii);
       const int D = thi - tlo + 1;
@@ -501,25 +480,25 @@ int vsx_merge_pairs(vsx_ctx * ctx, const vsx_merge_opts * opts, uint64_t n,
             h_match[d] = T.match[s]; h_mism[d] = T.mism[s]; h_same[d] = T.same[s]; h_diff[d] = T.diff[s];
           }
       std::memcpy(h_q2p, T.q2p, sizeof T.q2p);
-      DevTables dt;
-      MHIP(hipMalloc(&dt.p, ht.size()));
-      MHIP(hipMemcpy(dt.p, ht.data(), ht.size(), hipMemcpyHostToDevice));
+      DevBuf<uint8_t> dt;
+      VSX_HIP_AS("vsx_merge_pairs", dt.alloc(ht.size()));
+      VSX_HIP_AS("vsx_merge_pairs", hipMemcpy(dt.p, ht.data(), ht.size(), hipMemcpyHostToDevice));
       VsxMergeParams P {};
       P.truncqual = o.fastq_truncqual; P.maxns = o.fastq_maxns; P.minlen = o.fastq_minlen; P.maxlen = o.fastq_maxlen;
       P.minovlen = o.fastq_minovlen; P.maxdiffs = o.fastq_maxdiffs; P.minmergelen = o.fastq_minmergelen; P.maxmergelen = o.fastq_maxmergelen;
       P.maxdiffpct = o.fastq_maxdiffpct; P.maxee = o.fastq_maxee; P.minscore = H.minscore;
       P.ascii = (int32_t) o.fastq_ascii; P.qmin = (int32_t) o.fastq_qmin; P.qmax = (int32_t) o.fastq_qmax;
       P.mindiagcount = H.mindiagcount; P.allowstagger = o.fastq_allowmergestagger ? 1 : 0; P.tlo = tlo; P.tdim = D;
-      P.match = static_cast<const double *>(dt.p); P.mism = P.match + dd; P.q2p = P.mism + dd;
+      P.match = reinterpret_cast<const double *>(dt.p); P.mism = P.match + dd; P.q2p = P.mism + dd;
       P.qual_same = reinterpret_cast<const uint8_t *>(P.q2p + 128); P.qual_diff = P.qual_same + dd16;
 
       const uint64_t window = o.window > 0 ? (uint64_t) o.window : 32768;
       Slot slot[2];
       for (Slot & s : slot)
         {
-          MHIP(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-          MHIP(hipEventCreate(&s.ev0));
-          MHIP(hipEventCreate(&s.ev1));
+          VSX_HIP_AS("vsx_merge_pairs", hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+          VSX_HIP_AS("vsx_merge_pairs", hipEventCreate(&s.ev0));
+          VSX_HIP_AS("vsx_merge_pairs", hipEventCreate(&s.ev1));
         }
       uint64_t w = 0;
       for (uint64_t w0 = 0; w0 < n; w0 += window, ++w)

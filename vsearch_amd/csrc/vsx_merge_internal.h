@@ -3,6 +3,7 @@
 #define VSX_MERGE_INTERNAL_H
 
 #include <stdint.h>
+#include <hip/hip_runtime_api.h>
 #include "../../include/vsx_merge.h"
 
 #define VSX_MERGE_THREADS 64          // one wavefront per pair
@@ -37,6 +38,13 @@ struct VsxMergeDevRec {
   int32_t ndiag;                      // diagonals scored
   double  ee_merged, ee_fwd, ee_rev;
 };
+
+// vsx_merge.hip: one wavefront per item; items with host == 1 are skipped
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t vsx_launch_merge(const VsxMergeItem * d_items, uint32_t n_items, const uint8_t * d_blob, VsxMergeParams P,
+                            VsxMergeDevRec * d_recs, uint8_t * d_oseq, uint8_t * d_oqual, hipStream_t st);
 
 #ifdef __HIPCC__
 #define VSX_MG_HD __host__ __device__ inline

@@ -13,22 +13,16 @@
 //   compute_and_print_consensus (:429-500) -> vsx_msa_consensus_kernel, one lane per column
 // O(rows x alnlen) byte work, HBM/latency bound; nothing here is GEMM shaped.
 #include "../../include/vsx_search.h"
+#include "vsx_private.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <thread>
 #include <vector>
-
-extern "C" void vsx_internal_set_error(const char * msg);
-extern "C" int vsx_internal_device(const vsx_ctx * ctx);
-extern "C" hipStream_t vsx_internal_stream(const vsx_ctx * ctx);
-extern "C" int vsx_internal_usable_cpus(void);
-extern "C" const char * vsx_last_error(void);
 
 namespace {
 
@@ -142,25 +136,13 @@ __global__ __launch_bounds__(256) void vsx_msa_consensus_kernel(const MsaCluster
   crow[i] = best >= p[5] ? (uint8_t) sym4[best_sym] : (uint8_t) '-';
 }
 
-int mfail(int code, const char * what, hipError_t e)
-{
-  std::string m = std::string(what) + ": " + hipGetErrorString(e);
-  vsx_internal_set_error(m.c_str());
-  return code;
-}
-int minval(const char * what) { vsx_internal_set_error(what); return VSX_EINVAL; }
 
-struct DevBuf {
-  void * p = nullptr;
-  ~DevBuf() { if (p) (void) hipFree(p); }
-};
-
-#define MCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return mfail(e_ == hipErrorOutOfMemory ? VSX_ENOMEM : VSX_EHIP, #x, e_); } while (0)
+using DevBuf = vsxp::DevBuf<uint8_t>;
 
 template <typename T> int upload(DevBuf & b, const std::vector<T> & v, hipStream_t st)
 {
-  MCHK(hipMalloc(&b.p, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  if (!v.empty()) MCHK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  VSX_HIP(b.alloc(std::max<size_t>(v.size(), 1) * sizeof(T)));
+  if (!v.empty()) VSX_HIP(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
   return VSX_OK;
 }
 
@@ -169,7 +151,7 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
               const char * const * cigars, const uint64_t * abundances, vsx_msa_out * outs)
 {
   const bool dbg = std::getenv("VSX_DEBUG_TIMING") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const auto now = vsxp::now_s;
   const double t_0 = now();
   std::vector<MsaRow> rows;
   std::vector<MsaRun> runs;
@@ -185,7 +167,7 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
   for (uint32_t c = c0; c < c1; ++c)
     {
       const uint64_t m0 = cstart[c], m1 = cstart[c + 1];
-      if (m1 <= m0) return minval("vsx_msa_device: empty cluster");
+      if (m1 <= m0) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: empty cluster");
       const uint64_t n = m1 - m0;
       const uint32_t clen = lens[m0];
       const size_t run_first = runs.size();
@@ -202,7 +184,7 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
       for (uint64_t i = m0 + 1; i < m1; ++i)
         {
           const char * cg = cigars[i];
-          if (!cg || !seqs[i]) return minval("vsx_msa_device: member without CIGAR or sequence");
+          if (!cg || !seqs[i]) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: member without CIGAR or sequence");
           MsaRow mr {};
           mr.seq = blob.size(); mr.run0 = (uint32_t) runs.size();
           uint64_t cpos = 0, spos = 0;
@@ -210,27 +192,27 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
           while (*cg)
             {
               uint64_t k = 0; bool any = false;
-              while (*cg >= '0' && *cg <= '9') { k = k * 10 + (uint64_t) (*cg - '0'); ++cg; any = true; if (k > 0xffffffffull) return minval("vsx_msa_device: run too long"); }
+              while (*cg >= '0' && *cg <= '9') { k = k * 10 + (uint64_t) (*cg - '0'); ++cg; any = true; if (k > 0xffffffffull) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: run too long"); }
               if (!*cg) break;
               const char op = *cg++;
               if (!any) k = 1;
               if (op == 'M')
                 {
-                  if (cpos + k > clen || spos + k > lens[i]) return minval("vsx_msa_device: CIGAR does not fit the sequences");
+                  if (cpos + k > clen || spos + k > lens[i]) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: CIGAR does not fit the sequences");
                   if (k) runs.push_back(MsaRun {(uint32_t) cpos, (uint32_t) spos, (uint32_t) k, 0});
                   cpos += k; spos += k; if (k) last_d = false;
                 }
-              else if (op == 'I') { if (cpos + k > clen) return minval("vsx_msa_device: CIGAR does not fit the sequences"); cpos += k; if (k) last_d = false; }
+              else if (op == 'I') { if (cpos + k > clen) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: CIGAR does not fit the sequences"); cpos += k; if (k) last_d = false; }
               else if (op == 'D')
                 {
-                  if (last_d) return minval("vsx_msa_device: adjacent 'D' runs");
-                  if (spos + k > lens[i]) return minval("vsx_msa_device: CIGAR does not fit the sequences");
+                  if (last_d) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: adjacent 'D' runs");
+                  if (spos + k > lens[i]) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: CIGAR does not fit the sequences");
                   if (k) runs.push_back(MsaRun {(uint32_t) cpos, (uint32_t) spos, (uint32_t) k, 1});
                   maxins[cpos] = std::max<uint32_t>(maxins[cpos], (uint32_t) k);
                   spos += k; last_d = true;
                 }
             }
-          if (cpos != clen) return minval("vsx_msa_device: CIGAR does not span the centroid");
+          if (cpos != clen) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: CIGAR does not span the centroid");
           mr.run1 = (uint32_t) runs.size();
           rows.push_back(mr);
           blob.insert(blob.end(), (const uint8_t *) seqs[i], (const uint8_t *) seqs[i] + lens[i]);
@@ -243,7 +225,7 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
       for (uint32_t k = 0; k <= clen; ++k)
         {
           p += maxins[k];
-          if (p > 0xfffffff0ull) return minval("vsx_msa_device: alignment too long");
+          if (p > 0xfffffff0ull) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: alignment too long");
           cols.push_back(make_uint2((uint32_t) p, maxins[k]));
           ++p;
         }
@@ -266,7 +248,7 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
       rows_bytes += (n + 1) * ((uint64_t) alnlen + 1);
       prof_count += (uint64_t) alnlen * 6;
     }
-  if (rows.size() > 0x7fffffffull || runs.size() > 0xffffffffull) return minval("vsx_msa_device: too many rows in one pass");
+  if (rows.size() > 0x7fffffffull || runs.size() > 0xffffffffull) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: too many rows in one pass");
 
   const double t_1 = now();
   DevBuf d_rows, d_runs, d_cols, d_blob, d_ab, d_tiles, d_cls, d_cbc, d_cb0, d_out, d_prof;
@@ -275,9 +257,9 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
       || (rc = upload(d_ab, ab, st)) || (rc = upload(d_tiles, tiles, st)) || (rc = upload(d_cls, cls, st)) || (rc = upload(d_cbc, cb_cluster, st))
       || (rc = upload(d_cb0, cb_col0, st)))
     return rc;
-  MCHK(hipMalloc(&d_out.p, std::max<uint64_t>(rows_bytes, 1)));
-  MCHK(hipMalloc(&d_prof.p, std::max<uint64_t>(prof_count, 1) * sizeof(uint64_t)));
-  MCHK(hipMemsetAsync(d_prof.p, 0, std::max<uint64_t>(prof_count, 1) * sizeof(uint64_t), st));
+  VSX_HIP(d_out.alloc(std::max<uint64_t>(rows_bytes, 1)));
+  VSX_HIP(d_prof.alloc(std::max<uint64_t>(prof_count, 1) * sizeof(uint64_t)));
+  VSX_HIP(hipMemsetAsync(d_prof.p, 0, std::max<uint64_t>(prof_count, 1) * sizeof(uint64_t), st));
   hipLaunchKernelGGL(vsx_msa_rows_kernel, dim3((unsigned) rows.size()), dim3(256), 0, st, (const MsaRow *) d_rows.p, (const MsaRun *) d_runs.p,
                      (const uint2 *) d_cols.p, (const uint8_t *) d_blob.p, (uint8_t *) d_out.p);
   if (!tiles.empty())
@@ -285,14 +267,14 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
                        (const uint64_t *) d_ab.p, (unsigned long long *) d_prof.p);
   hipLaunchKernelGGL(vsx_msa_consensus_kernel, dim3((unsigned) cb_cluster.size()), dim3(256), 0, st, (const MsaCluster *) d_cls.p,
                      (const uint32_t *) d_cbc.p, (const uint32_t *) d_cb0.p, (const unsigned long long *) d_prof.p, (uint8_t *) d_out.p);
-  MCHK(hipGetLastError());
-  if (dbg) MCHK(hipStreamSynchronize(st));
+  VSX_HIP(hipGetLastError());
+  if (dbg) VSX_HIP(hipStreamSynchronize(st));
   const double t_2 = now();
   std::vector<char> h_rows((size_t) rows_bytes);
   std::vector<uint64_t> h_prof((size_t) prof_count);
-  if (rows_bytes) MCHK(hipMemcpyAsync(h_rows.data(), d_out.p, rows_bytes, hipMemcpyDeviceToHost, st));
-  if (prof_count) MCHK(hipMemcpyAsync(h_prof.data(), d_prof.p, prof_count * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  MCHK(hipStreamSynchronize(st));
+  if (rows_bytes) VSX_HIP(hipMemcpyAsync(h_rows.data(), d_out.p, rows_bytes, hipMemcpyDeviceToHost, st));
+  if (prof_count) VSX_HIP(hipMemcpyAsync(h_prof.data(), d_prof.p, prof_count * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  VSX_HIP(hipStreamSynchronize(st));
   const double t_3 = now();
 
   for (uint32_t c = c0; c < c1; ++c)
@@ -304,7 +286,7 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
       o->rows = (char *) std::malloc(std::max<size_t>(rb, 1));
       o->profile = (uint64_t *) std::malloc(std::max<size_t>((size_t) mc.alnlen * 6, 1) * sizeof(uint64_t));
       o->consensus = (char *) std::malloc((size_t) mc.alnlen + 1);
-      if (!o->rows || !o->profile || !o->consensus) { vsx_internal_set_error("vsx_msa_device: out of host memory"); return VSX_ENOMEM; }
+      if (!o->rows || !o->profile || !o->consensus) return vsxp::fail(VSX_ENOMEM, "vsx_msa_device: out of host memory");
       std::memcpy(o->rows, h_rows.data() + mc.rows, rb);
       if (mc.alnlen) std::memcpy(o->profile, h_prof.data() + mc.prof, (size_t) mc.alnlen * 6 * sizeof(uint64_t));
       // the consensus sequence = the uncensored columns whose best count >= gap count (msa.cpp:474-492): every non-'-'
@@ -327,17 +309,17 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
 extern "C" int vsx_msa_device_batch(vsx_ctx * ctx, uint32_t n_clusters, const uint64_t * cluster_start, const char * const * seqs,
                                     const uint32_t * lens, const char * const * cigars, const uint64_t * abundances, vsx_msa_out * outs)
 {
-  if (!ctx || !cluster_start || !seqs || !lens || !cigars || !outs) return minval("vsx_msa_device_batch: null argument");
+  if (!ctx || !cluster_start || !seqs || !lens || !cigars || !outs) return vsxp::fail(VSX_EINVAL, "vsx_msa_device_batch: null argument");
   for (uint32_t c = 0; c < n_clusters; ++c) std::memset(&outs[c], 0, sizeof outs[c]);
   const int device = vsx_internal_device(ctx);
-  MCHK(hipSetDevice(device));
+  VSX_HIP(hipSetDevice(device));
   for (uint32_t c = 0; c < n_clusters; ++c)
-    if (cluster_start[c + 1] <= cluster_start[c]) return minval("vsx_msa_device_batch: empty cluster");
+    if (cluster_start[c + 1] <= cluster_start[c]) return vsxp::fail(VSX_EINVAL, "vsx_msa_device_batch: empty cluster");
   // The kernels are a few per cent of the call; CIGAR parsing, the PCIe copies and the per-cluster result buffers are host
   // work, so the clusters are split (by rows) over host threads, each driving its own stream through passes of bounded size
   // (estimate per cluster: rows x (centroid + longest member)).
   const uint64_t total_rows = n_clusters ? cluster_start[n_clusters] - cluster_start[0] : 0;
-  const int nth = (int) std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t) vsx_internal_usable_cpus(), total_rows / 16384, (uint64_t) n_clusters, 32}));
+  const int nth = (int) std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t) vsxp::usable_cpus(), total_rows / 16384, (uint64_t) n_clusters, 32}));
   const uint64_t budget = nth > 1 ? (1ull << 28) : (1ull << 30);
   std::vector<int> rcs((size_t) nth, VSX_OK);
   std::vector<std::string> msgs((size_t) nth);
@@ -396,7 +378,7 @@ extern "C" int vsx_msa_device_batch(vsx_ctx * ctx, uint32_t n_clusters, const ui
 extern "C" int vsx_msa_device(vsx_ctx * ctx, uint32_t n, const char * const * seqs, const uint32_t * lens, const char * const * cigars,
                               const uint64_t * abundances, vsx_msa_out * out)
 {
-  if (!out || n == 0) return minval("vsx_msa_device: null argument");
+  if (!out || n == 0) return vsxp::fail(VSX_EINVAL, "vsx_msa_device: null argument");
   const uint64_t start[2] = {0, n};
   return vsx_msa_device_batch(ctx, 1, start, seqs, lens, cigars, abundances, out);
 }

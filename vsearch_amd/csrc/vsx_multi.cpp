@@ -15,6 +15,7 @@
 //
 // The same device may be listed more than once (two replicas on one GPU): that is how the suite checks this file on a one-GPU box.
 #include "../../include/vsx_search.h"
+#include "vsx_private.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -24,7 +25,7 @@
 #include <thread>
 #include <vector>
 
-extern "C" void vsx_internal_set_error(const char * msg);
+using vsxp::fail;
 
 struct vsx_multi_searcher {
   struct Replica {
@@ -44,11 +45,7 @@ struct vsx_multi_searcher {
   }
 };
 
-extern "C" int vsx_internal_usable_cpus(void);
-
 namespace {
-
-int mfail(int code, const std::string & msg) { vsx_internal_set_error(msg.c_str()); return code; }
 
 // run fn(d) for every replica on a thread of its own; the first failure (by device order) is reported
 template <typename F>
@@ -66,7 +63,7 @@ int on_all(vsx_multi_searcher * m, F fn)
   run(0);
   for (auto & t : th) t.join();
   for (size_t d = 0; d < D; ++d)
-    if (rc[d] != VSX_OK) return mfail(rc[d], "device " + std::to_string(m->rep[d].device) + ": " + msg[d]);
+    if (rc[d] != VSX_OK) return fail(rc[d], "device %d: %s", m->rep[d].device, msg[d].c_str());
   return VSX_OK;
 }
 
@@ -82,7 +79,7 @@ int merge_hits(const std::vector<vsx_hits> & H, const std::vector<Source> & src,
   out->first = (uint64_t *) std::malloc((nq + 1) * sizeof(uint64_t));
   out->hit = (vsx_hit *) std::malloc(std::max<uint64_t>(n_hits, 1) * sizeof(vsx_hit));
   out->cigar_blob = (char *) std::malloc(std::max<uint64_t>(bytes, 1));
-  if (!out->first || !out->hit || !out->cigar_blob) { vsx_hits_free(out); return mfail(VSX_ENOMEM, "vsx_multi: out of memory"); }
+  if (!out->first || !out->hit || !out->cigar_blob) { vsx_hits_free(out); return fail(VSX_ENOMEM, "vsx_multi: out of memory"); }
   // the CIGAR blobs are concatenated as they are: offsets of part p shift by the bytes of the parts before it
   std::vector<uint64_t> blob_shift(H.size(), 0);
   uint64_t at = 0;
@@ -127,7 +124,7 @@ int vsx_multi_searcher_create(vsx_multi_searcher ** out, const vsx_scoring * sco
                               const vsx_search_opts * opts, uint64_t n, const char * blob, uint64_t blob_bytes,
                               const uint64_t * offsets, const uint32_t * lengths, const vsx_seq_meta * meta)
 {
-  if (!out || !scoring || !opts || n_devices < 1 || !devices) return mfail(VSX_EINVAL, "vsx_multi_searcher_create: null argument");
+  if (!out || !scoring || !opts || n_devices < 1 || !devices) return fail(VSX_EINVAL, "vsx_multi_searcher_create: null argument");
   *out = nullptr;
   std::unique_ptr<vsx_multi_searcher> m(new vsx_multi_searcher);
   m->rep.resize((size_t) n_devices);
@@ -140,7 +137,7 @@ int vsx_multi_searcher_create(vsx_multi_searcher ** out, const vsx_scoring * sco
   {
     //  the floor of 2 applies to the auto-detected budget only: an explicit `threads` is the caller's limit and is never raised
     const bool explicit_budget = ropts.threads > 0;
-    int budget = explicit_budget ? ropts.threads : vsx_internal_usable_cpus();
+    int budget = explicit_budget ? ropts.threads : vsxp::usable_cpus();
     if (budget <= 0) budget = 2;
     ropts.threads = std::max(explicit_budget ? 1 : 2, budget / n_devices);
   }
@@ -170,9 +167,9 @@ vsx_searcher * vsx_multi_searcher_replica(vsx_multi_searcher * m, int32_t k)
 int vsx_multi_search_batch(vsx_multi_searcher * m, uint64_t nq, const char * qblob, uint64_t qbytes, const uint64_t * qoff,
                            const uint32_t * qlen, const vsx_seq_meta * qmeta, vsx_hits * out)
 {
-  if (!m || !out || (nq && (!qblob || !qoff || !qlen))) return mfail(VSX_EINVAL, "vsx_multi_search_batch: null argument");
+  if (!m || !out || (nq && (!qblob || !qoff || !qlen))) return fail(VSX_EINVAL, "vsx_multi_search_batch: null argument");
   std::memset(out, 0, sizeof *out);
-  if (nq > 0xFFFFFFFFull) return mfail(VSX_EINVAL, "vsx_multi_search_batch: more than 2^32 - 1 queries (vsx_hit.query is 32 bits wide)");
+  if (nq > 0xFFFFFFFFull) return fail(VSX_EINVAL, "vsx_multi_search_batch: more than 2^32 - 1 queries (vsx_hit.query is 32 bits wide)");
   const size_t D = m->rep.size();
   // contiguous blocks: block d = [lo[d], lo[d + 1])
   std::vector<uint64_t> lo(D + 1, 0);
@@ -204,9 +201,9 @@ int vsx_multi_search_batch(vsx_multi_searcher * m, uint64_t nq, const char * qbl
 
 int vsx_multi_allpairs(vsx_multi_searcher * m, int32_t acceptall, uint64_t first, uint64_t count, vsx_hits * out)
 {
-  if (!m || !out) return mfail(VSX_EINVAL, "vsx_multi_allpairs: null argument");
+  if (!m || !out) return fail(VSX_EINVAL, "vsx_multi_allpairs: null argument");
   std::memset(out, 0, sizeof *out);
-  if (first > m->n_db || count > m->n_db - first) return mfail(VSX_EINVAL, "vsx_multi_allpairs: rows exceed the database");
+  if (first > m->n_db || count > m->n_db - first) return fail(VSX_EINVAL, "vsx_multi_allpairs: rows exceed the database");
   const size_t D = m->rep.size();
   // boustrophedon deal of the rows first .. first + count - 1 (ascending within a device, as vsx_allpairs_rows wants them)
   std::vector<std::vector<uint32_t>> rows(D);

@@ -1,0 +1,220 @@
+// vsx_private.h -- the private interface of libvsx's host layer: every function one file of this directory defines and another
+// calls (and that neither include/*.h, vsx_internal.h nor vsx_kmer.h declares), and the host helpers the files share.  Host-only
+// C++; the file that defines a function includes this header too, so a declaration that drifts from its definition does not compile.
+#ifndef VSX_PRIVATE_H
+#define VSX_PRIVATE_H
+
+#include "../../include/vsx_search.h"
+
+#include <hip/hip_runtime_api.h>
+#include <algorithm>
+#include <chrono>
+#include <cstdarg>
+#include <cstdio>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+extern "C" {
+
+// ---- vsx_host.cpp ------------------------------------------------------------------------------------------------------------
+// one thread-local error slot for the whole library (vsx_last_error)
+void vsx_internal_set_error(const char * msg);
+const vsx_scoring * vsx_internal_scoring(const vsx_ctx * ctx);
+int vsx_internal_device(const vsx_ctx * ctx);
+hipStream_t vsx_internal_stream(const vsx_ctx * ctx);
+// CPUs this process may really use: affinity mask, capped by a cgroup v2 CPU quota
+int vsx_internal_usable_cpus(void);
+// the library's host worker pool: fn(0) runs on the caller, which also helps with queued jobs while it waits
+void vsx_internal_run_threads(int nth, void (*fn)(int, void *), void * arg);
+// VSX_POISON=1 (debugging aid): every device block this library hands out is filled with 0xA5 first, so a read of memory nobody
+// has written gives the same junk in every run instead of whatever an earlier plan, index or process left there
+void vsx_internal_poison(void * p, size_t bytes);
+// device memory under pressure: every live context of the device drops the stream-ordered blocks no plan holds and frees its idle
+// pool.  Whoever meets hipErrorOutOfMemory calls this once and retries (vsxp::device_malloc does).  Returns the bytes released.
+uint64_t vsx_internal_memory_pressure(int device);
+// The big stream-ordered scratch blocks of a context (three checkpoint blocks, the traceback slab): their sizes, and a reservation
+// of at least those sizes.  A search runs its windows on several contexts of one device; a context that meets its first full
+// window in the middle of a warm search would pay the multi-GB hipMalloc there, so the searcher levels the contexts after a call.
+void vsx_internal_scratch_sizes(vsx_ctx * ctx, uint64_t out[4]);
+int vsx_internal_scratch_reserve(vsx_ctx * ctx, const uint64_t want[4]);
+// what the plans of a context asked for since the last reset: {checkpoint block, slab} bytes
+void vsx_internal_scratch_requests(vsx_ctx * ctx, uint64_t out[2], int reset);
+// what the checkpoint block of ONE plan of `ntasks` whole-wave tasks (a query of qlen rows against up to eight targets of tlen
+// columns) will ask for
+uint64_t vsx_internal_ckpt_bytes_estimate(const vsx_ctx * ctx, uint64_t ntasks, uint32_t qlen, uint32_t tlen);
+void vsx_internal_seqset_device(const vsx_seqset * s, const uint8_t ** codes, const uint64_t ** off, const uint32_t ** len, uint64_t * n);
+// host copies of the set's lengths (the k-mer index build of long words lays its key slots out by their running sum)
+const uint32_t * vsx_internal_seqset_host_lengths(const vsx_seqset * s);
+// soft_mask: the set also keeps the case bitmap its k-mer index honours
+// (mode 1: the bitmap is the input's case; mode 2: the input is upper-cased and DUST-masked on the device, vsx_mask.hip)
+int vsx_internal_seqset_create_cased(vsx_ctx * ctx, vsx_seqset ** out, uint64_t n, const char * blob, uint64_t blob_bytes,
+                                     const uint64_t * offsets, const uint32_t * lengths, int mode);
+// the set's case bitmap (soft masking) or NULL: an index over a set that has one leaves out every word over a lower-case symbol
+const uint8_t * vsx_internal_seqset_lower(const vsx_seqset * s);
+// the bitmap on the host: bit i of byte i / 8 = blob byte i is masked
+int vsx_internal_seqset_lower_download(const vsx_seqset * s, uint8_t * dst, uint64_t nbytes);
+
+// ---- vsx_search.cpp ----------------------------------------------------------------------------------------------------------
+// what vsx_chimera.cpp reads of a searcher: its context, options (weak_id clamped), unclamped scoring, database set and masked text
+vsx_ctx * vsx_internal_searcher_ctx(const vsx_searcher * S);
+const vsx_search_opts * vsx_internal_searcher_opts(const vsx_searcher * S);
+const vsx_scoring * vsx_internal_searcher_scoring(const vsx_searcher * S);
+const vsx_seqset * vsx_internal_searcher_dbset(const vsx_searcher * S);
+void vsx_internal_searcher_text(const vsx_searcher * S, const char ** blob, const uint64_t ** off, const uint32_t ** len);
+// chimera detection's part search: the parts searched as given with candidate heaps of `tophits` entries; the searcher's own heap
+// size is restored before returning
+int vsx_internal_search_parts(vsx_searcher * S, int64_t tophits, uint64_t nq, const char * qblob, uint64_t qbytes,
+                              const uint64_t * qoff, const uint32_t * qlen, vsx_hits * out);
+
+}  // extern "C"
+
+// the de novo part search of vsx_uchime_denovo (vsx_chimera.cpp drives it; what needs the searcher's internals lives in vsx_search.cpp)
+struct VsxDenovo;
+int vsx_internal_denovo_create(vsx_searcher * S, VsxDenovo ** out);
+void vsx_internal_denovo_destroy(VsxDenovo * D);
+int vsx_internal_denovo_window(VsxDenovo * D, uint64_t s0, uint64_t wn, const std::vector<uint64_t> & poff, const std::vector<uint32_t> & plen,
+                               const std::vector<uint32_t> & pmember, double * t_rank, double * t_members);
+void vsx_internal_denovo_merge(VsxDenovo * D, uint64_t p, const uint8_t * present, std::vector<uint32_t> & targets);
+int vsx_internal_denovo_search(VsxDenovo * D, const std::vector<uint32_t> & parts, std::vector<std::vector<uint32_t>> & accepted,
+                               uint64_t * pairs, uint64_t * sentinels);
+void vsx_internal_denovo_commit(VsxDenovo * D, const std::vector<uint32_t> & seqnos);
+bool vsx_internal_searcher_has_abundances(const vsx_searcher * S);
+
+// ---- vsx_mask.cpp ------------------------------------------------------------------------------------------------------------
+// DUST of one sequence, for the dispatch layer's per-query masking (the caller owns the scratch copy; hard: --hardmask)
+void vsx_internal_dust_one(char * seq, int64_t len, std::vector<char> & scratch, bool hard = false);
+
+// ---- host helpers ------------------------------------------------------------------------------------------------------------
+#ifndef VSX_DEVICE_RESERVE_BYTES
+#define VSX_DEVICE_RESERVE_BYTES ((size_t) 6 << 30)      // what stays free for the runtime itself (kernel scratch of every queue, code objects)
+#endif
+
+// (hidden: the helpers add nothing to the library's dynamic symbols)
+namespace vsxp __attribute__((visibility("hidden"))) {
+
+// set the thread-local error text, return the code
+__attribute__((format(printf, 2, 3))) inline int fail(int code, const char * fmt, ...)
+{
+  char buf[1024];
+  va_list ap;
+  va_start(ap, fmt);
+  const int n = vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (n < (int) sizeof buf) { vsx_internal_set_error(buf); return code; }
+  std::string big((size_t) n + 1, '\0');
+  va_start(ap, fmt);
+  vsnprintf(&big[0], big.size(), fmt, ap);
+  va_end(ap);
+  vsx_internal_set_error(big.c_str());
+  return code;
+}
+
+inline int hip_fail(const char * who, const char * call, hipError_t e, const char * file, int line)
+{
+  return fail(e == hipErrorOutOfMemory ? VSX_ENOMEM : VSX_EHIP, "%s%s%s failed: %s (%s:%d)", who ? who : "", who ? ": " : "", call,
+              hipGetErrorString(e), file, line);
+}
+
+// return from the calling function when a HIP call fails: VSX_ENOMEM for hipErrorOutOfMemory, VSX_EHIP otherwise.
+// VSX_HIP_AS puts the name of the API function the caller serves in front of the text.
+#define VSX_HIP_AS(who, call) \
+  do { const hipError_t e_ = (call); if (e_ != hipSuccess) return vsxp::hip_fail(who, #call, e_, __FILE__, __LINE__); } while (0)
+#define VSX_HIP(call) VSX_HIP_AS(nullptr, call)
+
+// hipMalloc that never fills the device to the brim and asks the contexts of the device for their idle blocks before it gives up.
+// A device filled to the brim fails LATER and worse than a refused hipMalloc: the runtime cannot allocate a queue's kernel scratch
+// and aborts the process (HSA_STATUS_ERROR_OUT_OF_RESOURCES, profiles/r05/r05b_config5_share_abort.txt).  Keep a reserve.
+inline hipError_t device_malloc(void ** out, size_t bytes)
+{
+  if (bytes >= ((size_t) 16 << 20))
+    {
+      size_t free_b = 0, total_b = 0;
+      int dev = 0;
+      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < bytes + VSX_DEVICE_RESERVE_BYTES && hipGetDevice(&dev) == hipSuccess)
+        (void) vsx_internal_memory_pressure(dev);
+      (void) hipGetLastError();
+    }
+  hipError_t e = hipMalloc(out, bytes);
+  if (e == hipErrorOutOfMemory)
+    {
+      // the aligner contexts of this device may sit on idle checkpoint blocks of an earlier, much larger plan: ask for them
+      int dev = 0;
+      (void) hipGetLastError();
+      if (hipGetDevice(&dev) == hipSuccess && vsx_internal_memory_pressure(dev) > 0) e = hipMalloc(out, bytes);
+    }
+  return e;
+}
+
+// owning device buffer of `n` elements (a request for none still allocates one); every fresh block is poisoned
+template <typename T>
+struct DevBuf {
+  T * p = nullptr;
+  size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf & operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
+  void release() { if (p) { (void) hipFree(p); p = nullptr; n = 0; } }
+  hipError_t alloc(size_t count)
+  {
+    release();
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    const hipError_t e = device_malloc(reinterpret_cast<void **>(&p), bytes);
+    if (e == hipSuccess) { n = count; vsx_internal_poison(p, bytes); } else p = nullptr;
+    return e;
+  }
+  // grow-only: the block is replaced (old one freed first) only when it is too small
+  hipError_t ensure(size_t count) { return (p && count <= n) ? hipSuccess : alloc(count); }
+};
+
+// its pinned host counterpart
+template <typename T>
+struct PinnedBuf {
+  T * p = nullptr;
+  size_t n = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf & operator=(const PinnedBuf &) = delete;
+  ~PinnedBuf() { release(); }
+  void release() { if (p) { (void) hipHostFree(p); p = nullptr; n = 0; } }
+  hipError_t alloc(size_t count)
+  {
+    release();
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault);
+    if (e == hipSuccess) n = count; else p = nullptr;
+    return e;
+  }
+};
+
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+inline int usable_cpus() { return vsx_internal_usable_cpus(); }
+
+// f(0) on the caller, f(1) ... f(nth - 1) on the library's persistent worker pool (every parallel pass of a search window or a
+// clustering round used to create and join its own std::threads -- a dozen passes of 16 threads per round, ~3 ms of a 45 ms round)
+template <typename F>
+void run_pool(int nth, F && f)
+{
+  if (nth <= 1) { f(0); return; }
+  using Fn = typename std::remove_reference<F>::type;
+  vsx_internal_run_threads(nth, [](int t, void * a) { (*static_cast<Fn *>(a))(t); }, (void *) &f);
+}
+
+// chrmap_4bit (utils/maps.cpp): the codes the device encoder writes into a sequence set
+inline uint8_t map4(unsigned char c)
+{
+  switch (c | 0x20)
+    {
+    case 'a': return 1;  case 'b': return 14; case 'c': return 2;  case 'd': return 13;
+    case 'g': return 4;  case 'h': return 11; case 'k': return 12; case 'm': return 3;
+    case 'n': return 15; case 'r': return 5;  case 's': return 6;  case 't': return 8;
+    case 'u': return 8;  case 'v': return 7;  case 'w': return 9;  case 'y': return 10;
+    default: return 0;
+    }
+}
+inline bool ambiguous4(uint8_t c) { return c != 1 && c != 2 && c != 4 && c != 8; }     // chrmap_ambiguous_4bit
+
+}  // namespace vsxp
+
+#endif

@@ -11,10 +11,10 @@
 #include "../../include/vsx_search.h"
 #include "vsx_internal.h"
 #include "vsx_kmer.h"
+#include "vsx_private.h"
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cinttypes>
 #include <climits>
 #include <cfloat>
@@ -29,53 +29,13 @@
 #include <mutex>
 #include <vector>
 
-#include <sched.h>
-
-extern "C" void vsx_internal_set_error(const char * msg);
-extern "C" const vsx_scoring * vsx_internal_scoring(const vsx_ctx * ctx);
-extern "C" int vsx_internal_device(const vsx_ctx * ctx);
-extern "C" void vsx_internal_scratch_sizes(vsx_ctx * ctx, uint64_t out[4]);
-extern "C" void vsx_internal_scratch_requests(vsx_ctx * ctx, uint64_t out[2], int reset);
-extern "C" int vsx_internal_scratch_reserve(vsx_ctx * ctx, const uint64_t want[4]);
-extern "C" uint64_t vsx_internal_ckpt_bytes_estimate(const vsx_ctx * ctx, uint64_t ntasks, uint32_t qlen, uint32_t tlen);
-extern "C" void vsx_internal_run_threads(int nth, void (*fn)(int, void *), void * arg);        // the library's host worker pool (vsx_host.cpp)
-extern "C" int vsx_internal_seqset_create_cased(vsx_ctx * ctx, vsx_seqset ** out, uint64_t n, const char * blob, uint64_t blob_bytes,
-                                                const uint64_t * offsets, const uint32_t * lengths, int mode);
-extern "C" int vsx_internal_seqset_lower_download(const vsx_seqset * s, uint8_t * dst, uint64_t nbytes);
-void vsx_internal_dust_one(char * seq, int64_t len, std::vector<char> & scratch, bool hard = false);        // vsx_mask.cpp (hard: --hardmask)
+using vsxp::fail;
+using vsxp::now_s;
+using vsxp::run_pool;
+using vsxp::usable_cpus;
+using vsxp::map4;
 
 namespace {
-
-int sfail(int code, const std::string & msg) { vsx_internal_set_error(msg.c_str()); return code; }
-
-double now_s()
-{
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// f(0) on the caller, f(1) ... f(nth - 1) on the library's persistent worker pool (r06: every parallel pass of a search window or a
-// clustering round used to create and join its own std::threads -- a dozen passes of 16 threads per round, ~3 ms of a 45 ms round)
-template <typename F>
-void run_pool(int nth, F && f)
-{
-  if (nth <= 1) { f(0); return; }
-  using Fn = typename std::remove_reference<F>::type;
-  vsx_internal_run_threads(nth, [](int t, void * a) { (*static_cast<Fn *>(a))(t); }, (void *) &f);
-}
-
-int usable_cpus()
-{
-  cpu_set_t set;
-  int n = (sched_getaffinity(0, sizeof set, &set) == 0) ? CPU_COUNT(&set) : (int) std::thread::hardware_concurrency();
-  if (FILE * f = std::fopen("/sys/fs/cgroup/cpu.max", "r"))
-    {
-      char q[64]; long long period = 0;
-      if (std::fscanf(f, "%63s %lld", q, &period) == 2 && std::strcmp(q, "max") != 0 && period > 0)
-        n = std::max(1, std::min<int>(n, (int) (std::atoll(q) / period)));
-      std::fclose(f);
-    }
-  return std::max(1, n);
-}
 
 // chrmap_complement, utils/maps.cpp:121-150: IUPAC complement, case kept for the letters that have one, everything else 'N'
 inline char complement(unsigned char c)
@@ -104,19 +64,6 @@ inline unsigned mask_lower(unsigned char c)
 {
   switch (c) { case 'A': case 'C': case 'G': case 'T': case 'U': return 0; default: return 1; }
 }
-inline unsigned map4(unsigned char c)
-{
-  switch (c)
-    {
-    case 'A': case 'a': return 1;  case 'B': case 'b': return 14; case 'C': case 'c': return 2;  case 'D': case 'd': return 13;
-    case 'G': case 'g': return 4;  case 'H': case 'h': return 11; case 'K': case 'k': return 12; case 'M': case 'm': return 3;
-    case 'N': case 'n': return 15; case 'R': case 'r': return 5;  case 'S': case 's': return 6;
-    case 'T': case 't': case 'U': case 'u': return 8;
-    case 'V': case 'v': return 7;  case 'W': case 'w': return 9;  case 'Y': case 'y': return 10;
-    default: return 0;
-    }
-}
-
 // seqcmp, utils/seqcmp.cpp:70-92 (4-bit codes, stops at NUL)
 int seqcmp(const char * a, const char * b, int64_t n)
 {
@@ -585,7 +532,7 @@ static int marshal_hits_from(uint64_t nq, FRange range_of, vsx_hits * out, int t
 {
   out->n_queries = nq;
   out->first = (uint64_t *) std::malloc((nq + 1) * sizeof(uint64_t));
-  if (!out->first) { vsx_hits_free(out); return sfail(VSX_ENOMEM, "host allocation failed"); }
+  if (!out->first) { vsx_hits_free(out); return fail(VSX_ENOMEM, "host allocation failed"); }
   // positions first (a serial scan over two numbers per query), then the copies on host threads (r04: the serial form was 4-5 ms of a
   // 140 ms search call of 100 k queries)
   std::vector<uint64_t> blob_at(nq + 1);
@@ -604,7 +551,7 @@ static int marshal_hits_from(uint64_t nq, FRange range_of, vsx_hits * out, int t
   out->cigar_bytes = bytes;
   out->hit = (vsx_hit *) std::malloc(std::max<uint64_t>(total, 1) * sizeof(vsx_hit));
   out->cigar_blob = (char *) std::malloc(std::max<uint64_t>(bytes, 1));
-  if (!out->hit || !out->cigar_blob) { vsx_hits_free(out); return sfail(VSX_ENOMEM, "host allocation failed"); }
+  if (!out->hit || !out->cigar_blob) { vsx_hits_free(out); return fail(VSX_ENOMEM, "host allocation failed"); }
   auto fill = [&](uint64_t q0, uint64_t q1) {
     for (uint64_t q = q0; q < q1; ++q)
       {
@@ -751,7 +698,7 @@ static int run_stages(const vsx_searcher & S, std::vector<QState> & st, FSeq qse
             if (err[(size_t) t] != VSX_OK)
               {
                 vsx_results_free(&res);
-                return sfail(err[(size_t) t], err[(size_t) t] == VSX_EHIP ? "search: device and host accept filters disagree"
+                return fail(err[(size_t) t], err[(size_t) t] == VSX_EHIP ? "search: device and host accept filters disagree"
                                                                            : "search: fallback aligner failed");
               }
           }
@@ -1057,11 +1004,11 @@ void vsx_search_opts_default(vsx_search_opts * o)
 int vsx_searcher_create(vsx_ctx * ctx, vsx_searcher ** out, const vsx_search_opts * opts, uint64_t n,
                         const char * blob, uint64_t blob_bytes, const uint64_t * offsets, const uint32_t * lengths)
 {
-  if (!ctx || !out || !opts || (n && (!blob || !offsets || !lengths))) return sfail(VSX_EINVAL, "vsx_searcher_create: null argument");
+  if (!ctx || !out || !opts || (n && (!blob || !offsets || !lengths))) return fail(VSX_EINVAL, "vsx_searcher_create: null argument");
   *out = nullptr;
-  if (opts->id < 0.0 || opts->id > 1.0) return sfail(VSX_EINVAL, "vsx_searcher_create: --id must be in [0, 1]");
-  if (opts->wordlength < 3 || opts->wordlength > 15) return sfail(VSX_EINVAL, "vsx_searcher_create: wordlength must be 3..15");
-  if (opts->maxaccepts < 0 || opts->maxrejects < 0) return sfail(VSX_EINVAL, "vsx_searcher_create: negative maxaccepts/maxrejects");
+  if (opts->id < 0.0 || opts->id > 1.0) return fail(VSX_EINVAL, "vsx_searcher_create: --id must be in [0, 1]");
+  if (opts->wordlength < 3 || opts->wordlength > 15) return fail(VSX_EINVAL, "vsx_searcher_create: wordlength must be 3..15");
+  if (opts->maxaccepts < 0 || opts->maxrejects < 0) return fail(VSX_EINVAL, "vsx_searcher_create: negative maxaccepts/maxrejects");
   std::unique_ptr<vsx_searcher> S(new vsx_searcher);
   S->ctx = ctx;
   S->scoring = *vsx_internal_scoring(ctx);
@@ -1076,7 +1023,7 @@ int vsx_searcher_create(vsx_ctx * ctx, vsx_searcher ** out, const vsx_search_opt
   S->off.assign(offsets, offsets + n);
   S->len.assign(lengths, lengths + n);
   for (uint64_t i = 0; i < n; ++i)
-    if (offsets[i] + lengths[i] > blob_bytes) return sfail(VSX_EINVAL, "vsx_searcher_create: sequence exceeds the blob");
+    if (offsets[i] + lengths[i] > blob_bytes) return fail(VSX_EINVAL, "vsx_searcher_create: sequence exceeds the blob");
   // clamp to the database size; 0 means "all" (usearch_global.cpp:598-611)
   const int64_t sc = (int64_t) n;
   S->mr = (opts->maxrejects == 0 || opts->maxrejects > sc) ? sc : opts->maxrejects;
@@ -1087,12 +1034,12 @@ int vsx_searcher_create(vsx_ctx * ctx, vsx_searcher ** out, const vsx_search_opt
   // soft masking: the set keeps a case bitmap for its device k-mer index (the alignment itself is case-blind)
   // (2 = DUST: the device masks the set, vsx_mask.hip, and the host copy takes the result over -- from here on a dust-masked
   //  database is a soft-masked one, exactly as in the reference where dust_all rewrites the Database's text, mask.cpp:233-249)
-  if (S->o.soft_mask < 0 || S->o.soft_mask > 2) return sfail(VSX_EINVAL, "vsx_searcher_create: soft_mask must be 0 (none), 1 (soft) or 2 (dust)");
-  if (S->o.qmask < 0 || S->o.qmask > 3) return sfail(VSX_EINVAL, "vsx_searcher_create: qmask must be 0 (as soft_mask), 1 (none), 2 (soft) or 3 (dust)");
+  if (S->o.soft_mask < 0 || S->o.soft_mask > 2) return fail(VSX_EINVAL, "vsx_searcher_create: soft_mask must be 0 (none), 1 (soft) or 2 (dust)");
+  if (S->o.qmask < 0 || S->o.qmask > 3) return fail(VSX_EINVAL, "vsx_searcher_create: qmask must be 0 (as soft_mask), 1 (none), 2 (soft) or 3 (dust)");
   S->qmode = S->o.qmask ? S->o.qmask - 1 : S->o.soft_mask;
   if (S->o.soft_mask == 2 && !sequences_disjoint(n, [&](uint64_t k) { return offsets[k]; }, [&](uint64_t k) { return (uint64_t) lengths[k]; }))
-    return sfail(VSX_EINVAL, "vsx_searcher_create: DUST masking (soft_mask 2) needs sequences that do not overlap in the blob");
-  if (S->o.hardmask < 0 || S->o.hardmask > 3) return sfail(VSX_EINVAL, "vsx_searcher_create: hardmask must be 0..3 (bit 0: database, bit 1: queries)");
+    return fail(VSX_EINVAL, "vsx_searcher_create: DUST masking (soft_mask 2) needs sequences that do not overlap in the blob");
+  if (S->o.hardmask < 0 || S->o.hardmask > 3) return fail(VSX_EINVAL, "vsx_searcher_create: hardmask must be 0..3 (bit 0: database, bit 1: queries)");
   // r06, --hardmask on the database: the TEXT is rewritten first (host: the option is rare, the exact DUST intervals are needed -- the
   // device bitmap also flags every ambiguity code -- and a symbol that becomes 'N' changes the alignment); what is indexed and aligned
   // from here on is the masked text, with its remaining lower case masked for the k-mers as in every mode but "none"
@@ -1100,7 +1047,7 @@ int vsx_searcher_create(vsx_ctx * ctx, vsx_searcher ** out, const vsx_search_opt
   if (hard_db)
     {
       if (!sequences_disjoint(n, [&](uint64_t k) { return offsets[k]; }, [&](uint64_t k) { return (uint64_t) lengths[k]; }))
-        return sfail(VSX_EINVAL, "vsx_searcher_create: --hardmask needs sequences that do not overlap in the blob");
+        return fail(VSX_EINVAL, "vsx_searcher_create: --hardmask needs sequences that do not overlap in the blob");
       char * const text = S->blob.data();
       if (S->o.soft_mask == 2) dust_states(S.get(), text, n, [&](uint64_t k) { return offsets[k]; }, [&](uint64_t k) { return (int64_t) lengths[k]; }, true);
       else hardmask_states(S.get(), text, n, [&](uint64_t k) { return offsets[k]; }, [&](uint64_t k) { return (int64_t) lengths[k]; });
@@ -1136,7 +1083,7 @@ int vsx_searcher_create(vsx_ctx * ctx, vsx_searcher ** out, const vsx_search_opt
 
 int vsx_searcher_set_meta(vsx_searcher * S, const vsx_seq_meta * meta)
 {
-  if (!S) return sfail(VSX_EINVAL, "vsx_searcher_set_meta: null searcher");
+  if (!S) return fail(VSX_EINVAL, "vsx_searcher_set_meta: null searcher");
   S->tsize.clear();
   S->tlabel.clear();
   if (!meta) return VSX_OK;
@@ -1193,12 +1140,12 @@ int64_t vsx_search_candidates(vsx_searcher * S, const char * q, uint32_t qlen, u
 int vsx_search_candidates_batch(vsx_searcher * S, int32_t device, uint64_t nq, const char * qblob, uint64_t qbytes,
                                 const uint64_t * qoff, const uint32_t * qlen, vsx_candidates * out)
 {
-  if (!S || !out || (nq && (!qblob || !qoff || !qlen))) return sfail(VSX_EINVAL, "vsx_search_candidates_batch: null argument");
+  if (!S || !out || (nq && (!qblob || !qoff || !qlen))) return fail(VSX_EINVAL, "vsx_search_candidates_batch: null argument");
   std::memset(out, 0, sizeof *out);
   for (uint64_t i = 0; i < nq; ++i)
-    if (qoff[i] + qlen[i] > qbytes) return sfail(VSX_EINVAL, "vsx_search_candidates_batch: query exceeds the blob");
+    if (qoff[i] + qlen[i] > qbytes) return fail(VSX_EINVAL, "vsx_search_candidates_batch: query exceeds the blob");
   if (device && !device_kmer_ok(*S))
-    return sfail(VSX_EINVAL, "vsx_search_candidates_batch: the device path needs wordlength 3..15 and a non-empty database");
+    return fail(VSX_EINVAL, "vsx_search_candidates_batch: the device path needs wordlength 3..15 and a non-empty database");
   const double t0 = now_s();
   std::vector<std::vector<Cand>> cands;
   KmerAcct acct;
@@ -1208,7 +1155,7 @@ int vsx_search_candidates_batch(vsx_searcher * S, int32_t device, uint64_t nq, c
   if ((S->qmode == 2 || hard_q) && qbytes)
     {
       if (!sequences_disjoint(nq, [&](uint64_t k) { return qoff[k]; }, [&](uint64_t k) { return (uint64_t) qlen[k]; }))
-        return sfail(VSX_EINVAL, "vsx_search_candidates_batch: DUST / hard query masking needs queries that do not overlap in the blob");
+        return fail(VSX_EINVAL, "vsx_search_candidates_batch: DUST / hard query masking needs queries that do not overlap in the blob");
       masked.assign(qblob, qbytes);
       if (S->qmode == 2) dust_states(S, &masked[0], nq, [&](uint64_t k) { return qoff[k]; }, [&](uint64_t k) { return qlen[k]; }, hard_q);
       else hardmask_states(S, &masked[0], nq, [&](uint64_t k) { return qoff[k]; }, [&](uint64_t k) { return qlen[k]; });
@@ -1223,7 +1170,7 @@ int vsx_search_candidates_batch(vsx_searcher * S, int32_t device, uint64_t nq, c
   out->start = (uint64_t *) std::malloc((nq + 1) * sizeof(uint64_t));
   out->target = (uint32_t *) std::malloc(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
   out->count = (uint32_t *) std::malloc(std::max<uint64_t>(total, 1) * sizeof(uint32_t));
-  if (!out->start || !out->target || !out->count) { vsx_candidates_free(out); return sfail(VSX_ENOMEM, "vsx_search_candidates_batch: out of memory"); }
+  if (!out->start || !out->target || !out->count) { vsx_candidates_free(out); return fail(VSX_ENOMEM, "vsx_search_candidates_batch: out of memory"); }
   uint64_t p = 0;
   for (uint64_t k = 0; k < nq; ++k)
     {
@@ -1273,10 +1220,10 @@ int vsx_search_batch_meta(vsx_searcher * S, uint64_t nq, const char * qblob, uin
 static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, uint64_t qbytes, const uint64_t * qoff,
                              const uint32_t * qlen, const vsx_seq_meta * qmeta, vsx_hits * out, bool raw_queries)
 {
-  if (!S || !out || (nq && (!qblob || !qoff || !qlen))) return sfail(VSX_EINVAL, "vsx_search_batch: null argument");
+  if (!S || !out || (nq && (!qblob || !qoff || !qlen))) return fail(VSX_EINVAL, "vsx_search_batch: null argument");
   std::memset(out, 0, sizeof *out);
   for (uint64_t i = 0; i < nq; ++i)
-    if (qoff[i] + qlen[i] > qbytes) return sfail(VSX_EINVAL, "vsx_search_batch: query exceeds the blob");
+    if (qoff[i] + qlen[i] > qbytes) return fail(VSX_EINVAL, "vsx_search_batch: query exceeds the blob");
   const double t_begin = now_s();
   static const bool timeline = std::getenv("VSX_DEBUG_TIMELINE") != nullptr;
   // lazy first batches (advance()): VSX_SEARCH_LAZY=0 aligns the reference's batches of eight from the start (A/B, tests)
@@ -1684,7 +1631,7 @@ static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, 
     out->first = (uint64_t *) std::malloc((nq + 1) * sizeof(uint64_t));
     out->hit = (vsx_hit *) std::malloc(std::max<uint64_t>(out->n_hits, 1) * sizeof(vsx_hit));
     out->cigar_blob = (char *) std::malloc(std::max<uint64_t>(out->cigar_bytes, 1));
-    if (!out->first || !out->hit || !out->cigar_blob) { vsx_hits_free(out); return sfail(VSX_ENOMEM, "host allocation failed"); }
+    if (!out->first || !out->hit || !out->cigar_blob) { vsx_hits_free(out); return fail(VSX_ENOMEM, "host allocation failed"); }
     std::atomic<size_t> next_w {0};
     run_pool((int) std::max<size_t>(1, std::min<size_t>((size_t) std::min(std::max(1, S->threads), 8), n_windows)), [&](int) {
       for (;;)
@@ -1916,7 +1863,7 @@ static int ap_complete(vsx_searcher * S, int32_t acceptall, const ApList & L, Ap
       }
       for (int t = 0; t < nth; ++t)
         if (err[(size_t) t] != VSX_OK)
-          return sfail(err[(size_t) t], err[(size_t) t] == VSX_EHIP ? "vsx_allpairs_rows: device and host accept filters disagree"
+          return fail(err[(size_t) t], err[(size_t) t] == VSX_EHIP ? "vsx_allpairs_rows: device and host accept filters disagree"
                                                                      : "vsx_allpairs_rows: fallback aligner failed");
       if (rank_drift.load())
         {
@@ -1939,7 +1886,7 @@ static int ap_complete(vsx_searcher * S, int32_t acceptall, const ApList & L, Ap
           h.target = pt[r];
           const char * q = S->blob.data() + S->off[qi];
           const int frc = fill_hit(*S, [&]() { return q; }, (int64_t) S->len[qi], h, one, 0, sentinels);
-          if (frc != VSX_OK) return sfail(frc, "vsx_allpairs_rows: fallback aligner failed");
+          if (frc != VSX_OK) return fail(frc, "vsx_allpairs_rows: fallback aligner failed");
           if (acceptable_aligned(*S, S->len[qi], h, S->abundance(qi)))
             {
               kept[k].push_back(std::move(h));
@@ -1990,7 +1937,7 @@ static int ap_complete(vsx_searcher * S, int32_t acceptall, const ApList & L, Ap
       {
         sentinels += psent[(size_t) t];
         if (err[(size_t) t] != VSX_OK)
-          return sfail(err[(size_t) t], err[(size_t) t] == VSX_EHIP ? "vsx_allpairs_rows: device and host accept filters disagree"
+          return fail(err[(size_t) t], err[(size_t) t] == VSX_EHIP ? "vsx_allpairs_rows: device and host accept filters disagree"
                                                                      : "vsx_allpairs_rows: fallback aligner failed");
       }
   }
@@ -2005,11 +1952,11 @@ static int ap_complete(vsx_searcher * S, int32_t acceptall, const ApList & L, Ap
 
 int vsx_allpairs_rows(vsx_searcher * S, int32_t acceptall, const uint32_t * rows, uint64_t count, vsx_hits * out)
 {
-  if (!S || !out || (count && !rows)) return sfail(VSX_EINVAL, "vsx_allpairs_rows: null argument");
+  if (!S || !out || (count && !rows)) return fail(VSX_EINVAL, "vsx_allpairs_rows: null argument");
   std::memset(out, 0, sizeof *out);
   const uint64_t n = S->len.size();
   for (uint64_t k = 0; k < count; ++k)
-    if (rows[k] >= n || (k && rows[k] <= rows[k - 1])) return sfail(VSX_EINVAL, "vsx_allpairs_rows: rows must be ascending database sequence numbers");
+    if (rows[k] >= n || (k && rows[k] <= rows[k - 1])) return fail(VSX_EINVAL, "vsx_allpairs_rows: rows must be ascending database sequence numbers");
   ApList L;
   int rc = ap_enumerate(S, acceptall, rows, count, L, S->threads);
   if (rc != VSX_OK) return rc;
@@ -2027,9 +1974,9 @@ int vsx_allpairs_rows(vsx_searcher * S, int32_t acceptall, const uint32_t * rows
 // sink stops the run and is handed back.
 int vsx_allpairs_stream(vsx_searcher * S, int32_t acceptall, uint64_t first, uint64_t count, uint64_t block, vsx_hits_sink sink, void * user)
 {
-  if (!S || !sink) return sfail(VSX_EINVAL, "vsx_allpairs_stream: null argument");
+  if (!S || !sink) return fail(VSX_EINVAL, "vsx_allpairs_stream: null argument");
   const uint64_t n = S->len.size();
-  if (first > n || count > n - first) return sfail(VSX_EINVAL, "vsx_allpairs_stream: query block out of range");
+  if (first > n || count > n - first) return fail(VSX_EINVAL, "vsx_allpairs_stream: query block out of range");
   if (block == 0) block = 1000;
   const uint64_t nb = (count + block - 1) / block;
   const int side = std::max(1, S->threads / 2);                  // enumeration and completion run beside each other and beside the planner of stage B
@@ -2112,10 +2059,10 @@ int vsx_allpairs_stream(vsx_searcher * S, int32_t acceptall, uint64_t first, uin
 
 int vsx_allpairs_block(vsx_searcher * S, int32_t acceptall, uint64_t first, uint64_t count, vsx_hits * out)
 {
-  if (!S || !out) return sfail(VSX_EINVAL, "vsx_allpairs_block: null argument");
+  if (!S || !out) return fail(VSX_EINVAL, "vsx_allpairs_block: null argument");
   std::memset(out, 0, sizeof *out);
   const uint64_t n = S->len.size();
-  if (first > n || count > n - first) return sfail(VSX_EINVAL, "vsx_allpairs_block: query block out of range");
+  if (first > n || count > n - first) return fail(VSX_EINVAL, "vsx_allpairs_block: query block out of range");
   std::vector<uint32_t> rows(count);
   for (uint64_t k = 0; k < count; ++k) rows[k] = (uint32_t) (first + k);
   return vsx_allpairs_rows(S, acceptall, rows.data(), count, out);
@@ -2138,11 +2085,11 @@ static bool enough_kmers(const vsx_searcher & S, uint32_t shared, uint32_t kmers
 
 int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
 {
-  if (!S || !out) return sfail(VSX_EINVAL, "vsx_cluster_fast: null argument");
+  if (!S || !out) return fail(VSX_EINVAL, "vsx_cluster_fast: null argument");
   std::memset(out, 0, sizeof *out);
   // (never silently: a caller asking for --strand both must not get plus-strand clusters back)
-  if (S->o.strand_both) return sfail(VSX_EINVAL, "vsx_cluster_fast: clustering with --strand both is not provided");
-  if (S->qmode != S->o.soft_mask) return sfail(VSX_EINVAL, "vsx_cluster_fast: clustering masks everything by soft_mask; qmask must be 0");
+  if (S->o.strand_both) return fail(VSX_EINVAL, "vsx_cluster_fast: clustering with --strand both is not provided");
+  if (S->qmode != S->o.soft_mask) return fail(VSX_EINVAL, "vsx_cluster_fast: clustering masks everything by soft_mask; qmask must be 0");
   const double t_begin = now_s();
   const uint64_t n = S->len.size();
   if (round == 0) round = 16384;          // (r03: 4096 before; with the next round's main ranking prefetched, fewer and larger rounds win: 10.4 -> 8.5 s at 2 M sequences)
@@ -2270,7 +2217,7 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
               const size_t total = centroid_list.size();
               if (total - main_n > main_n / 8 + 2 * round)
                 {
-                  if (have_main) return sfail(VSX_EHIP, "vsx_cluster_fast: the main index changed under a prefetched ranking");   // (excluded by the launch condition below)
+                  if (have_main) return fail(VSX_EHIP, "vsx_cluster_fast: the main index changed under a prefetched ranking");   // (excluded by the launch condition below)
                   const int irc = vsx_kmer_index_rebuild(cix.get(), centroid_list.data(), total);       // main: everything
                   if (irc != VSX_OK) return irc;
                   main_n = total;
@@ -2560,7 +2507,7 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
                           acct.cells += (uint64_t) ql * S->len[h.target];
                           rc = fill_hit(*S, [&]() { return seq_of(seqno); }, ql, h, *rp, (uint64_t) ri, acct.sentinels);
                           vsx_results_free(&one);
-                          if (rc != VSX_OK) { vsx_results_free(&spec); return sfail(rc, "vsx_cluster_fast: fallback aligner failed"); }
+                          if (rc != VSX_OK) { vsx_results_free(&spec); return fail(rc, "vsx_cluster_fast: fallback aligner failed"); }
                         }
                       else { h.rejected = true; ++q.rejects; }
                     }
@@ -2632,7 +2579,7 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
     H->first = (uint64_t *) std::malloc((n + 1) * sizeof(uint64_t));
     H->hit = (vsx_hit *) std::malloc(std::max<size_t>(kept_rec.size(), 1) * sizeof(vsx_hit));
     H->cigar_blob = (char *) std::malloc(std::max<size_t>(kept_cigar.size(), 1));
-    if (!H->first || !H->hit || !H->cigar_blob) { vsx_hits_free(H); return sfail(VSX_ENOMEM, "host allocation failed"); }
+    if (!H->first || !H->hit || !H->cigar_blob) { vsx_hits_free(H); return fail(VSX_ENOMEM, "host allocation failed"); }
     if (!kept_rec.empty()) std::memcpy(H->hit, kept_rec.data(), kept_rec.size() * sizeof(vsx_hit));
     if (!kept_cigar.empty()) std::memcpy(H->cigar_blob, kept_cigar.data(), kept_cigar.size());
     // the records are in sequence order, at most one per sequence
@@ -2643,12 +2590,12 @@ int vsx_cluster_fast(vsx_searcher * S, uint64_t round, vsx_cluster_out * out)
         if (at < kept_rec.size() && kept_rec[at].query == q) ++at;
       }
     H->first[n] = at;
-    if (at != kept_rec.size()) { vsx_hits_free(H); return sfail(VSX_EHIP, "vsx_cluster_fast: hit records out of order"); }
+    if (at != kept_rec.size()) { vsx_hits_free(H); return fail(VSX_EHIP, "vsx_cluster_fast: hit records out of order"); }
   }
   out->n = n;
   out->n_clusters = nclusters;
   out->clusterno = (uint32_t *) std::malloc(std::max<uint64_t>(n, 1) * sizeof(uint32_t));
-  if (!out->clusterno) { vsx_hits_free(&out->hits); return sfail(VSX_ENOMEM, "vsx_cluster_fast: host allocation failed"); }
+  if (!out->clusterno) { vsx_hits_free(&out->hits); return fail(VSX_ENOMEM, "vsx_cluster_fast: host allocation failed"); }
   std::memcpy(out->clusterno, clusterno.data(), n * sizeof(uint32_t));
   out->hits.pairs_aligned = acct.pairs; out->hits.cells_aligned = acct.cells; out->hits.stages = acct.stages;
   out->hits.sentinel_pairs = acct.sentinels; out->hits.seconds_kmer = t_kmer; out->hits.seconds_align = acct.t_align;
@@ -2682,7 +2629,7 @@ const vsx_seqset * vsx_internal_searcher_dbset(const vsx_searcher * S) { return 
 int vsx_internal_search_parts(vsx_searcher * S, int64_t tophits, uint64_t nq, const char * qblob, uint64_t qbytes, const uint64_t * qoff,
                               const uint32_t * qlen, vsx_hits * out)
 {
-  if (!S) return sfail(VSX_EINVAL, "vsx_internal_search_parts: null searcher");
+  if (!S) return fail(VSX_EINVAL, "vsx_internal_search_parts: null searcher");
   struct Restore { vsx_searcher * S; int64_t v; ~Restore() { S->tophits = v; } } restore {S, S->tophits};
   S->tophits = std::min<int64_t>(tophits, (int64_t) S->len.size());
   return search_batch_impl(S, nq, qblob, qbytes, qoff, qlen, nullptr, out, true);
@@ -2763,7 +2710,7 @@ int vsx_internal_denovo_create(vsx_searcher * S, VsxDenovo ** out)
 {
   *out = nullptr;
   if (!device_kmer_subsets_ok(*S))
-    return sfail(VSX_EINVAL, "vsx_uchime_denovo: needs the device k-mer subset indexes: word length 3..8, at least one sequence, VSX_KMER not 'host'");
+    return fail(VSX_EINVAL, "vsx_uchime_denovo: needs the device k-mer subset indexes: word length 3..8, at least one sequence, VSX_KMER not 'host'");
   std::unique_ptr<VsxDenovo> D(new VsxDenovo);
   D->S = S;
   D->keep = (uint32_t) (S->ma + S->mr);
