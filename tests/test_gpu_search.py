@@ -642,6 +642,55 @@ def test_search_window_pipeline_equals_single_thread(gpu_required):
     assert " passed" in p.stdout
 
 
+def test_search_graded_windows_equal_one_window(gpu_required):
+    """More than 32 768 queries at the default window take the piped search with graded windows (40 000 queries: cuts of 4 096 /
+    8 192 / 15 424 / 8 192 / 4 096, three rank workers, up to three consumers, windows marshalled in whatever order they finished);
+    window=65536 runs the same queries as ONE window on the calling thread.  A query's hits do not depend on its window: every hit
+    field and every CIGAR must be equal, query by query."""
+    import numpy as np
+    from vsearch_amd import Aligner
+    from vsearch_amd.search import SearchSession, HIT_FIELDS
+    rs = np.random.RandomState(40000)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    db = acgt[rs.randint(0, 4, size=(64, 200))]
+    nq = 40000
+    src, qlen = rs.randint(0, 64, nq), rs.randint(60, 81, nq)
+    start = (rs.random_sample(nq) * (201 - qlen)).astype(np.int64)
+    minus = rs.random_sample(nq) < 0.5
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    queries = []
+    for k in range(nq):
+        q = db[src[k], start[k]:start[k] + qlen[k]].copy()
+        sub = rs.random_sample(qlen[k]) < 0.03                       # 3 % substitutions: another base
+        q[sub] = acgt[(np.searchsorted(acgt, q[sub]) + rs.randint(1, 4, int(sub.sum()))) % 4]
+        queries.append((comp[q[::-1]] if minus[k] else q).tobytes())
+    dbs = [row.tobytes() for row in db]
+
+    def cigars(hits, cig):
+        nul = np.flatnonzero(np.frombuffer(cig, np.uint8) == 0)
+        off = hits["cigar_off"].astype(np.int64)
+        end = nul[np.searchsorted(nul, off)]
+        return [cig[a:b] for a, b in zip(off.tolist(), end.tolist())]
+
+    with Aligner() as al:
+        got = []
+        for opts in ({}, {"window": 65536}):
+            s = SearchSession(al, dbs, id=0.9, strand_both=1, **opts)
+            got.append(s.search_batch_raw(queries))
+            s.close()
+    (f1, h1, c1), (f2, h2, c2) = got
+    for first, hits in ((f1, h1), (f2, h2)):
+        assert len(first) == nq + 1 and first[0] == 0 and first[nq] == len(hits)
+        assert np.all(first[1:] >= first[:-1])
+    assert len(h2) > nq // 2                                         # (the queries do find their sources)
+    assert np.array_equal(f1, f2)
+    assert np.array_equal(h1["query"], np.repeat(np.arange(nq), np.diff(f1).astype(np.int64)))
+    for name in HIT_FIELDS:
+        assert np.array_equal(h1[name], h2[name]), name
+    assert cigars(h1, c1) == cigars(h2, c2)
+
+
 def test_dust_masking_refuses_overlapping_sequences(gpu_required):
     """DUST rewrites the text in place: sequences that share bytes of the blob would get the union of their masks (the reference
     masks every sequence on its own, mask.cpp:233-249), so the library refuses them -- database and raw queries alike."""

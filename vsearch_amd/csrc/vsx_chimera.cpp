@@ -1,6 +1,6 @@
 // vsx_chimera.cpp -- --uchime_ref and de novo chimera dispatch (include/vsx_search.h vsx_uchime_ref, vsx_uchime_denovo) and the host
 // restatement of the selection and scoring.  The de novo loop (denovo_window below) reuses steps 4-5; its part search lives in
-// vsx_search.cpp (vsx_internal_denovo_*).
+// vsx_denovo_search.cpp (vsx_internal_denovo_*).
 //
 // chimera_process_query (reference core/chimera.cpp:2003-2170) for a WINDOW of queries at a time:
 //   1. partition_query (:1930-1955): 4 parts per query of length >= 4 -- offsets into the caller's blob, nothing is copied

@@ -482,7 +482,7 @@ void vsx_internal_poison(void * p, size_t bytes)
   static const bool on = std::getenv("VSX_POISON") != nullptr;
   if (on && p && bytes) { (void) hipMemset(p, 0xA5, bytes); (void) hipDeviceSynchronize(); }
 }
-// the host worker pool for vsx_search.cpp (fn(0) runs on the caller, which also helps with queued jobs while it waits)
+// the host worker pool of the dispatch layer, vsx_search.cpp and the commands on its searcher (fn(0) runs on the caller, which also helps with queued jobs while it waits)
 void vsx_internal_run_threads(int nth, void (*fn)(int, void *), void * arg) { run_threads(nth, [&](int t) { fn(t, arg); }); }
 // shared with vsx_search.cpp: one thread-local error slot for the whole library
 void vsx_internal_set_error(const char * msg) { g_err = msg ? msg : ""; }

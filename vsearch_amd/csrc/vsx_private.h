@@ -69,7 +69,10 @@ int vsx_internal_search_parts(vsx_searcher * S, int64_t tophits, uint64_t nq, co
 
 }  // extern "C"
 
-// the de novo part search of vsx_uchime_denovo (vsx_chimera.cpp drives it; what needs the searcher's internals lives in vsx_search.cpp)
+bool vsx_internal_searcher_has_abundances(const vsx_searcher * S);
+
+// ---- vsx_denovo_search.cpp ---------------------------------------------------------------------------------------------------
+// the de novo part search of vsx_uchime_denovo (vsx_chimera.cpp drives it; what needs the searcher's internals lives there)
 struct VsxDenovo;
 int vsx_internal_denovo_create(vsx_searcher * S, VsxDenovo ** out);
 void vsx_internal_denovo_destroy(VsxDenovo * D);
@@ -79,7 +82,6 @@ void vsx_internal_denovo_merge(VsxDenovo * D, uint64_t p, const uint8_t * presen
 int vsx_internal_denovo_search(VsxDenovo * D, const std::vector<uint32_t> & parts, std::vector<std::vector<uint32_t>> & accepted,
                                uint64_t * pairs, uint64_t * sentinels);
 void vsx_internal_denovo_commit(VsxDenovo * D, const std::vector<uint32_t> & seqnos);
-bool vsx_internal_searcher_has_abundances(const vsx_searcher * S);
 
 // ---- vsx_mask.cpp ------------------------------------------------------------------------------------------------------------
 // DUST of one sequence, for the dispatch layer's per-query masking (the caller owns the scratch copy; hard: --hardmask)
