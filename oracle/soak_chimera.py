@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""TEST INFRASTRUCTURE ONLY: randomized soak of chimera detection (vsx_uchime_ref, vsx_uchime_denovo -> vsx_chimera.hip and its
+host route) against the REFERENCE CLI's --uchimeout, byte for byte.
+
+A round draws one of --uchime_ref, --uchime_denovo, --uchime2_denovo, --uchime3_denovo; a length class (60-120, 300-500,
+1 200-1 600, 3 900-4 200: the last one straddles the kernel's limit of 4 096); the mask mode and --hardmask; --minh, --mindiv,
+--mindiffs, --xn, --dn, --abskew (de novo); window and search_window.  Data: for --uchime_ref a family database of 20-40 references
+and 30-60 queries (two- and three-parent chimeras, mutated members, odd sequences); for the de novo commands 80-150 sized sequences
+of a small tests/denovo_data.cascade_set().  The two long classes divide the number of QUERIES (for the de novo commands: of
+sequences, each of which is a query) by 3 and by 8; the database of --uchime_ref keeps its 20-40 references, so a query still
+meets up to 16 candidates.  The reference aligns every query with each of them: a full-size round at 4 000 symbols costs it
+more than ten seconds.  A round the reference refuses counts as failing.  --reference-only counts the reference's lines without
+a device.  The output's "coverage" counts the rounds per command and length class and the rounds with --hardmask / --abskew.
+
+    python oracle/soak_chimera.py --seconds 120 --seed 1 --out soak_chimera.json
+"""
+import argparse
+import json
+import os
+import random
+import subprocess
+import sys
+import tempfile
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, ROOT)
+
+from oracle import refcli  # noqa: E402
+from tests import common, denovo_data  # noqa: E402
+
+LENGTHS = [((60, 120), 1), ((300, 500), 1), ((1200, 1600), 3), ((3900, 4200), 8)]
+MASKS = {"none": 0, "soft": 1, "dust": 2}
+
+
+def draw(rng):
+    """-> (command, (length range, divisor of the counts), keywords of the session, the CLI's arguments)"""
+    cmd = rng.choice(["uchime_ref", "uchime_denovo", "uchime2_denovo", "uchime3_denovo"])
+    length = rng.choice(LENGTHS)
+    o, cli = {}, []
+    mask = rng.choice(["none", "soft", "dust"])
+    if cmd == "uchime_ref":
+        cli += ["--qmask", mask, "--dbmask", mask]
+    else:
+        cli += ["--qmask", mask]
+    o["soft_mask"] = MASKS[mask]
+    if rng.random() < 0.25:
+        cli.append("--hardmask")
+        o["hardmask"] = 3 if cmd == "uchime_ref" else 1
+    for key, vals in (("minh", [0.1, 0.2, 0.5]), ("mindiv", [0.5, 1.5]), ("mindiffs", [2, 4]), ("xn", [4.0, 6.5]), ("dn", [1.1, 2.0])):
+        v = rng.choice(vals)
+        if rng.random() < 0.3:
+            o[key] = v
+            cli += ["--" + key, str(v)]
+    v = rng.choice([1.0, 1.5, 3.5, 8.0])
+    if cmd != "uchime_ref" and rng.random() < 0.3:
+        o["abskew"] = v
+        cli += ["--abskew", str(v)]
+    w, sw = rng.choice([0, 1, 7, 50]), rng.choice([0, 5, 64])
+    if w:
+        o["window"] = w
+    if sw:
+        o["search_window"] = sw
+    return cmd, length, o, cli
+
+
+def _chimera(rng, parents):
+    n = min(len(p) for p in parents)
+    cuts = sorted(rng.sample(range(n // 6, n - n // 6), len(parents) - 1))
+    edges = [0] + cuts + [None]
+    return common.mutate(rng, "".join(p[edges[i]:edges[i + 1]] for i, p in enumerate(parents)), 0.01)
+
+
+def ref_data(rng, length, div):
+    (lo, hi), n_db, n_q = length, rng.randint(20, 40), max(4, rng.randint(30, 60) // div)
+    members = rng.choice([2, 4, 5])
+    db = []
+    while len(db) < n_db:
+        anc = common.rnd_seq(rng, rng.randint(lo, hi))
+        db += [common.mutate(rng, anc, rng.choice([0.03, 0.05, 0.08])) for _ in range(min(members, n_db - len(db)))]
+    qs = []
+    for i in range(n_q):
+        r = rng.random()
+        if r < 0.35:
+            qs.append(_chimera(rng, rng.sample(db, 2)))
+        elif r < 0.6 and len(db) >= 3:
+            qs.append(_chimera(rng, rng.sample(db, 3)))
+        elif r < 0.85:
+            qs.append(common.mutate(rng, rng.choice(db), 0.03))
+        else:
+            qs.append(rng.choice([common.rnd_seq(rng, rng.randint(1, 40)), common.mutate(rng, rng.choice(db), 0.05, "ACGTNRY"),
+                                  rng.choice(db).lower(), "AC" * rng.randint(20, 60) + rng.choice(db)[:lo]]))
+    return [f"r{i}" for i in range(len(db))], db, [f"q{i}" for i in range(len(qs))], qs
+
+
+def denovo_data_set(rng, length, div):
+    fam, chim = max(2, rng.randint(20, 30) // div), max(2, rng.randint(18, 36) // div)
+    return denovo_data.cascade_set(seed=rng.randrange(1 << 30), n_families=fam, members=(2, 4), n_chimeras=chim, extras=False, length=length)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=60.0)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--max-rounds", type=int, default=0, help="stop after this many rounds (0: run for --seconds): a deterministic set of rounds for a given seed")
+    ap.add_argument("--reference-only", action="store_true", help="run the reference alone and count its lines (no device)")
+    a = ap.parse_args()
+    if not refcli.available():
+        raise SystemExit("oracle/_ref/vsearch_ref missing: make -C oracle ref_full")
+    al = None
+    if not a.reference_only:
+        from vsearch_amd import Aligner, ChimeraSession, DenovoChimeraSession
+        al = Aligner()
+    rng = random.Random(a.seed)
+    t_end = time.time() + a.seconds
+    rounds = lines = bad = 0
+    ref_seconds = 0.0
+    failing = []
+    coverage = {}
+    with tempfile.TemporaryDirectory(prefix="vsxsoakc_") as tmp:
+        qf, df, uo = os.path.join(tmp, "q.fa"), os.path.join(tmp, "db.fa"), os.path.join(tmp, "u.tsv")
+        while time.time() < t_end and (a.max_rounds <= 0 or rounds < a.max_rounds):
+            cmd, (length, div), o, cli = draw(rng)
+            if cmd == "uchime_ref":
+                tn, db, qn, qs = ref_data(rng, length, div)
+                refcli.write_fasta(df, tn, db)
+                args = ["--uchime_ref", qf, "--db", df]
+            else:
+                qn, qs = denovo_data_set(rng, length, div)
+                args = [f"--{cmd}", qf]
+            refcli.write_fasta(qf, qn, qs)
+            t0 = time.time()
+            p = subprocess.run([refcli.REF_BIN] + args + ["--uchimeout", uo, "--threads", "1", "--quiet"] + cli, capture_output=True, text=True)
+            ref_seconds += time.time() - t0
+            rounds += 1
+            for key in [f"{cmd}@{length[0]}-{length[1]}"] + [k for k in ("hardmask", "abskew") if k in o]:
+                coverage[key] = coverage.get(key, 0) + 1
+            full = [cmd] + cli + [f"length={length}", f"n={len(qs)}"] + [f"{k}={o[k]}" for k in ("window", "search_window") if k in o]
+            if p.returncode != 0:
+                bad += 1
+                if len(failing) < 10:
+                    failing.append({"cli": full, "round": rounds - 1, "error": p.stderr[-300:]})
+                continue
+            exp = open(uo).read().splitlines()
+            lines += len(exp)
+            if a.reference_only:
+                continue
+            if cmd == "uchime_ref":
+                got = ChimeraSession(al, db, labels=tn, **o).uchimeout(qs, qn)
+            else:
+                got = DenovoChimeraSession(al, qs, qn, variant=cmd.split("_")[0], **o).uchimeout()
+            if got != exp:
+                bad += 1
+                if len(failing) < 10:
+                    first = next((i for i, (x, y) in enumerate(zip(got, exp)) if x != y), min(len(got), len(exp)))
+                    failing.append({"cli": full, "round": rounds - 1, "lines": [len(got), len(exp)], "first_diff": first,
+                                    "got": got[first] if first < len(got) else None, "exp": exp[first] if first < len(exp) else None})
+    if al is not None:
+        al.close()
+    out = {"rounds": rounds, "lines": lines, "failing_rounds": bad, "failures": failing, "seed": a.seed, "seconds": a.seconds,
+           "reference_seconds": round(ref_seconds, 3), "coverage": coverage,
+           "what": "vsx_uchime_ref / vsx_uchime_denovo vs vsearch_ref --uchime_ref / --uchime*_denovo --uchimeout with the same randomly drawn options"}
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f)
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()

@@ -22,8 +22,8 @@ def _chimera(rng, parents):
     return common.mutate(rng, "".join(p[edges[i]:edges[i + 1]] for i, p in enumerate(parents)), 0.004)
 
 
-def cascade_set(seed=77, n_families=400, members=(2, 8), n_chimeras=None, extras=True):
-    """(labels, sequences) in input order (not sorted)"""
+def cascade_set(seed=77, n_families=400, members=(2, 8), n_chimeras=None, extras=True, length=(300, 500)):
+    """(labels, sequences) in input order (not sorted); length: the range of the families' ancestor lengths"""
     rng = random.Random(seed)
     seqs, sizes, names = [], [], []
 
@@ -34,7 +34,7 @@ def cascade_set(seed=77, n_families=400, members=(2, 8), n_chimeras=None, extras
 
     good = []
     for f in range(n_families):
-        anc = common.rnd_seq(rng, rng.randint(300, 500))
+        anc = common.rnd_seq(rng, rng.randint(*length))
         for m in range(rng.randint(*members)):
             good.append(common.mutate(rng, anc, 0.02))
     ranks = list(range(1, len(good) + 1))

@@ -141,3 +141,45 @@ def test_out_of_range_quality(host_merge, name, build, opts, fatal):
         with pytest.raises(VsxError, match=rf"FASTQ quality value \({fatal[1]}\) {fatal[0]} \({fatal[2]}\)") as ei:
             host_merge(*data[1:], **opts)
         assert ei.value.code == -1          # VSX_EINVAL
+
+
+needs_cli = pytest.mark.skipif(not os.path.exists(md.ref_binary()), reason="oracle/_ref/vsearch_ref not built")
+
+
+@needs_cli
+def test_boundary_pairs_host_path(host_merge):
+    """merge_data.boundary_pairs() (tests/test_gpu_merge_edges.py runs it through the kernel): the host path against the live
+    reference, and the conditions the list must meet, on the reference's own output"""
+    from tests.test_gpu_merge_edges import BOUNDARY_RUNS, check_boundary_reference
+    data = md.boundary_pairs()
+    assert len(set(data[0])) == len(data[0])
+    refs = []
+    for extra in BOUNDARY_RUNS:
+        opts = dict(md.BOUNDARY_OPTS, **extra)
+        refs.append(md.run_reference(*data, **opts))
+        assert refs[-1]["returncode"] == 0, refs[-1]["stderr"]
+        assert_matches(host_merge(*data[1:], **opts), data[0], refs[-1])
+    check_boundary_reference(refs)
+    k = data[0].index("cap_homopolymer_512")
+    assert host_merge(*[[col[k]] for col in data[1:]]).stats["diagonals_scored"] >= 1000
+    # each capacity pair on its own, at the reference's defaults: `repeat`; the pairs whose two best diagonals tie below minscore:
+    # `minscore` (the first, unstaggered diagonal wins; the second would give `staggered`)
+    for k, lab in enumerate(data[0]):
+        if lab.startswith("cap_"):
+            alone = [[col[k]] for col in data]
+            want = {"minscore": 1} if "tie" in lab else {"repeat": 1}
+            ref = md.run_reference(*alone)
+            assert ref["returncode"] == 0 and ref["reasons"] == want, (lab, ref["reasons"])
+            assert host_merge(*alone[1:]).reason_counts() == want, lab
+
+
+@needs_cli
+@pytest.mark.parametrize("which", [0, 2])
+def test_encoding_sets_host_path(host_merge, which):
+    from tests.test_gpu_merge_edges import ENCODING_SETS, check_encoding_reference, encoding_data
+    name, ascii, qmin, qmax, opts = ENCODING_SETS[which]
+    data = encoding_data(ascii, qmin, qmax)
+    opts = dict(opts, maxns=4)
+    ref = md.run_reference(*data, **opts)
+    check_encoding_reference(data, ref, ascii, opts)
+    assert_matches(host_merge(*data[1:], **opts), data[0], ref)
