@@ -274,8 +274,8 @@ int vsx_msa_device_batch(vsx_ctx * ctx, uint32_t n_clusters, const uint64_t * cl
    Parent selection and scoring run in one kernel (one workgroup per query) that reads the alignments' run words where the
    traceback left them; queries above VSX_CHIMERA_MAX_QLEN, and queries with a candidate the 16-bit aligner refused (realigned with
    vsx_lma_align), are answered by a host restatement of the same two functions.  Plus strand only (the reference refuses
-   --strand both here).  The de novo forms (--uchime_denovo / uchime2 / uchime3) are vsx_uchime_denovo below.  Not covered:
-   --chimeras_denovo, --uchimealns. */
+   --strand both here).  The de novo forms (--uchime_denovo / uchime2 / uchime3) are vsx_uchime_denovo below, the long-read
+   detector --chimeras_denovo is vsx_chimeras_denovo.  Not covered: --uchimealns / --alnout text. */
 typedef struct vsx_chimera_opts {
   vsx_search_opts search;   /* the searcher's options: masking, hardmask, wordlength, threads, window (of the part search) and the
                                detection parameters id = weak_id = 0.55, maxaccepts 4, maxrejects 16.  As in the reference, the
@@ -361,6 +361,73 @@ typedef struct vsx_chimera_denovo_stats {
   uint64_t queries_kernel, queries_host;                           /* evaluations by the kernel / the host restatement */
 } vsx_chimera_denovo_stats;
 void vsx_chimera_denovo_last_stats(vsx_chimera_denovo_stats * out);
+
+/* ---- de novo chimera detection in long, high-quality reads: --chimeras_denovo (vsx_chimera.cpp / vsx_chimera_long.hip) ----
+   The loop is vsx_uchime_denovo's (abundance-sorted input, growing index of the queries that were not chimeric, windows of
+   speculative passes), with three differences (chimera_process_query, core/chimera.cpp:2003-2170):
+     parts       (length + 99) / 100, or `parts` when given, clamped to 2 .. 100 (realloc_arrays :285-299); a query shorter than its
+                 part count is not searched.  The candidates are the accepted hits of all parts, repeated targets dropped: up to
+                 maxaccepts x parts of them
+     selection   find_best_parents_long (:505-624): up to parents_max rounds; each round takes, over the candidates in list order,
+                 the longest stretch of still unused query positions, uninterrupted by an insertion, in which the candidate matches
+                 (a non-zero AND of the 4-bit codes) with at most diff_pct percent mismatches; it must reach length_min.  The query
+                 is chimeric iff at least two such regions were found and they cover every position
+     evaluation  eval_parents_long (:995-1242): the identity of the query with each parent over the columns of the multiple
+                 alignment (query length + the longest insertion in front of each position), equal 4-bit codes counting as matches
+   Selection and evaluation run in one kernel (one workgroup per query) over the run words the traceback left in HBM.
+   The kernel takes a query iff
+     - its length is at most VSX_CHIMERAS_LONG_MAX_QLEN and it has at most VSX_CHIMERAS_LONG_MAX_CAND candidates,
+     - the 16-bit aligner refused none of its candidates, and
+     - diff_pct * 2^13 is an integer (0, 1, 2.5, 0.125, ...; not 0.1).  The reference scans a segment with sums of doubles, diff_pct
+       per match and diff_pct - 100 per mismatch; for such a percentage every partial sum over <= 2 048 positions is a multiple of
+       2^-13 below 2^18, exactly representable, so the kernel forms the same sums as 32-bit integers in units of 2^-13 (they stay
+       below 2^31) and the order of addition cannot matter.  With diff_pct = 0 a region is simply a run of matching positions.
+       For any other percentage the sums are formed in the reference's order by the host restatement only.
+   Every other query is answered by the host restatement of the same two functions (also under VSX_CHIMERA=host). */
+#define VSX_CHIMERAS_LONG_MAX_PARENTS 20    /* maxparents (chimera.cpp:111) */
+#define VSX_CHIMERAS_LONG_MAX_QLEN    2048  /* longest query the long-read kernel takes (its LDS layout) */
+#define VSX_CHIMERAS_LONG_MAX_CAND    64    /* most candidates of one query the long-read kernel takes (its LDS layout) */
+#define VSX_CHIMERA_CHIMERIC          3     /* vsx_chimeras_long_result.status: Status::chimeric (the other value is NO_PARENTS) */
+typedef struct vsx_chimeras_long_opts {
+  vsx_search_opts search;   /* as vsx_chimera_denovo_opts.base.search: id = weak_id = 0.55, maxaccepts 4, maxrejects 16, self = selfid = 1,
+                               maxsizeratio = 1 / abskew */
+  int32_t parts;            /* --chimeras_parts: 0 = by length, else 2 .. 100 */
+  int32_t parents_max;      /* --chimeras_parents_max: 2 .. 20, default 3 */
+  int32_t length_min;       /* --chimeras_length_min: >= 1, default 10 */
+  int32_t pad;
+  double  diff_pct;         /* --chimeras_diff_pct: 0.0 .. 50.0, default 0.0 */
+  double  abskew;           /* --abskew: >= 1.0, default 1.0 for this command (cli.cc:4481-4484) */
+  int64_t window;           /* queries per speculative window; 0 = 4 096 */
+} vsx_chimeras_long_opts;
+void vsx_chimeras_long_opts_default(vsx_chimeras_long_opts * o);
+/* One record per sequence.  parent / start / len [0 .. n_parents) are the regions found, sorted by start (database indices; the same
+   sequence may appear twice); they are filled for a query that is not chimeric, too (fewer than two regions, or a position left
+   uncovered).  The identities, alnlen and the divergence are set for chimeric queries only. */
+typedef struct vsx_chimeras_long_result {
+  int32_t  status;                                           /* VSX_CHIMERA_NO_PARENTS or VSX_CHIMERA_CHIMERIC */
+  char     flag;                                             /* 'Y' or 'N' */
+  char     pad[3];
+  int32_t  n_parents;
+  int32_t  alnlen;                                           /* query length + the longest insertion in front of each position */
+  uint32_t parent[VSX_CHIMERAS_LONG_MAX_PARENTS];
+  int32_t  start[VSX_CHIMERAS_LONG_MAX_PARENTS];
+  int32_t  len[VSX_CHIMERAS_LONG_MAX_PARENTS];
+  double   id_query_parent[VSX_CHIMERAS_LONG_MAX_PARENTS];   /* QA, QB, QC, ...: 100 * equal columns / alnlen */
+  double   id_query_top;                                     /* QT = the largest of them */
+  double   divergence;                                       /* 100 * (100 - QT) / QT */
+} vsx_chimeras_long_result;
+/* out[k] = the searcher's sequence k.  Preconditions as vsx_uchime_denovo: sequences pre-sorted by abundance, abundances set, word
+   length <= 8, plus strand.  VSX_EINVAL: an option outside its range (cli.cc:4390-4411: length_min < 1, parents_max outside 2 .. 20,
+   diff_pct outside 0 .. 50, parts neither 0 nor 2 .. 100), abskew < 1, a searcher not created with the options above.
+   VSX_CHIMERA=host answers every query with the host restatement. */
+int vsx_chimeras_denovo(vsx_searcher * s, const vsx_chimeras_long_opts * opts, vsx_chimeras_long_result * out);
+/* accounting of the calling thread's last vsx_chimeras_denovo (the fields of vsx_uchime_denovo's) */
+void vsx_chimeras_denovo_last_stats(vsx_chimera_denovo_stats * out);
+/* For tests / tooling: the host restatement on ONE query and nc candidates given as text with their alignments (CIGAR text, query
+   against candidate, as vsx_lma_align writes it); no device.  The record's parents are candidate numbers 0 .. nc - 1.  Only the
+   selection and evaluation options of `opts` are read (and range-checked as above). */
+int vsx_internal_chimeras_long_host(const char * q, uint32_t qlen, uint32_t nc, const char * const * t, const uint32_t * tlen,
+                                    const char * const * cigars, const vsx_chimeras_long_opts * opts, vsx_chimeras_long_result * out);
 
 /* The scalar fallback the callers run on the SHRT_MAX sentinel: LinearMemoryAligner::align + alignstats
    (core/linmemalign.cpp:694-808; call sites core/searchcore.cpp:806-832, commands/allpairs_global.cpp:447-473).

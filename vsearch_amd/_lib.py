@@ -30,7 +30,9 @@ SEARCH_SYMBOLS = ["vsx_search_opts_default", "vsx_searcher_create", "vsx_searche
                   "vsx_multi_searcher_create", "vsx_multi_searcher_destroy", "vsx_multi_searcher_devices", "vsx_multi_searcher_replica",
                   "vsx_multi_search_batch", "vsx_multi_allpairs",
                   "vsx_chimera_opts_default", "vsx_uchime_ref", "vsx_chimera_last_stats",
-                  "vsx_chimera_denovo_opts_default", "vsx_uchime_denovo", "vsx_chimera_denovo_last_stats"]
+                  "vsx_chimera_denovo_opts_default", "vsx_uchime_denovo", "vsx_chimera_denovo_last_stats",
+                  "vsx_chimeras_long_opts_default", "vsx_chimeras_denovo", "vsx_chimeras_denovo_last_stats",
+                  "vsx_internal_chimeras_long_host"]
 # include/vsx_merge.h (a list of its own: SYMBOLS stays exactly what include/vsx.h declares; build() checks both)
 MERGE_SYMBOLS = ["vsx_merge_opts_default", "vsx_merge_pairs", "vsx_merge_out_free", "vsx_merge_last_stats"]
 
@@ -93,6 +95,25 @@ class ChimeraDenovoStats(C.Structure):
                 ("queries_reevaluated", C.c_uint64), ("parts", C.c_uint64), ("pairs_searched", C.c_uint64),
                 ("pairs_aligned", C.c_uint64), ("sentinel_pairs", C.c_uint64), ("queries_kernel", C.c_uint64),
                 ("queries_host", C.c_uint64)]
+
+
+CHIMERAS_LONG_MAX_PARENTS = 20
+CHIMERAS_LONG_MAX_QLEN = 2048      # VSX_CHIMERAS_LONG_MAX_QLEN
+CHIMERAS_LONG_MAX_CAND = 64        # VSX_CHIMERAS_LONG_MAX_CAND
+
+
+class ChimerasLongOpts(C.Structure):
+    """vsx_chimeras_long_opts (include/vsx_search.h): searcher options + the --chimeras_denovo parameters"""
+    _fields_ = [("search", SearchOpts), ("parts", C.c_int32), ("parents_max", C.c_int32), ("length_min", C.c_int32),
+                ("pad", C.c_int32), ("diff_pct", C.c_double), ("abskew", C.c_double), ("window", C.c_int64)]
+
+
+class ChimerasLongResult(C.Structure):
+    """vsx_chimeras_long_result (include/vsx_search.h)"""
+    _fields_ = [("status", C.c_int32), ("flag", C.c_char), ("pad", C.c_char * 3), ("n_parents", C.c_int32), ("alnlen", C.c_int32),
+                ("parent", C.c_uint32 * CHIMERAS_LONG_MAX_PARENTS), ("start", C.c_int32 * CHIMERAS_LONG_MAX_PARENTS),
+                ("len", C.c_int32 * CHIMERAS_LONG_MAX_PARENTS), ("id_query_parent", C.c_double * CHIMERAS_LONG_MAX_PARENTS),
+                ("id_query_top", C.c_double), ("divergence", C.c_double)]
 
 
 class MergeOpts(C.Structure):

@@ -8,13 +8,18 @@
     .uchime_denovo() -> per-sequence dicts in processing order (abundance-sorted); .order[k] = input index of record k
     .uchimeout() -> the --uchimeout lines in processing order;  .nonchimeras() -> input indices of the non-chimeras
 
+    ChimerasDenovoSession(aligner, seqs, labels, **opts)   ~ --chimeras_denovo (long, high-quality reads; vsx_chimeras_denovo)
+    .chimeras_denovo() -> per-sequence dicts in processing order;  .tabbedout() -> the --tabbedout lines (chimeras only)
+    .chimeras / .nonchimeras -> the labels of --chimeras / --nonchimeras in output order
+
 Options: minh, mindiv, mindiffs, xn, dn (the UCHIME parameters) and the searcher's soft_mask (--dbmask: 0 none, 1 soft, 2 dust =
 default), qmask (--qmask when it differs: 1 + mode), hardmask, wordlength, threads, window (queries per chimera window) and
 search_window (queries per window of the part search)."""
 import ctypes as C
 
 from . import _lib
-from ._lib import ChimeraDenovoOpts, ChimeraDenovoStats, ChimeraOpts, ChimeraResult, ChimeraStats, check
+from ._lib import (ChimeraDenovoOpts, ChimeraDenovoStats, ChimeraOpts, ChimeraResult, ChimerasLongOpts, ChimerasLongResult, ChimeraStats,
+                   check)
 from .search import _blob, _meta
 
 NONE = 0xFFFFFFFF
@@ -254,3 +259,120 @@ class DenovoChimeraSession:
         if records is None:
             records = self._records if self._records is not None else self.uchime_denovo()
         return [self.order[k] for k, r in enumerate(records) if r["flag"] == "N"]
+
+
+LONG_STATUS = {0: "no_parents", 3: "chimeric"}
+
+
+def chimeras_long_default_opts():
+    """vsx_chimeras_long_opts_default as a ChimerasLongOpts structure"""
+    o = ChimerasLongOpts()
+    _lib.load().vsx_chimeras_long_opts_default(C.byref(o))
+    return o
+
+
+def long_record(r):
+    """a ChimerasLongResult as a dict: the per-parent arrays cut to n_parents"""
+    n = r.n_parents
+    return dict(status=LONG_STATUS[r.status], flag=r.flag.decode(), n_parents=n, alnlen=r.alnlen, parent=[int(x) for x in r.parent[:n]],
+                start=list(r.start[:n]), len=list(r.len[:n]), id_query_parent=list(r.id_query_parent[:n]),
+                id_query_top=r.id_query_top, divergence=r.divergence)
+
+
+def format_tabbedout(rec, qname, tnames):
+    """one --tabbedout line of --chimeras_denovo (eval_parents_long, chimera.cpp:1183-1239); chimeric records only"""
+    ids = rec["id_query_parent"]
+    third = tnames[rec["parent"][2]] if rec["n_parents"] > 2 else "*"
+    return "%.4f\t%s\t%s\t%s\t%s\t%.2f\t%.2f\t%.2f\t%.2f\t%.2f\t0\t0\t0\t0\t0\t0\t%.2f\tY" % (
+        99.9999, qname, tnames[rec["parent"][0]], tnames[rec["parent"][1]], third, 100.0, ids[0], ids[1],
+        ids[2] if rec["n_parents"] > 2 else 0.0, rec["id_query_top"], 0.0)
+
+
+class ChimerasDenovoSession:
+    """--chimeras_denovo of one set of sequences: the long-read detector.  Constructor conventions as DenovoChimeraSession (length
+    filter, ;size= parsing, sortbyabundance order, soft_mask = the --qmask mode, hardmask).  Options: parts (0 = by length),
+    parents_max (3), length_min (10), diff_pct (0.0), abskew (1.0), window, wordlength (3..8), minwordmatches, threads,
+    search_window."""
+
+    def __init__(self, aligner, seqs, labels, minseqlength=1, maxseqlength=50000, **opts):
+        lib = _lib.load()
+        if len(labels) != len(seqs):
+            raise ValueError("labels: one header per sequence")
+        self.aligner = aligner
+        aligner._children.add(self)
+        o = chimeras_long_default_opts()
+        for k, v in opts.items():
+            if k == "soft_mask" and isinstance(v, str):
+                v = MASK_MODES[v]
+            if k in _SEARCH_KEYS:
+                setattr(o.search, k, v)
+            elif k == "search_window":
+                o.search.window = v
+            elif k in ("parts", "parents_max", "length_min", "diff_pct", "window"):
+                setattr(o, k, v)
+            elif k == "abskew":
+                o.abskew = v
+                o.search.maxsizeratio = 1.0 / v
+            else:
+                raise TypeError(f"unknown chimera option {k}")
+        self.opts = o
+        keep = [i for i, s in enumerate(seqs) if minseqlength <= len(s) <= maxseqlength]
+        sizes = {i: header_size(labels[i]) for i in keep}
+        kl = [labels[i] for i in keep]
+        self.order = [keep[j] for j in sort_by_abundance([sizes[i] for i in keep], kl)]
+        self.seqs = [seqs[i] for i in self.order]
+        self.labels = [labels[i] for i in self.order]
+        self.sizes = [sizes[i] for i in self.order]
+        blob, off, lens = _blob(self.seqs)
+        self._keep = (blob, off, lens)
+        self.h = C.c_void_p()
+        check(lib.vsx_searcher_create(aligner.h, C.byref(self.h), C.byref(o.search), len(lens),
+                                      C.cast(C.c_char_p(blob), C.c_void_p), len(blob),
+                                      off.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p)),
+              "vsx_searcher_create")
+        m, self._meta_keep = _meta(self.sizes, self.labels, len(lens))
+        check(lib.vsx_searcher_set_meta(self.h, C.byref(m)), "vsx_searcher_set_meta")
+        self.stats = {}
+        self._records = None
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            _lib.load().vsx_searcher_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def chimeras_denovo(self):
+        """one dict per sequence in processing order: status ('chimeric' / 'no_parents'), flag, n_parents, parent (processing-order
+        indices), start, len, id_query_parent, id_query_top, divergence, alnlen"""
+        lib = _lib.load()
+        n = len(self.seqs)
+        out = (ChimerasLongResult * max(n, 1))()
+        check(lib.vsx_chimeras_denovo(self.h, C.byref(self.opts), out), "vsx_chimeras_denovo")
+        st = ChimeraDenovoStats()
+        lib.vsx_chimeras_denovo_last_stats(C.byref(st))
+        self.stats = {k: getattr(st, k) for k, _ in ChimeraDenovoStats._fields_}
+        self._records = [long_record(out[k]) for k in range(n)]
+        return self._records
+
+    def _recs(self):
+        return self._records if self._records is not None else self.chimeras_denovo()
+
+    def tabbedout(self, records=None):
+        """--tabbedout lines in processing order (what the reference CLI writes with one thread): one per chimeric query"""
+        records = records if records is not None else self._recs()
+        return [format_tabbedout(r, qn, self.labels) for r, qn in zip(records, self.labels) if r["flag"] == "Y"]
+
+    @property
+    def chimeras(self):
+        """labels of the --chimeras file, in output order"""
+        return [qn for r, qn in zip(self._recs(), self.labels) if r["flag"] == "Y"]
+
+    @property
+    def nonchimeras(self):
+        """labels of the --nonchimeras file, in output order"""
+        return [qn for r, qn in zip(self._recs(), self.labels) if r["flag"] != "Y"]

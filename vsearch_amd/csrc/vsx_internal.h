@@ -134,9 +134,35 @@ struct VsxChimParams {
   int32_t pad;
 };
 
+// vsx_chimera_long.hip: one query of the long-read kernel (--chimeras_denovo).  Its candidates are the targets of plan pairs
+// pair0 .. pair0 + ncand - 1, read from the pair-indexed array the launcher is given: the item carries no candidate array
+struct VsxChimLongItem {
+  uint32_t q;                        // index in the query set
+  uint32_t ncand;                    // <= VSX_CHIMERAS_LONG_MAX_CAND
+  uint32_t pair0;
+  uint32_t out;                      // index of its result record
+};
+struct VsxChimLongParams {
+  int32_t parents_max, length_min;
+  double  diff_pct;                  // the host restatement's
+  int32_t gain;                      // the kernel's: diff_pct * 2^13 (the host sends the kernel only items for which that is an integer)
+  int32_t pad;
+};
+// workgroups of one launch when the kernel scans with a tolerance, and the ints of scratch each of them owns
+#define VSX_CHIMLONG_SCRATCH_GROUPS 256u
+#define VSX_CHIMLONG_SCRATCH_INTS   ((size_t) VSX_CHIMERAS_LONG_MAX_QLEN * VSX_CHIMERAS_LONG_MAX_CAND)
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+// vsx_chimera_long.hip: find_best_parents_long + eval_parents_long per item; pair_target[p] = database index of plan pair p's target;
+// out is indexed by item.out (struct vsx_chimeras_long_result, include/vsx_search.h)
+hipError_t vsx_launch_chimeras_long(const VsxChimLongItem * d_items, uint32_t nitems, const uint8_t * qcodes, const uint64_t * qoff,
+                                    const uint32_t * qlen, const uint8_t * tcodes, const uint64_t * toff, const uint32_t * tlen,
+                                    const VsxPairOut * d_hits, const uint32_t * d_pair_target, uint64_t n_pairs, const uint32_t * d_runs,
+                                    uint64_t n_runs, VsxChimLongParams P, int32_t * d_scratch /* GROUPS x INTS, or null when P.gain == 0 */,
+                                    void * d_out, hipStream_t st);
 
 // vsx_chimera.hip: find_best_parents + eval_parents per item; out is indexed by item.out (struct vsx_chimera_result, include/vsx_search.h)
 hipError_t vsx_launch_chimera_eval(const VsxChimItem * d_items, uint32_t nitems, const uint8_t * qcodes, const uint64_t * qoff,
