@@ -35,6 +35,8 @@ SEARCH_SYMBOLS = ["vsx_search_opts_default", "vsx_searcher_create", "vsx_searche
                   "vsx_internal_chimeras_long_host"]
 # include/vsx_merge.h (a list of its own: SYMBOLS stays exactly what include/vsx.h declares; build() checks both)
 MERGE_SYMBOLS = ["vsx_merge_opts_default", "vsx_merge_pairs", "vsx_merge_out_free", "vsx_merge_last_stats"]
+# include/vsx_filter.h
+FILTER_SYMBOLS = ["vsx_fastx_filter_opts_default", "vsx_fastx_filter", "vsx_fastx_filter_out_free", "vsx_fastx_filter_last_stats"]
 
 
 class Candidates(C.Structure):
@@ -144,6 +146,38 @@ class MergeStats(C.Structure):
     _fields_ = [("seconds_stage", C.c_double), ("seconds_kernel", C.c_double), ("seconds_unpack", C.c_double),
                 ("seconds_total", C.c_double), ("pairs", C.c_uint64), ("windows", C.c_uint64), ("diagonals_scored", C.c_uint64),
                 ("pairs_host", C.c_uint64)]
+
+
+class FilterOpts(C.Structure):
+    """vsx_fastx_filter_opts (include/vsx_filter.h): the Parameters fields the filter's analysis reads"""
+    _fields_ = [(n, C.c_int64) for n in ("ascii", "qmin", "qmax", "stripleft", "stripright", "trunclen", "trunclen_keep", "truncqual",
+                                         "minqual", "minlen", "maxlen", "maxns", "minsize", "maxsize")] + \
+               [(n, C.c_double) for n in ("maxee", "maxee_rate", "truncee", "truncee_rate")] + [("window", C.c_int64)]
+
+
+class FilterReads(C.Structure):
+    """vsx_fastx_reads (include/vsx_filter.h): one side of the input"""
+    _fields_ = [("seq", C.c_void_p), ("qual", C.c_void_p), ("bytes", C.c_uint64), ("off", C.c_void_p), ("len", C.c_void_p),
+                ("abundance", C.c_void_p)]
+
+
+class FilterRecord(C.Structure):
+    """vsx_fastx_filter_record (include/vsx_filter.h)"""
+    _fields_ = [("start", C.c_int32), ("length", C.c_int32), ("ee", C.c_double), ("discarded", C.c_uint8), ("truncated", C.c_uint8),
+                ("pad", C.c_uint8 * 6)]
+
+
+class FilterOut(C.Structure):
+    """vsx_fastx_filter_out (include/vsx_filter.h)"""
+    _fields_ = [("n", C.c_uint64), ("fwd", C.POINTER(FilterRecord)), ("rev", C.POINTER(FilterRecord)),
+                ("pair_discarded", C.POINTER(C.c_uint8)), ("kept", C.c_uint64), ("kept_truncated", C.c_uint64), ("discarded", C.c_uint64)]
+
+
+class FilterStats(C.Structure):
+    """vsx_fastx_filter_stats (include/vsx_filter.h)"""
+    _fields_ = [("seconds_stage", C.c_double), ("seconds_h2d", C.c_double), ("seconds_kernel", C.c_double),
+                ("seconds_d2h_output", C.c_double), ("seconds_total", C.c_double), ("reads", C.c_uint64), ("windows", C.c_uint64),
+                ("reads_host", C.c_uint64)]
 
 
 class SeqMeta(C.Structure):
@@ -320,6 +354,14 @@ def load():
     lib.vsx_merge_out_free.restype = None
     lib.vsx_merge_last_stats.argtypes = [C.POINTER(MergeStats)]
     lib.vsx_merge_last_stats.restype = None
+    lib.vsx_fastx_filter_opts_default.argtypes = [C.POINTER(FilterOpts)]
+    lib.vsx_fastx_filter_opts_default.restype = None
+    lib.vsx_fastx_filter.argtypes = [vp, C.POINTER(FilterOpts), C.c_uint64, C.POINTER(FilterReads), C.POINTER(FilterReads),
+                                     C.POINTER(FilterOut)]
+    lib.vsx_fastx_filter_out_free.argtypes = [C.POINTER(FilterOut)]
+    lib.vsx_fastx_filter_out_free.restype = None
+    lib.vsx_fastx_filter_last_stats.argtypes = [C.POINTER(FilterStats)]
+    lib.vsx_fastx_filter_last_stats.restype = None
     _lib = lib
     return lib
 

@@ -46,7 +46,7 @@ double symbol_error_probability(int symbol, int64_t ascii)
 {
   const int value = symbol - (int) ascii;
   if (value < 2) return 0.75;
-  return std::pow(10.0, -value / 10.0);
+  return vsxp::phred_error_probability(value);
 }
 
 // Edgar & Flyvbjerg (2015) posterior qualities and the log-odds scores of an observed match / mismatch
@@ -247,12 +247,7 @@ struct OutBuilder {
 
 int quality_failure(const vsx_merge_opts & o, const QualError & e)
 {
-  char msg[256];
-  if (e.kind == 1)
-    std::snprintf(msg, sizeof msg, "vsx_merge_pairs: FASTQ quality value (%d) below qmin (%lld)", e.value, (long long) o.fastq_qmin);
-  else
-    std::snprintf(msg, sizeof msg, "vsx_merge_pairs: FASTQ quality value (%d) above qmax (%lld)", e.value, (long long) o.fastq_qmax);
-  return fail(VSX_EINVAL, "%s", msg);
+  return vsxp::quality_failure("vsx_merge_pairs", e.kind, e.value, (long long) o.fastq_qmin, (long long) o.fastq_qmax);
 }
 
 // ---- the window pipeline ----------------------------------------------------------------------------------------------------

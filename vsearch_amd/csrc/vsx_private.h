@@ -9,6 +9,7 @@
 #include <hip/hip_runtime_api.h>
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -188,6 +189,16 @@ struct PinnedBuf {
     return e;
   }
 };
+
+// the error probability of a Phred quality value, as the reference tabulates it (the device never evaluates it: tables are host-built)
+inline double phred_error_probability(int value) { return std::pow(10.0, -value / 10.0); }
+
+// the reference's fatal error for a quality value outside [qmin, qmax]; kind 1: below qmin, 2: above qmax
+inline int quality_failure(const char * who, int kind, int value, long long qmin, long long qmax)
+{
+  if (kind == 1) return fail(VSX_EINVAL, "%s: FASTQ quality value (%d) below qmin (%lld)", who, value, qmin);
+  return fail(VSX_EINVAL, "%s: FASTQ quality value (%d) above qmax (%lld)", who, value, qmax);
+}
 
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
