@@ -9,7 +9,8 @@ from .search import SearchSession, msa, msa_batch, dust_mask  # noqa: F401
 from .chimera import ChimeraSession, ChimerasDenovoSession, DenovoChimeraSession  # noqa: F401
 from .merge import merge_pairs, MergeResult, MERGE_REASONS  # noqa: F401
 from .filter import filter_reads, FilterResult  # noqa: F401
+from .eestats import read_stats, EEStatsResult  # noqa: F401
 from ._lib import SENTINEL, VsxError, load as load_library  # noqa: F401
 
 __all__ = ["Aligner", "SequenceSet", "Plan", "AlignmentResults", "RawResults", "cigar_from_runs", "DEFAULT_SCORING", "scoring_from_tuple",
-           "SearchSession", "ChimeraSession", "DenovoChimeraSession", "ChimerasDenovoSession", "merge_pairs", "MergeResult", "MERGE_REASONS", "filter_reads", "FilterResult", "SENTINEL", "VsxError", "load_library"]
+           "SearchSession", "ChimeraSession", "DenovoChimeraSession", "ChimerasDenovoSession", "merge_pairs", "MergeResult", "MERGE_REASONS", "filter_reads", "FilterResult", "read_stats", "EEStatsResult", "SENTINEL", "VsxError", "load_library"]

@@ -37,6 +37,9 @@ SEARCH_SYMBOLS = ["vsx_search_opts_default", "vsx_searcher_create", "vsx_searche
 MERGE_SYMBOLS = ["vsx_merge_opts_default", "vsx_merge_pairs", "vsx_merge_out_free", "vsx_merge_last_stats"]
 # include/vsx_filter.h
 FILTER_SYMBOLS = ["vsx_fastx_filter_opts_default", "vsx_fastx_filter", "vsx_fastx_filter_out_free", "vsx_fastx_filter_last_stats"]
+# include/vsx_eestats.h
+EESTATS_SYMBOLS = ["vsx_fastq_eestats_opts_default", "vsx_fastq_eestats", "vsx_fastq_eestats_out_free", "vsx_fastq_eestats_last_stats"]
+EESTATS_WANT_EESTATS, EESTATS_WANT_EESTATS2 = 1, 2
 
 
 class Candidates(C.Structure):
@@ -178,6 +181,28 @@ class FilterStats(C.Structure):
     _fields_ = [("seconds_stage", C.c_double), ("seconds_h2d", C.c_double), ("seconds_kernel", C.c_double),
                 ("seconds_d2h_output", C.c_double), ("seconds_total", C.c_double), ("reads", C.c_uint64), ("windows", C.c_uint64),
                 ("reads_host", C.c_uint64)]
+
+
+class EEStatsOpts(C.Structure):
+    """vsx_fastq_eestats_opts (include/vsx_eestats.h)"""
+    _fields_ = [(n, C.c_int64) for n in ("ascii", "qmin", "qmax", "len_shortest", "len_longest", "len_increment")] + \
+               [("ee_cutoffs", C.POINTER(C.c_double)), ("n_ee_cutoffs", C.c_uint64), ("want", C.c_uint32), ("pad", C.c_uint32),
+                ("window", C.c_int64), ("hist_budget", C.c_uint64)]
+
+
+class EEStatsOut(C.Structure):
+    """vsx_fastq_eestats_out (include/vsx_eestats.h)"""
+    _fields_ = [("n", C.c_uint64), ("symbols", C.c_uint64), ("len_min", C.c_uint64), ("len_max", C.c_uint64),
+                ("qual_cols", C.c_uint64), ("reads_at", C.POINTER(C.c_uint64)), ("qual_counts", C.POINTER(C.c_uint64)),
+                ("sum_ee", C.POINTER(C.c_double)), ("ee_bins", C.POINTER(C.c_int64)), ("len_steps", C.c_uint64),
+                ("n_ee_cutoffs", C.c_uint64), ("cutoff_counts", C.POINTER(C.c_uint64))]
+
+
+class EEStatsStats(C.Structure):
+    """vsx_fastq_eestats_stats (include/vsx_eestats.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_walk", "seconds_sum", "seconds_quantile",
+                                          "seconds_d2h_output", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("reads", "windows", "reads_host")]
 
 
 class SeqMeta(C.Structure):
@@ -362,6 +387,13 @@ def load():
     lib.vsx_fastx_filter_out_free.restype = None
     lib.vsx_fastx_filter_last_stats.argtypes = [C.POINTER(FilterStats)]
     lib.vsx_fastx_filter_last_stats.restype = None
+    lib.vsx_fastq_eestats_opts_default.argtypes = [C.POINTER(EEStatsOpts)]
+    lib.vsx_fastq_eestats_opts_default.restype = None
+    lib.vsx_fastq_eestats.argtypes = [vp, C.POINTER(EEStatsOpts), C.c_uint64, C.POINTER(FilterReads), C.POINTER(EEStatsOut)]
+    lib.vsx_fastq_eestats_out_free.argtypes = [C.POINTER(EEStatsOut)]
+    lib.vsx_fastq_eestats_out_free.restype = None
+    lib.vsx_fastq_eestats_last_stats.argtypes = [C.POINTER(EEStatsStats)]
+    lib.vsx_fastq_eestats_last_stats.restype = None
     _lib = lib
     return lib
 
