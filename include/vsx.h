@@ -117,6 +117,7 @@ typedef struct vsx_plan_info {
   uint64_t tasks_sparse;    /* ... in a sparse-task class: tasks of <= 4 / <= 2 targets that share a wave with 1 / 3 others */
   uint64_t waves;           /* wavefronts the DP launches of one run start (= tasks without sparse-task classes)            */
   uint64_t tasks_pair;      /* ... in a pair-profile class: groups of four tasks of one pure-ACGT query as one workgroup    */
+  uint64_t tasks_split;     /* ... in a split-profile class: whole-wave MAX3 tasks whose targets are all plain A / C / G / T */
 } vsx_plan_info;
 
 const char * vsx_version_string(void);

@@ -44,6 +44,9 @@ __device__ __forceinline__ unsigned pmaxu(unsigned a, unsigned b)
 #define R 16
 //       mode 2 = PAIR profile: one dword per (symbol pair of the two targets, position, row) = both halves ready; 16 pairs (pure
 //       A/C/G/T targets) x 16 x 16 x 4 B = 16 KB per wave, i.e. at most 2 waves per SIMD; ds_read_b128 per 4 rows, add, max3, sub, 2 max.
+//       mode 3 = SPLIT profile: two dword tables of 4 symbols, LO[sym][row] = score and HI[sym][row] = score << 16, quarter-major
+//       [table][sym][quarter][lane][4 dwords] = 8 KB per wave; ds_read_b128 per 4 rows and target (one quarter ahead, quarter 0 of the
+//       next step before the last quarter), add3, max3, sub, 2 max: the row body of vsx_forward_kernel SPLIT.
 template <int MODE>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 2 : 4, 8))) k_rows(int steps, unsigned * out, unsigned seed)
 {
@@ -101,6 +104,35 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MODE ==
             E[r] = pmaxu(E[r], he);
           }
       }
+    else if (MODE == 3)
+      {
+        const char * base = reinterpret_cast<const char *>(QP) + l * 16;
+        const char * pa = base + (ca & 3u) * 1024u, * pb = base + ((cb & 3u) + 4u) * 1024u;
+        uint4 lo = *reinterpret_cast<const uint4 *>(pa), hi = *reinterpret_cast<const uint4 *>(pb), lo2, hi2;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          {
+            if ((r & 3) == 0)
+              {
+                if (r) { lo = lo2; hi = hi2; }
+                // the quarter after this one; before the last quarter: quarter 0 of another symbol pair (the next step's, in the kernel)
+                const int k = (r >> 2) + 1;
+                if (k < R / 4) { lo2 = *reinterpret_cast<const uint4 *>(pa + k * 256); hi2 = *reinterpret_cast<const uint4 *>(pb + k * 256); }
+                else { lo2 = *reinterpret_cast<const uint4 *>(base + (cb & 3u) * 1024u); hi2 = *reinterpret_cast<const uint4 *>(base + ((ca & 3u) + 4u) * 1024u); }
+              }
+            const unsigned vl = (r & 3) == 0 ? lo.x : ((r & 3) == 1 ? lo.y : ((r & 3) == 2 ? lo.z : lo.w));
+            const unsigned vh = (r & 3) == 0 ? hi.x : ((r & 3) == 1 ? hi.y : ((r & 3) == 2 ? hi.z : hi.w));
+            const unsigned h0 = Hd + vl + vh;
+            const unsigned h2 = max3(h0, F, E[r]);
+            Hd = hin[r];
+            hout[r] = h2;
+            const unsigned he = h2 - go;
+            F = pmaxu(F, he);
+            E[r] = pmaxu(E[r], he);
+          }
+        Hd ^= lo2.x & hi2.x & 1u;          // (keeps the look-ahead reads alive)
+        diag ^= Hd & 1u;
+      }
     else
       {
         const unsigned aA = (unsigned) (size_t) QP + (ca * (16 * R) + (unsigned) l * R) * 2u;
@@ -157,7 +189,7 @@ template <int MODE> static void run(int waves_per_simd)
   CK(hipMemcpy(&h0, out, 4, hipMemcpyDeviceToHost));
   const double cycles = ms * 1e-3 * 2.4e9;
   printf("mode %d (%s) waves/SIMD %d: %8.3f ms, %.1f cycles per lane-row and wave   [check %08x]\n", MODE,
-         MODE == 0 ? "b64 loads + perm, 6 VALU per row" : (MODE == 1 ? "u16 loads, add3, 5 VALU per row" : "pair profile, b128 loads, 5 VALU per row"), waves_per_simd, ms,
+         MODE == 0 ? "b64 loads + perm, 6 VALU per row" : (MODE == 1 ? "u16 loads, add3, 5 VALU per row" : (MODE == 2 ? "pair profile, b128 loads, 5 VALU per row" : "split LO / HI tables, 2 x b128 per 4 rows, add3, 5 VALU per row")), waves_per_simd, ms,
          cycles / ((double) steps * R * waves_per_simd), h0);
   CK(hipFree(out));
 }
@@ -173,5 +205,6 @@ int main()
   printf("  (table: lane x holds 0x1100 + x at its address, 0x2200 + x at +128)  d16_hi zeroes the low half: %s\n", (h[0] & 0xffffu) == 0 ? "YES" : "no");
   for (int w = 1; w <= 4; w *= 2) { run<0>(w); run<1>(w); if (w <= 2) run<2>(w); }
   run<0>(3);
+  run<3>(4); run<3>(3);
   return 0;
 }

@@ -170,7 +170,19 @@ DEV u32 pk_max3_bits(u32 a, u32 b, u32 c)            // IEEE maximum of three: t
 // 16.22 -> 15.6, 300 x 300 10.10 -> 9.76, 400 x 400 16.83 -> 16.07, 150 x 300 5.43 -> 5.22 (same box, two runs each).  The sparse-task
 // classes (NQ > 1) always were single-strip, which is why they compiled without spills (VERDICT r05 "next" 3b asked what they do not
 // keep live: the strip state).
-template <int R, bool TRACK, bool TILT = false, bool MAX3 = false, int NQ = 1, bool PAIR = false, bool ONE = false>
+// SPLIT (the SPLIT-PROFILE classes of the MAX3 family): a whole-wave single-strip task whose TARGETS are all plain A / C / G / T (the
+// query may hold anything: its symbol picks the matrix column that is baked into the table).  Two dword tables replace the byte profile,
+//   LO[sym][row] = S'[sym][q_row]   and   HI[sym][row] = S'[sym][q_row] << 16,
+// a lane reads its rows of LO at target A's symbol and of HI at target B's, four rows per ds_read_b128, and h0 = Hdiag + lo + hi is ONE
+// v_add3_u32: the row body loses its v_perm_b32 (5 instead of 6 instructions per lane-row, as in PAIR).  No carry crosses the halves for
+// the reason the v_add_u32 is exact: primed scores are 0 .. 255 and the planner proves the range of every half.
+// Layout, quarter-major: TAB[table][sym 0..3][quarter k][lane l][4 dwords] -- for read k the 16 lanes of a group fetch 16 consecutive
+// 16-byte pieces, every symbol block is a multiple of 256 B, and each 16-lane pass of a ds_read_b128 holds every l once: conflict-free
+// without padding.  2 x 4 x 16 RP x 4 B = 8 KB at R = 16 (the pair table: 16-20 KB), which one wave can afford at 16 waves per CU once
+// the class drops FEEDB: phase B derives (QR_t, R_t) from a flag of the column (bit 10 = column >= D - 1) that travels with the symbols.
+// The rows are read in quarters, quarter k + 1 in flight while quarter k is consumed; quarter 0 of step t + 1 is requested before the
+// last quarter of step t from the look-ahead offsets.  Checkpoints are bit-identical to the byte-profile class.
+template <int R, bool TRACK, bool TILT = false, bool MAX3 = false, int NQ = 1, bool PAIR = false, bool ONE = false, bool SPLIT = false>
 __global__ void __launch_bounds__(PAIR ? 256 : 64) __attribute__((amdgpu_waves_per_eu(NQ == 1 ? (ONE ? VSX_FWD_WAVES_ONE(R, TILT) : VSX_FWD_WAVES(R, TILT)) : VSX_FWD_WAVES_NQ(R, NQ), 8)))
 vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                    const uint8_t * __restrict__ qc, const uint8_t * __restrict__ tc,
@@ -210,28 +222,33 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
   static_assert(NQ == 1 || NQ == 2 || NQ == 4, "tasks per wave");
   static_assert(NQ == 1 || TILT, "the sparse-task classes exist for the look-ahead TILT kernels only");
   static_assert(!PAIR || (NQ == 1 && TILT), "the pair-profile classes extend the FEED2 look-ahead kernels");
+  static_assert(!SPLIT || (TILT && MAX3 && NQ == 1 && !PAIR && ONE), "the split-profile classes are whole-wave single-strip MAX3 kernels");
   constexpr int WPB = PAIR ? 4 : 1;                  // waves per workgroup
   constexpr int QPBYTES = 16 * 16 * RP;              // one byte profile
   // pair profile: row stride RPP dwords with RPP / 4 odd, so that the 16 lanes of a group (each reading whole 16-byte quarters) start
   // in sixteen different 4-bank groups
   constexpr int RPP = ((RP / 4) & 1) ? RP : RP + 4;
   __shared__ __attribute__((aligned(16))) u32 PPf[PAIR ? 16 * 16 * RPP : 4];
-  __shared__ __attribute__((aligned(16))) int16_t QP[!PAIR ? (QPL ? (NQ * QPBYTES) / 2 : 16 * 16 * R) : 8];
+  constexpr int NQT = RP / 4;                        // SPLIT: quarters (ds_read_b128) per table and step
+  static_assert(!SPLIT || NQT >= 2, "the split-profile rows are read a quarter ahead");
+  constexpr int SPSYM = NQT * 256;                   // SPLIT: bytes of one symbol block [quarter][lane][4 dwords]
+  __shared__ __attribute__((aligned(16))) int16_t QP[!PAIR ? (SPLIT ? (2 * 4 * SPSYM) / 2 : (QPL ? (NQ * QPBYTES) / 2 : 16 * 16 * R)) : 8];
   // feed block of the column pipeline: [lane group][column of the 16-block] (sym, QR_t, R_t, H) and F -- written once per 16
   // steps by the 16 lanes of a group, read back one column per step for lane 0 (replaces five v_mov_b32_dpp row_ror rotations)
   constexpr int FSZ = (TILT ? 2 : 1) * 4 * 16;                         // feed entries of one wave
   __shared__ uint4 FEED4a[FSZ * WPB];                                  // QPL: two blocks (the next one is built a step early)
-  __shared__ u32 FEEDFa[FSZ * WPB];
+  __shared__ u32 FEEDFa[FSZ * WPB];                                    // (FEED2 classes never touch it: not allocated there)
   // FEED2 (the classes with the look-ahead byte profile): the record of a column is (byte offsets of the two targets' profile rows in
   // the halves of one dword, symbols + flags, H, F) -- an interior step reads H and F of its column and the offsets of the next column
   // from three neighbouring dwords, and the profile addresses are two adds -- and (QR_t, R_t) live in a second array for phase B
+  // (SPLIT: no second array, see above)
   constexpr bool FEED2 = TILT;
-  __shared__ uint2 FEEDBa[FEED2 ? 2 * 4 * 16 * WPB : 1];
+  __shared__ uint2 FEEDBa[(FEED2 && !SPLIT) ? 2 * 4 * 16 * WPB : 1];
 
   const int wv = PAIR ? __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6)) : 0;      // wave of the workgroup = task of the group of four (scalar: the task's fields stay in SGPRs)
   uint4 * const FEED4 = FEED4a + wv * FSZ;
   u32 * const FEEDF = FEEDFa + wv * FSZ;
-  uint2 * const FEEDB = FEEDBa + (FEED2 ? wv * FSZ : 0);
+  uint2 * const FEEDB = FEEDBa + ((FEED2 && !SPLIT) ? wv * FSZ : 0);
   const int lane = PAIR ? (int) (threadIdx.x & 63) : (int) threadIdx.x;
   const int gw = lane >> 4;                        // lane group of the wave
   constexpr int GPT = 4 / NQ;                      // lane groups per task
@@ -299,6 +316,26 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                         }
                     }
                   PPf[(pr * 16 + row / RP) * RPP + rr] = ((u32) va & 0xffu) | (((u32) vb & 0xffu) << 16);
+                }
+            }
+          else if (SPLIT)
+            {
+              u32 * const TAB = reinterpret_cast<u32 *>(QP);
+              for (int idx = lane; idx < 2 * 4 * NQT * 64; idx += 64)
+                {
+                  const int tb = idx / (4 * NQT * 64), sy = (idx / (NQT * 64)) & 3, k = (idx % (NQT * 64)) >> 6;
+                  const int Lr = (idx >> 2) & 15, rr = 4 * k + (idx & 3);
+                  int v = 0;
+                  if (rr < R)
+                    {
+                      if (Lr == 0 && rr < pad) v = -P.top_step + 2 * tl;
+                      else if (Lr < total_lanes)
+                        {
+                          const int gi = (Lr == 0) ? rr - pad : rcnt0 + (Lr - 1) * R + rr;
+                          v = P.matrix[(1 << sy) * 16 + (int) qq[gi]];
+                        }
+                    }
+                  TAB[idx] = ((u32) v & 0xffu) << (tb ? 16 : 0);
                 }
             }
           else if (QPL)
@@ -402,6 +439,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                   f_H = (s == 0) ? bpack(rawH - pad * tl) : rawS.x;
                   f_F = (s == 0) ? vsub(f_H, qrt_i_pk) : rawS.y;
                   const u32 f_off = PAIR ? (((rawA >> 1) - (rawA >> 3)) * 4u + ((rawB >> 1) - (rawB >> 3))) * (u32) (16 * RPP * 4)
+                                  : SPLIT ? (((rawA >> 1) - (rawA >> 3)) * (u32) SPSYM | ((((rawB >> 1) - (rawB >> 3)) + 4u) * (u32) SPSYM) << 16)
                                          : (rawA * (u32) (16 * RP) | ((rawB * (u32) (16 * RP)) << 16));
                   FEED4[(blk & 1) * 64 + gw * 16 + l] = make_uint4(f_off, 0u, f_H, f_F);
                   prefetch(blk + 1);
@@ -411,8 +449,9 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               const u32 qB = (u32) ((c < DB - 1) ? P.qrt_i : P.qrt_r) & 0xffffu;
               const u32 rA = (u32) ((c < DA - 1) ? P.rt_i : P.rt_r) & 0xffffu;
               const u32 rB = (u32) ((c < DB - 1) ? P.rt_i : P.rt_r) & 0xffffu;
-              const u32 sA = rawA | ((c == DA - 1) ? 0x100u : 0u) | ((c < DpA) ? 0x200u : 0u);
-              const u32 sB = rawB | ((c == DB - 1) ? 0x100u : 0u) | ((c < DpB) ? 0x200u : 0u);
+              // (SPLIT, bit 10: the column takes the right-end penalties -- what phase B makes (QR_t, R_t) from)
+              const u32 sA = rawA | ((c == DA - 1) ? 0x100u : 0u) | ((c < DpA) ? 0x200u : 0u) | ((SPLIT && !(c < DA - 1)) ? 0x400u : 0u);
+              const u32 sB = rawB | ((c == DB - 1) ? 0x100u : 0u) | ((c < DpB) ? 0x200u : 0u) | ((SPLIT && !(c < DB - 1)) ? 0x400u : 0u);
               f_sym = sA | (sB << 16);
               f_qrt = qA | (qB << 16);
               f_rt = rA | (rB << 16);
@@ -432,9 +471,10 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                   // QPb[code][16 positions][RP] bytes; PAIR: the byte offset of PP[pair = 4 ia + ib] (codes 1 2 4 8 -> 0 1 2 3; a column
                   // past a target's end has code 0 -> index 0: any valid address, nobody keeps what it yields)
                   const u32 f_off = PAIR ? (((rawA >> 1) - (rawA >> 3)) * 4u + ((rawB >> 1) - (rawB >> 3))) * (u32) (16 * RPP * 4)
+                                  : SPLIT ? (((rawA >> 1) - (rawA >> 3)) * (u32) SPSYM | ((((rawB >> 1) - (rawB >> 3)) + 4u) * (u32) SPSYM) << 16)
                                          : (rawA * (u32) (16 * RP) | ((rawB * (u32) (16 * RP)) << 16));
                   FEED4[fo + gw * 16 + l] = make_uint4(f_off, f_sym, f_H, f_F);
-                  FEEDB[fo + gw * 16 + l] = make_uint2(f_qrt, f_rt);
+                  if (!SPLIT) FEEDB[fo + gw * 16 + l] = make_uint2(f_qrt, f_rt);
                 }
               else
                 {
@@ -449,7 +489,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
       constexpr int PD = RP / 4;
       u32 profA[2][(QPL && !PAIR) ? PD : 1], profB[2][(QPL && !PAIR) ? PD : 1];
       auto load_profile = [&](u32 (&buf)[2][(QPL && !PAIR) ? PD : 1], u32 sy) __attribute__((always_inline)) {
-        if (PAIR) return;                            // (the pair profile is read at the top of the step it serves: see step())
+        if (PAIR || SPLIT) return;                   // (the pair profile is read at the top of the step it serves, the split tables by quarters: see step())
         const u32 cd = sy & 0x000F000Fu;
         // (the offsets are multiples of 16 RP: the rows keep the alignment of l RP, which the compiler cannot see through the feed --
         //  so the FEED2 form spells the wide LDS reads out)
@@ -493,11 +533,21 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
 #pragma unroll
         for (int k = 0; k < ((QPL && !PAIR) ? PD : 1); ++k) { buf[0][k] = a[k]; buf[1][k] = b[k]; }
       };
+      // SPLIT: one quarter (4 rows) of both tables; `sy` = the byte offsets of target A's block of LO and target B's block of HI
+      u32 sq0l[4] = {0, 0, 0, 0}, sq0h[4] = {0, 0, 0, 0};         // quarter 0 of the coming step, requested a step early
+      const uint8_t * const sp_lane = reinterpret_cast<const uint8_t *>(QP) + l * 16;
+      auto split_read = [&](u32 * lo, u32 * hi, u32 sy, int k) __attribute__((always_inline)) {
+        const uint4 va = *reinterpret_cast<const uint4 *>(sp_lane + (sy & 0xFFFFu) + k * 256);
+        const uint4 vb = *reinterpret_cast<const uint4 *>(sp_lane + (sy >> 16) + k * 256);
+        lo[0] = va.x; lo[1] = va.y; lo[2] = va.z; lo[3] = va.w;
+        hi[0] = vb.x; hi[1] = vb.y; hi[2] = vb.z; hi[3] = vb.w;
+      };
       if (QPL)
         {
           build_feed(0, std::false_type {});
           sym = dpp_shr1(FEED4[gw * 16].x, 0u);           // the symbols of step 0
           load_profile(profA, sym);
+          if (SPLIT) split_read(sq0l, sq0h, sym, 0);
         }
 
       const uint4 * const feed4_g = FEED4 + gw * 16;
@@ -562,13 +612,28 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               load_profile(pn, symn);
             }
           else sym = dpp_shr1(fv.x, sym);
+          // SPLIT: quarter 0 of this step arrived with the last one.  Outside the steady loop a lane may sit this step out and work in the
+          // next, so quarter 0 of the next step is requested here, by all lanes; the steady loop requests it late (see the row loop)
+          u32 sc0l[4], sc0h[4];
+#pragma unroll
+          for (int z = 0; z < 4; ++z) { sc0l[z] = sq0l[z]; sc0h[z] = sq0h[z]; }
+          if (SPLIT && !STEADY) split_read(sq0l, sq0h, symn, 0);
           if (!INTERIOR)
             {
               if (FEED2)
                 {
-                  const uint2 fb = FEEDB[fo + gw * 16 + (t & 15)];
-                  qrt = dpp_shr1(fb.x, qrt); rt = dpp_shr1(fb.y, rt);
                   symf = dpp_shr1(fv.y, symf);
+                  if (SPLIT)
+                    {
+                      // (a lane that has not shifted a column in yet holds symf = 0: the interior pair, as the shifted registers would)
+                      const u32 em = a_pk_ashr15(symf << 5);                        // bit 10 (column >= D - 1)
+                      qrt = a_bfi_v(em, pack16(P.qrt_r), qrt_i_pk); rt = a_bfi_v(em, pack16(P.rt_r), pack16(P.rt_i));
+                    }
+                  else
+                    {
+                      const uint2 fb = FEEDB[fo + gw * 16 + (t & 15)];
+                      qrt = dpp_shr1(fb.x, qrt); rt = dpp_shr1(fb.y, rt);
+                    }
                 }
               else { qrt = dpp_shr1(fv.y, qrt); rt = dpp_shr1(fv.z, rt); }
             }
@@ -583,6 +648,13 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               const int16_t * qpA = QP + (code & 0xFu) * (16 * R) + l * R;
               const int16_t * qpB = QP + (code >> 16) * (16 * R) + l * R;
               u32 pa = 0, pb = 0;                                               // two rows' scores per dword
+              u32 spl[SPLIT ? RP : 1], sph[SPLIT ? RP : 1];                     // SPLIT: this step's rows of LO / HI
+              if (SPLIT)
+                {
+#pragma unroll
+                  for (int z = 0; z < 4; ++z) { spl[SPLIT ? z : 0] = sc0l[z]; sph[SPLIT ? z : 0] = sc0h[z]; }
+                  if (NQT > 1) split_read(spl + (SPLIT ? 4 : 0), sph + (SPLIT ? 4 : 0), sym, 1);
+                }
               u32 Hd = diag;
               u32 F = inF;
               u32 smn = 0x7FFF7FFFu, smx = 0x80008000u;
@@ -604,8 +676,17 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
 #pragma unroll
               for (int r = 0; r < R; ++r)
                 {
-                  u32 V;
-                  if (PAIR) V = pp[r];
+                  u32 V = 0;
+                  if (SPLIT)
+                    {
+                      // quarter k + 2 is requested when quarter k has been consumed; before the last quarter, quarter 0 of the next step
+                      if ((r & 3) == 0 && r > 0)
+                        {
+                          if (r / 4 + 1 < NQT) split_read(spl + (SPLIT ? r + 4 : 0), sph + (SPLIT ? r + 4 : 0), sym, r / 4 + 1);
+                          else if (STEADY) split_read(sq0l, sq0h, symn, 0);
+                        }
+                    }
+                  else if (PAIR) V = pp[r];
                   else if (QPL)
                     {
                       if ((r & 3) == 0) { pa = pc[0][r >> 2]; pb = pc[1][r >> 2]; }
@@ -636,7 +717,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
                       else V = (u32) (uint16_t) qpA[r] | ((u32) (uint16_t) qpB[r] << 16);
                     }
                   // onestep (:765-780)
-                  const u32 h0 = vadd(Hd, V);
+                  const u32 h0 = SPLIT ? Hd + spl[SPLIT ? r : 0] + sph[SPLIT ? r : 0] : vadd(Hd, V);       // (SPLIT: v_add3_u32)
                   // (row R-1 keeps the two-step maximum where the leave-column tracking needs h1 = max(h0, F) on its own: the steps of
                   //  phase B.  In the interior steps of the MAX3 class the tracking reads ext-left alone -- LASTFAST below)
                   const bool ONE_MAX = MAX3 && (r < R - 1 || LASTFAST);     // (folds after unrolling)
@@ -2251,6 +2332,17 @@ static hipError_t launch_fwd2(int track, int nq, int one, const VsxDevParams & P
         }
       else return hipErrorInvalidValue;
     }
+  if (nq == 16)
+    {
+      // the split-profile classes: whole-wave single-strip MAX3 tasks whose targets are all plain A / C / G / T
+      if (!(P.tilt != 0 && P.max3 && !track && one)) return hipErrorInvalidValue;
+      if constexpr (VSX_SPLIT_ROWS(R))
+        {
+          VSX_FWD_GO(ntasks, R, false, true, true, 1, false, true, true);
+          return hipGetLastError();
+        }
+      else return hipErrorInvalidValue;
+    }
   if (nq != 1)
     {
       // the sparse-task classes (NQ tasks per wave): TILT family only, R >= 4 (a one-row-per-lane wave has nothing to share)
@@ -2288,6 +2380,7 @@ static hipError_t launch_fwd2(int track, int nq, int one, const VsxDevParams & P
 
 // nq = tasks per wave: 1, or 2 / 4 for the sparse-task classes (tasks of <= 4 / <= 2 targets, TILT family, single-strip queries);
 // 8 = the pair-profile class: workgroups of four whole-wave tasks of one pure-ACGT query (ntasks a multiple of 4)
+// 16 = the split-profile class: whole-wave tasks with plain-ACGT targets, MAX3 and single-strip (rows in VSX_SPLIT_ROWS)
 // one != 0: every task of the launch is a single-strip query (ONE)
 extern "C" hipError_t vsx_launch_forward(int rows, int track, int nq, int one, VsxDevParams P, const VsxTask * d_tasks, uint32_t ntasks,
                                          const uint8_t * q, const uint8_t * t, uint32_t * dir, uint2 * strip,

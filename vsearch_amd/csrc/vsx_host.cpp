@@ -1063,6 +1063,10 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
   //  a search's windows never have one, and every new query set used to pay a purity pass with a device-wide synchronisation)
   static const bool pair_env = std::getenv("VSX_PAIRPROF") ? std::strcmp(std::getenv("VSX_PAIRPROF"), "0") != 0 : (VSX_PAIRPROF_DEFAULT != 0);
   const bool pair_try = pair_env && n_pairs >= 32;
+  // split-profile classes (vsx_forward_kernel SPLIT): a whole-wave single-strip MAX3 task whose TARGETS are all plain A / C / G / T reads
+  // its scores from two dword tables, LO[sym][row] and HI[sym][row] = score << 16, and adds both to the diagonal in one v_add3_u32 (5
+  // instead of 6 instructions per lane-row).  Needs the purity of the target set only (once per set).  VSX_SPLITPROF=0 switches it off
+  static const bool split_env = !(std::getenv("VSX_SPLITPROF") && std::strcmp(std::getenv("VSX_SPLITPROF"), "0") == 0);
 
   std::unique_ptr<vsx_plan> pl(new vsx_plan);
   pl->ctx = ctx; pl->Q = queries; pl->T = targets; pl->n_pairs = n_pairs;
@@ -1323,6 +1327,34 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
           if (pt.nq == 2 || pt.nq == 4)
             for (const Key & c : ks)
               if (c.count < sparse_min && pt.nq == c.nq && pt.rows == c.rows && pt.track == c.track && pt.tilt == c.tilt) { pt.nq = 1; break; }
+    }
+  // split-profile classes: what the PAIR groups and the sparse classes left in the whole-wave MAX3 class, single-strip, in a row class
+  // that has the kernel, every target plain ACGT -> nq = 16.  After the merging of sparse row classes above, so that the byte-profile
+  // tasks merge exactly as they would without this class and a task that moved to a denser row class joins with its new row count
+  if (split_env)
+    {
+      auto split_shape = [&](const ProtoTask & pt) {
+        return pt.nq == 1 && pt.tilt == 2 && VSX_SPLIT_ROWS(pt.rows) && (int64_t) queries->len[pt.q] <= 16ll * pt.rows;
+      };
+      bool any = false;
+      for (size_t x = 0; x < protos.size() && !any; ++x) any = split_shape(protos[x]);
+      if (any)
+        {
+          const int rc = ensure_impure(targets);
+          if (rc != VSX_OK) return rc;
+          const int nts = (int) std::max<size_t>(1, std::min<size_t>((size_t) vsx_internal_usable_cpus(), protos.size() / 4096));
+          run_threads(nts, [&](int th) {
+            const size_t lo = protos.size() * (size_t) th / (size_t) nts, hi = protos.size() * (size_t) (th + 1) / (size_t) nts;
+            for (size_t x = lo; x < hi; ++x)
+              {
+                ProtoTask & pt = protos[x];
+                if (!split_shape(pt)) continue;
+                bool pure = true;
+                for (uint32_t sidx = 0; sidx < pt.n && pure; ++sidx) pure = !targets->impure[tidx[pt.pair[sidx]]];
+                if (pure) pt.nq = 16;
+              }
+          });
+        }
     }
   // kernel classes together (one launch per class and chunk)
   auto by_class = [](const ProtoTask & a, const ProtoTask & b) {
@@ -1624,7 +1656,7 @@ int vsx_plan_run(vsx_plan * pl)
           VsxDevParams Pf = L.tilt ? ctx->Pt : ctx->P;
           Pf.max3 = (L.tilt == 2) ? 1 : 0;
           static const bool one_off = std::getenv("VSX_ONESTRIP") && std::strcmp(std::getenv("VSX_ONESTRIP"), "0") == 0;      // A/B, tests: the general kernels
-          VSX_HIP(vsx_launch_forward(L.rows, L.track, L.nq, (L.multi || (one_off && L.nq != 8)) ? 0 : 1, Pf, pl->d_tasks.p + L.first, L.count,
+          VSX_HIP(vsx_launch_forward(L.rows, L.track, L.nq, (L.multi || (one_off && L.nq < 8)) ? 0 : 1, Pf, pl->d_tasks.p + L.first, L.count,
                                     pl->Q->codes(), pl->T->codes(), dir, pl->d_strip.p,
                                     pl->d_slot.p + (size_t) L.first * VSX_TASK_SLOTS, st));
         }
@@ -1701,6 +1733,7 @@ int vsx_plan_describe(const vsx_plan * pl, vsx_plan_info * info)
       {
         if (L.nq == 2 || L.nq == 4) info->tasks_sparse += L.count;
         if (L.nq == 8) info->tasks_pair += L.count;
+        if (L.nq == 16) info->tasks_split += L.count;
         info->waves += (L.nq == 2 || L.nq == 4) ? (L.count + (uint32_t) L.nq - 1) / (uint32_t) L.nq : L.count;
         if (L.tilt) info->tasks_tilted += L.count;
         if (L.tilt == 2) info->tasks_max3 += L.count;

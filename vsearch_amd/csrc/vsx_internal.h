@@ -26,6 +26,9 @@
 #define VSX_MID_MIN_ROWS 18
 #endif
 #define VSX_MID(R_, TILT_) ((TILT_) && (R_) >= VSX_MID_MIN_ROWS)
+// Row counts that have a split-profile DP kernel (vsx_forward_kernel SPLIT; the planner's class 16): the ones measured faster than the
+// byte profile.  R = 16 holds 8 KB of tables + 2 KB of feed = 10 240 B of LDS per wave (16 waves per CU), R = 10 6 KB + 2 KB.
+#define VSX_SPLIT_ROWS(R_) ((R_) == 10 || (R_) == 16)
 
 // Device-side constants derived from the 14 post-fixup penalties (reference search16_init,
 // core/align_simd.cpp:1282-1376 and the QR/R vectors at :1629-1649).  "pk" = the int16 value
@@ -189,7 +192,8 @@ hipError_t vsx_launch_encode(const uint8_t * d_ascii, uint8_t * d_codes, uint64_
 hipError_t vsx_launch_purity(const uint8_t * d_codes, const uint64_t * d_off, const uint32_t * d_len,
                              uint64_t nseq, uint8_t * d_impure, hipStream_t st);
 // rows must be one of vsx_supported_rows(); track == 0 selects the variant without overflow (H min/max) tracking
-// nq = tasks per wave (1; 2 / 4 = the sparse-task classes of the TILT family: tasks of <= 4 / <= 2 targets in their first slots)
+// nq = tasks per wave (1; 2 / 4 = the sparse-task classes of the TILT family: tasks of <= 4 / <= 2 targets in their first slots);
+// 8 = the pair-profile class, 16 = the split-profile class (whole-wave single-strip MAX3 tasks with plain-ACGT targets, VSX_SPLIT_ROWS)
 hipError_t vsx_launch_forward(int rows, int track, int nq, int one /* every task single-strip */, VsxDevParams P, const VsxTask * d_tasks, uint32_t ntasks,
                               const uint8_t * d_qcodes, const uint8_t * d_tcodes,
                               uint32_t * d_dir, uint2 * d_strip, VsxSlotOut * d_slot, hipStream_t st);
