@@ -40,6 +40,9 @@ FILTER_SYMBOLS = ["vsx_fastx_filter_opts_default", "vsx_fastx_filter", "vsx_fast
 # include/vsx_eestats.h
 EESTATS_SYMBOLS = ["vsx_fastq_eestats_opts_default", "vsx_fastq_eestats", "vsx_fastq_eestats_out_free", "vsx_fastq_eestats_last_stats"]
 EESTATS_WANT_EESTATS, EESTATS_WANT_EESTATS2 = 1, 2
+# include/vsx_fastq_stats.h
+FASTQ_STATS_SYMBOLS = ["vsx_fastq_stats_opts_default", "vsx_fastq_stats", "vsx_fastq_stats_out_free", "vsx_fastq_stats_last_stats",
+                       "vsx_fastq_chars_opts_default", "vsx_fastq_chars", "vsx_fastq_chars_out_free", "vsx_fastq_chars_last_stats"]
 
 
 class Candidates(C.Structure):
@@ -202,6 +205,43 @@ class EEStatsStats(C.Structure):
     """vsx_fastq_eestats_stats (include/vsx_eestats.h)"""
     _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_walk", "seconds_sum", "seconds_quantile",
                                           "seconds_d2h_output", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("reads", "windows", "reads_host")]
+
+
+class FastqStatsOpts(C.Structure):
+    """vsx_fastq_stats_opts (include/vsx_fastq_stats.h)"""
+    _fields_ = [(n, C.c_int64) for n in ("ascii", "qmin", "qmax", "window")]
+
+
+class FastqStatsOut(C.Structure):
+    """vsx_fastq_stats_out (include/vsx_fastq_stats.h)"""
+    _fields_ = [("n", C.c_uint64), ("symbols", C.c_uint64), ("len_min", C.c_uint64), ("len_max", C.c_uint64),
+                ("length_counts", C.POINTER(C.c_uint64)), ("symbol_counts", C.POINTER(C.c_uint64)), ("sum_ee", C.POINTER(C.c_double)),
+                ("ee_counts", C.POINTER(C.c_uint64)), ("q_counts", C.POINTER(C.c_uint64))]
+
+
+class FastqStatsStats(C.Structure):
+    """vsx_fastq_stats_stats (include/vsx_fastq_stats.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_walk", "seconds_sum", "seconds_d2h_output",
+                                          "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("reads", "windows", "reads_host")]
+
+
+class FastqCharsOpts(C.Structure):
+    """vsx_fastq_chars_opts (include/vsx_fastq_stats.h)"""
+    _fields_ = [("tail", C.c_int64), ("window", C.c_int64)]
+
+
+class FastqCharsOut(C.Structure):
+    """vsx_fastq_chars_out (include/vsx_fastq_stats.h)"""
+    _fields_ = [("n", C.c_uint64), ("total_chars", C.c_uint64), ("seq_counts", C.c_uint64 * 256), ("qual_counts", C.c_uint64 * 256),
+                ("tail_counts", C.c_uint64 * 256), ("maxrun", C.c_int32 * 256), ("qmin_n", C.c_uint8), ("qmax_n", C.c_uint8),
+                ("pad", C.c_uint8 * 6)]
+
+
+class FastqCharsStats(C.Structure):
+    """vsx_fastq_chars_stats (include/vsx_fastq_stats.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_kernel", "seconds_d2h_output", "seconds_total")] + \
                [(n, C.c_uint64) for n in ("reads", "windows", "reads_host")]
 
 
@@ -395,6 +435,20 @@ def load():
     lib.vsx_fastq_eestats_out_free.restype = None
     lib.vsx_fastq_eestats_last_stats.argtypes = [C.POINTER(EEStatsStats)]
     lib.vsx_fastq_eestats_last_stats.restype = None
+    lib.vsx_fastq_stats_opts_default.argtypes = [C.POINTER(FastqStatsOpts)]
+    lib.vsx_fastq_stats_opts_default.restype = None
+    lib.vsx_fastq_stats.argtypes = [vp, C.POINTER(FastqStatsOpts), C.c_uint64, C.POINTER(FilterReads), C.POINTER(FastqStatsOut)]
+    lib.vsx_fastq_stats_out_free.argtypes = [C.POINTER(FastqStatsOut)]
+    lib.vsx_fastq_stats_out_free.restype = None
+    lib.vsx_fastq_stats_last_stats.argtypes = [C.POINTER(FastqStatsStats)]
+    lib.vsx_fastq_stats_last_stats.restype = None
+    lib.vsx_fastq_chars_opts_default.argtypes = [C.POINTER(FastqCharsOpts)]
+    lib.vsx_fastq_chars_opts_default.restype = None
+    lib.vsx_fastq_chars.argtypes = [vp, C.POINTER(FastqCharsOpts), C.c_uint64, C.POINTER(FilterReads), C.POINTER(FastqCharsOut)]
+    lib.vsx_fastq_chars_out_free.argtypes = [C.POINTER(FastqCharsOut)]
+    lib.vsx_fastq_chars_out_free.restype = None
+    lib.vsx_fastq_chars_last_stats.argtypes = [C.POINTER(FastqCharsStats)]
+    lib.vsx_fastq_chars_last_stats.restype = None
     _lib = lib
     return lib
 
