@@ -152,6 +152,44 @@ int vsx_search_batch_meta(vsx_searcher * s, uint64_t n_queries, const char * qbl
                           const uint64_t * qoffsets, const uint32_t * qlengths, const vsx_seq_meta * qmeta, vsx_hits * out);
 void vsx_hits_free(vsx_hits * h);
 
+/* ---- exact sequence search: --search_exact (commands/search_exact.cpp, core/dbhash.cpp; vsx_exact.cpp / vsx_exact.hip) ----
+   A query strand matches a database sequence iff the lengths are equal and every position has the same 4-bit code
+   (chrmap_4bit, utils/seqcmp.cpp): case-blind, U = T, an ambiguity code equals only itself.  The database is the searcher's text
+   as indexed (vsx_searcher_db_text); the queries are masked per strand as vsx_search_batch masks them, which changes a result
+   only with --hardmask (masked symbols are 'N').  EVERY match is evaluated: it passes search_acceptable_unaligned with the
+   query's annotations and, as a finished hit with id 100, search_acceptable_aligned; the accepted ones are returned, ordered by
+   target (a query that matches one target on both strands: plus first).  The hit is fixed: nwscore = qlen x match score,
+   alignment length = matches = shortest = longest = qlen, no differences, every identity 100.0, CIGAR "<qlen>M".
+   Honoured: strand_both, soft_mask / qmask / hardmask, the unaligned and aligned filters, self, window (queries per device
+   window, 0 = 65 536), threads.  Ignored: id, weak_id, maxaccepts, maxrejects, wordlength, minwordmatches.
+   The exact index -- code words of the database, their 64-bit hashes, an open-addressing table -- is built on the device by the
+   first call and lives in the searcher; the k-mer index is not built.  A zero-length query or database sequence matches nothing.
+   Environment: VSX_EXACT=host answers with the host restatement (a std::unordered_multimap over the code strings);
+   VSX_EXACT_HASH_BITS=n (1 .. 64, read when the index is built) keeps the low n bits of every hash, so that chains of false
+   candidates form and the comparison alone decides (tests).  Not re-entrant per searcher. */
+int vsx_search_exact(vsx_searcher * s, uint64_t n_queries, const char * qblob, uint64_t qblob_bytes,
+                     const uint64_t * offsets, const uint32_t * lengths, const vsx_seq_meta * meta /* may be NULL */, vsx_hits * out);
+/* accounting of the calling thread's last vsx_search_exact */
+typedef struct vsx_exact_stats {
+  double   seconds_index;        /* index build; non-zero in the call that built it */
+  double   seconds_stage;        /* masking and staging of the query windows (host) */
+  double   seconds_kernel;       /* hash + probe kernels (device time) */
+  double   seconds_marshal;      /* sorting, filters, hit records, the result's arrays */
+  double   seconds_total;
+  uint64_t windows;
+  uint64_t queries_device, queries_host;      /* answered by the kernels / by the host restatement */
+  uint64_t strands_probed, slots_visited, candidates_compared;
+  uint64_t hits, queries_matched;             /* accepted hits, queries with at least one */
+} vsx_exact_stats;
+void vsx_search_exact_last_stats(vsx_exact_stats * out);
+/* For tests / tooling: the host restatement of the whole call on a database given as text; no device, no context.  The database
+   is masked as vsx_searcher_create masks it for --hardmask (without --hardmask no masking changes a match). */
+int vsx_internal_search_exact_host(const vsx_scoring * scoring, const vsx_search_opts * opts, uint64_t n, const char * blob,
+                                   uint64_t blob_bytes, const uint64_t * offsets, const uint32_t * lengths,
+                                   const vsx_seq_meta * db_meta /* may be NULL */, uint64_t n_queries, const char * qblob,
+                                   uint64_t qblob_bytes, const uint64_t * qoffsets, const uint32_t * qlengths,
+                                   const vsx_seq_meta * qmeta /* may be NULL */, vsx_hits * out);
+
 /* DUST-mask sequences in place, as dust() of the reference does (core/mask.cpp:127-199): everything upper case, the
    low-complexity intervals lower case.  Host threads (threads <= 0: all usable CPUs); sequences must not overlap.  What
    soft_mask = 2 applies to the queries; exported for callers that prepare their own text. */

@@ -5,7 +5,7 @@ The package is a thin host-side mirror of the reference's aligner interface over
 """
 from .aligner import (Aligner, SequenceSet, Plan, AlignmentResults, RawResults, DEFAULT_SCORING,  # noqa: F401
                       scoring_from_tuple, cigar_from_runs)
-from .search import SearchSession, msa, msa_batch, dust_mask  # noqa: F401
+from .search import SearchSession, msa, msa_batch, dust_mask, exact_summary, search_exact_host  # noqa: F401
 from .chimera import ChimeraSession, ChimerasDenovoSession, DenovoChimeraSession  # noqa: F401
 from .merge import merge_pairs, MergeResult, MERGE_REASONS  # noqa: F401
 from .filter import filter_reads, FilterResult  # noqa: F401
@@ -14,4 +14,4 @@ from .fastq_stats import fastq_stats, fastq_chars, FastqStatsResult, FastqCharsR
 from ._lib import SENTINEL, VsxError, load as load_library  # noqa: F401
 
 __all__ = ["Aligner", "SequenceSet", "Plan", "AlignmentResults", "RawResults", "cigar_from_runs", "DEFAULT_SCORING", "scoring_from_tuple",
-           "SearchSession", "ChimeraSession", "DenovoChimeraSession", "ChimerasDenovoSession", "merge_pairs", "MergeResult", "MERGE_REASONS", "filter_reads", "FilterResult", "read_stats", "EEStatsResult", "fastq_stats", "fastq_chars", "FastqStatsResult", "FastqCharsResult", "SENTINEL", "VsxError", "load_library"]
+           "SearchSession", "exact_summary", "search_exact_host", "ChimeraSession", "DenovoChimeraSession", "ChimerasDenovoSession", "merge_pairs", "MergeResult", "MERGE_REASONS", "filter_reads", "FilterResult", "read_stats", "EEStatsResult", "fastq_stats", "fastq_chars", "FastqStatsResult", "FastqCharsResult", "SENTINEL", "VsxError", "load_library"]

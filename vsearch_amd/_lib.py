@@ -22,6 +22,8 @@ SYMBOLS = [
     "vsx_cigar_from_runs", "vsx_plan_destroy",
     "vsx_align_pairs", "vsx_align_pairs_filtered", "vsx_align_pairs_ranked", "vsx_ranked_free", "vsx_plan_set_filter", "vsx_results_free", "vsx_plan_describe",
 ]
+# include/vsx_search.h, exact sequence search (--search_exact); part of SEARCH_SYMBOLS
+EXACT_SYMBOLS = ["vsx_search_exact", "vsx_search_exact_last_stats", "vsx_internal_search_exact_host"]
 # include/vsx_search.h
 SEARCH_SYMBOLS = ["vsx_search_opts_default", "vsx_searcher_create", "vsx_searcher_destroy", "vsx_searcher_db_text", "vsx_search_batch",
                   "vsx_search_batch_meta", "vsx_searcher_set_meta",
@@ -32,7 +34,7 @@ SEARCH_SYMBOLS = ["vsx_search_opts_default", "vsx_searcher_create", "vsx_searche
                   "vsx_chimera_opts_default", "vsx_uchime_ref", "vsx_chimera_last_stats",
                   "vsx_chimera_denovo_opts_default", "vsx_uchime_denovo", "vsx_chimera_denovo_last_stats",
                   "vsx_chimeras_long_opts_default", "vsx_chimeras_denovo", "vsx_chimeras_denovo_last_stats",
-                  "vsx_internal_chimeras_long_host"]
+                  "vsx_internal_chimeras_long_host"] + EXACT_SYMBOLS
 # include/vsx_merge.h (a list of its own: SYMBOLS stays exactly what include/vsx.h declares; build() checks both)
 MERGE_SYMBOLS = ["vsx_merge_opts_default", "vsx_merge_pairs", "vsx_merge_out_free", "vsx_merge_last_stats"]
 # include/vsx_filter.h
@@ -270,6 +272,13 @@ class Hits(C.Structure):
                 ("seconds_total", C.c_double)]
 
 
+class ExactStats(C.Structure):
+    """vsx_exact_stats (include/vsx_search.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_index", "seconds_stage", "seconds_kernel", "seconds_marshal", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("windows", "queries_device", "queries_host", "strands_probed", "slots_visited",
+                                          "candidates_compared", "hits", "queries_matched")]
+
+
 class Scoring(C.Structure):
     """vsx_scoring: the 14 post-fixup values in search16_init order + n_mismatch."""
     _fields_ = [(n, C.c_int64) for n in (
@@ -449,6 +458,12 @@ def load():
     lib.vsx_fastq_chars_out_free.restype = None
     lib.vsx_fastq_chars_last_stats.argtypes = [C.POINTER(FastqCharsStats)]
     lib.vsx_fastq_chars_last_stats.restype = None
+    lib.vsx_search_exact.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(SeqMeta), C.POINTER(Hits)]
+    lib.vsx_search_exact_last_stats.argtypes = [C.POINTER(ExactStats)]
+    lib.vsx_search_exact_last_stats.restype = None
+    lib.vsx_internal_search_exact_host.argtypes = [C.POINTER(Scoring), C.POINTER(SearchOpts), C.c_uint64, vp, C.c_uint64, vp, vp,
+                                                   C.POINTER(SeqMeta), C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(SeqMeta),
+                                                   C.POINTER(Hits)]
     _lib = lib
     return lib
 

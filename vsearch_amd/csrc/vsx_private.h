@@ -84,6 +84,11 @@ int vsx_internal_denovo_search(VsxDenovo * D, const std::vector<uint32_t> & part
                                uint64_t * pairs, uint64_t * sentinels);
 void vsx_internal_denovo_commit(VsxDenovo * D, const std::vector<uint32_t> & seqnos);
 
+// ---- vsx_exact.cpp -----------------------------------------------------------------------------------------------------------
+// the exact-match index of a searcher (device table + code words, host map), built by the first vsx_search_exact
+struct VsxExactIndex;
+void vsx_internal_exact_index_destroy(VsxExactIndex * X);
+
 // ---- vsx_mask.cpp ------------------------------------------------------------------------------------------------------------
 // DUST of one sequence, for the dispatch layer's per-query masking (the caller owns the scratch copy; hard: --hardmask)
 void vsx_internal_dust_one(char * seq, int64_t len, std::vector<char> & scratch, bool hard = false);

@@ -16,20 +16,6 @@ using vsxp::map4;
 
 namespace vsxs __attribute__((visibility("hidden"))) {
 
-// chrmap_complement, utils/maps.cpp:121-150: IUPAC complement, case kept for the letters that have one, everything else 'N'
-inline char complement(unsigned char c)
-{
-  static const char up[] = "TVGHNNCDNNMNKNNNNYSAABWNRN";    // complement of 'A' .. 'Z'
-  if (c >= 'A' && c <= 'Z') return up[c - 'A'];
-  if (c >= 'a' && c <= 'z')
-    {
-      const char u = up[c - 'a'];
-      const bool kept = std::strchr("abcdghkmnrstuvwy", (int) c) != nullptr;       // letters whose row entry is lower case
-      return kept ? (char) (u | 0x20) : 'N';
-    }
-  return 'N';
-}
-
 // utils/maps.cpp: chrmap_2bit (:156-186), chrmap_mask_ambig (:208-236), chrmap_mask_lower (:239-267), chrmap_4bit
 inline unsigned map2(unsigned char c)
 {
@@ -649,6 +635,7 @@ void vsx_searcher_destroy(vsx_searcher * s)
 {
   if (!s) return;
   vsx_kmer_index_destroy(s->kidx);
+  vsx_internal_exact_index_destroy(s->xidx);
   vsx_seqset_destroy(s->dbset);
   vsx_destroy(s->ctx2);
   vsx_destroy(s->ctx3);

@@ -50,6 +50,7 @@ struct vsx_searcher {
   int threads = 1;
   bool indexed = false;              // the k-mer index is built on first use (allpairs never needs it)
   VsxKmerIndex * kidx = nullptr;     // device index (vsx_kmer.hip), built on first use by the batch search
+  VsxExactIndex * xidx = nullptr;    // exact-match index (vsx_exact.cpp), built on first use by vsx_search_exact
   std::vector<uint64_t> word_total;  // postings per word (statistics of the device index)
   std::vector<uint8_t> is_centroid;  // clustering: which sequences are in the growing index
   std::vector<uint64_t> tsize;       // Database::getabundance of the targets (empty: all 1)
@@ -64,6 +65,20 @@ namespace vsxs __attribute__((visibility("hidden"))) {
 using vsxp::fail;
 using vsxp::now_s;
 using vsxp::run_pool;
+
+// chrmap_complement, utils/maps.cpp:121-150: IUPAC complement, case kept for the letters that have one, everything else 'N'
+inline char complement(unsigned char c)
+{
+  static const char up[] = "TVGHNNCDNNMNKNNNNYSAABWNRN";    // complement of 'A' .. 'Z'
+  if (c >= 'A' && c <= 'Z') return up[c - 'A'];
+  if (c >= 'a' && c <= 'z')
+    {
+      const char u = up[c - 'a'];
+      const bool kept = std::strchr("abcdghkmnrstuvwy", (int) c) != nullptr;       // letters whose row entry is lower case
+      return kept ? (char) (u | 0x20) : 'N';
+    }
+  return 'N';
+}
 
 struct Cand { uint32_t target, count, length; };
 

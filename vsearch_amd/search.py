@@ -271,6 +271,49 @@ class SearchSession:
             lib.vsx_hits_free(C.byref(res))
 
     @staticmethod
+    def _raw_hits(res):
+        """(first, hits, cigar blob) copies of a vsx_hits; the C result is released"""
+        lib = _lib.load()
+        try:
+            n, nh = int(res.n_queries), int(res.n_hits)
+            first = np.ctypeslib.as_array(res.first, shape=(n + 1,)).copy()
+            hits = np.ctypeslib.as_array(res.hit, shape=(max(nh, 1),))[:nh].copy()
+            cig = C.string_at(res.cigar_blob, int(res.cigar_bytes)) if res.cigar_bytes else b""
+            return first, hits, cig
+        finally:
+            lib.vsx_hits_free(C.byref(res))
+
+    def search_exact_raw(self, queries, sizes=None, labels=None):
+        """--search_exact (vsx_search_exact): every database sequence whose 4-bit codes equal a query strand's, filtered like any
+        other hit; (first[n + 1] uint64, hits = structured array of vsx_hit, cigar blob bytes), as search_batch_raw returns.
+        self.exact_stats holds the call's vsx_exact_stats."""
+        lib = _lib.load()
+        blob, off, lens = _blob(queries)
+        res = Hits()
+        m, keep = _meta(sizes, labels, len(lens))
+        check(lib.vsx_search_exact(self.h, len(lens), C.cast(C.c_char_p(blob), C.c_void_p), len(blob), off.ctypes.data_as(C.c_void_p),
+                                   lens.ctypes.data_as(C.c_void_p), C.byref(m) if keep else None, C.byref(res)), "vsx_search_exact")
+        self.exact_stats = exact_last_stats()
+        return self._raw_hits(res)
+
+    def search_exact(self, queries, sizes=None, labels=None):
+        """search_exact_raw as the per-query lists of dicts search_batch returns (userout(..., hits=...) prints them)"""
+        return self.hits_as_lists(*self.search_exact_raw(queries, sizes, labels))
+
+    @staticmethod
+    def exact_uc_lines(queries, qnames, tnames, hits, uc_allhits=False):
+        """the --uc records of --search_exact (core/results.cpp:274-327): an H record per reported hit -- the first one only unless
+        uc_allhits -- and an N record for a query without hits"""
+        lines = []
+        for q, hs in enumerate(hits):
+            for h in (hs if uc_allhits else hs[:1]):
+                strand = "-" if h.get("strand") else "+"
+                lines.append(f"H\t{h['target']}\t{len(queries[q])}\t{h['id']:.1f}\t{strand}\t0\t0\t=\t{qnames[q]}\t{tnames[h['target']]}")
+            if not hs:
+                lines.append(f"N\t*\t*\t*\t.\t*\t*\t*\t{qnames[q]}\t*")
+        return lines
+
+    @staticmethod
     def hits_as_lists(first, hits, cig):
         """(first, hits, cigar blob) -> the per-query lists of dicts search_batch returns"""
         out = []
@@ -329,6 +372,63 @@ class SearchSession:
             for h in hs:
                 lines.append("\t".join(fmt[f](q, h) for f in fields))
         return lines
+
+
+def exact_last_stats():
+    """vsx_exact_stats of the calling thread's last exact search, as a dict"""
+    st = _lib.ExactStats()
+    _lib.load().vsx_search_exact_last_stats(C.byref(st))
+    return {n: getattr(st, n) for n, _ in _lib.ExactStats._fields_}
+
+
+def exact_summary(hits, sizes=None, n_targets=None):
+    """What the reference reports after --search_exact: the matched and not-matched query indices (--matched / --notmatched),
+    the per-target counts of matching queries -- weighted by the queries' abundances when `sizes` is given, as
+    --dbmatched --sizeout writes them; a query counts once for every hit it has (search_exact.cpp: dbmatched[target] += qsize per
+    hit) -- and the two counts of the closing "Matching unique query sequences" / "Matching total query sequences" lines."""
+    matched = [q for q, hs in enumerate(hits) if hs]
+    notmatched = [q for q, hs in enumerate(hits) if not hs]
+    counts = {} if n_targets is None else {t: 0 for t in range(n_targets)}
+    for q, hs in enumerate(hits):
+        for h in hs:
+            counts[h["target"]] = counts.get(h["target"], 0) + (1 if sizes is None else int(sizes[q]))
+    total = len(hits) if sizes is None else sum(int(x) for x in sizes)
+    return dict(matched=matched, notmatched=notmatched, dbmatched=counts,
+                queries_matched=len(matched), queries=len(hits),
+                abundance_matched=sum(1 if sizes is None else int(sizes[q]) for q in matched), abundance=total)
+
+
+def search_exact_host(db, queries, db_sizes=None, db_labels=None, sizes=None, labels=None, scoring=None, raw=False, **opts):
+    """The host restatement of --search_exact on a database given as text (vsx_internal_search_exact_host): no device, no
+    context.  -> the per-query lists of dicts SearchSession.search_exact returns, or with raw=True what search_exact_raw
+    returns.  What the device path is compared to."""
+    from .aligner import DEFAULT_SCORING
+    lib = _lib.load()
+    o = SearchOpts()
+    lib.vsx_search_opts_default(C.byref(o))
+    o.id = 1.0
+    for k, v in opts.items():
+        k = "self" if k == "self_" else k
+        if not hasattr(o, k):
+            raise TypeError(f"unknown search option {k}")
+        setattr(o, k, v)
+    sc = scoring
+    if sc is None:
+        sc = _lib.Scoring()
+        for k, v in DEFAULT_SCORING.items():
+            setattr(sc, k, int(v))
+    dblob, doff, dlens = _blob(db)
+    qblob, qoff, qlens = _blob(queries)
+    dm, dkeep = _meta(db_sizes, db_labels, len(dlens))
+    qm, qkeep = _meta(sizes, labels, len(qlens))
+    res = Hits()
+    check(lib.vsx_internal_search_exact_host(C.byref(sc), C.byref(o), len(dlens), C.cast(C.c_char_p(dblob), C.c_void_p), len(dblob),
+                                             doff.ctypes.data_as(C.c_void_p), dlens.ctypes.data_as(C.c_void_p),
+                                             C.byref(dm) if dkeep else None, len(qlens), C.cast(C.c_char_p(qblob), C.c_void_p),
+                                             len(qblob), qoff.ctypes.data_as(C.c_void_p), qlens.ctypes.data_as(C.c_void_p),
+                                             C.byref(qm) if qkeep else None, C.byref(res)), "vsx_internal_search_exact_host")
+    got = SearchSession._raw_hits(res)
+    return got if raw else SearchSession.hits_as_lists(*got)
 
 
 def _msa_unpack(lib, out):
