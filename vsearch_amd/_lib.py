@@ -47,6 +47,11 @@ FASTQ_STATS_SYMBOLS = ["vsx_fastq_stats_opts_default", "vsx_fastq_stats", "vsx_f
                        "vsx_fastq_chars_opts_default", "vsx_fastq_chars", "vsx_fastq_chars_out_free", "vsx_fastq_chars_last_stats"]
 
 
+# include/vsx_derep.h
+DEREP_SYMBOLS = ["vsx_derep_opts_default", "vsx_derep", "vsx_derep_out_free", "vsx_derep_last_stats", "vsx_internal_derep_thresholds"]
+DEREP_THRESHOLDS = 129             # VSX_DEREP_THRESHOLDS
+
+
 class Candidates(C.Structure):
     """vsx_candidates (include/vsx_search.h)"""
     _fields_ = [("n_queries", C.c_uint64), ("start", C.POINTER(C.c_uint64)), ("target", C.POINTER(C.c_uint32)),
@@ -245,6 +250,30 @@ class FastqCharsStats(C.Structure):
     """vsx_fastq_chars_stats (include/vsx_fastq_stats.h)"""
     _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_kernel", "seconds_d2h_output", "seconds_total")] + \
                [(n, C.c_uint64) for n in ("reads", "windows", "reads_host")]
+
+
+class DerepOpts(C.Structure):
+    """vsx_derep_opts (include/vsx_derep.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("strand_both", "by_label", "want_quality", "qout_max")] + \
+               [(n, C.c_int64) for n in ("minseqlength", "maxseqlength", "minuniquesize", "maxuniquesize", "topn", "ascii", "asciiout",
+                                         "qminout", "qmaxout", "window")]
+
+
+class DerepOut(C.Structure):
+    """vsx_derep_out (include/vsx_derep.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n", "kept", "nucleotides", "shortest", "longest", "discarded_short", "discarded_long",
+                                          "sumsize", "maxsize")] + \
+               [("median", C.c_double), ("selected", C.c_uint64), ("n_clusters", C.c_uint64)] + \
+               [(n, C.POINTER(C.c_uint64)) for n in ("rep", "size", "count", "member_start", "member")] + \
+               [("strand", C.POINTER(C.c_uint8)), ("qual_off", C.POINTER(C.c_uint64)), ("qual_blob", C.POINTER(C.c_char)),
+                ("qual_bytes", C.c_uint64)]
+
+
+class DerepStats(C.Structure):
+    """vsx_derep_stats (include/vsx_derep.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_hash", "seconds_group", "seconds_account",
+                                          "seconds_quality", "seconds_output", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("windows", "slots_visited", "candidates_compared", "reads_host")]
 
 
 class SeqMeta(C.Structure):
@@ -464,6 +493,15 @@ def load():
     lib.vsx_internal_search_exact_host.argtypes = [C.POINTER(Scoring), C.POINTER(SearchOpts), C.c_uint64, vp, C.c_uint64, vp, vp,
                                                    C.POINTER(SeqMeta), C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(SeqMeta),
                                                    C.POINTER(Hits)]
+    lib.vsx_derep_opts_default.argtypes = [C.POINTER(DerepOpts)]
+    lib.vsx_derep_opts_default.restype = None
+    lib.vsx_derep.argtypes = [vp, C.POINTER(DerepOpts), C.c_uint64, C.POINTER(FilterReads), vp, vp, C.POINTER(DerepOut)]
+    lib.vsx_derep_out_free.argtypes = [C.POINTER(DerepOut)]
+    lib.vsx_derep_out_free.restype = None
+    lib.vsx_derep_last_stats.argtypes = [C.POINTER(DerepStats)]
+    lib.vsx_derep_last_stats.restype = None
+    lib.vsx_internal_derep_thresholds.argtypes = [C.POINTER(C.c_double)]
+    lib.vsx_internal_derep_thresholds.restype = None
     _lib = lib
     return lib
 

@@ -21,7 +21,13 @@
 using namespace vsxs;
 using vsxp::DevBuf;
 using vsxp::PinnedBuf;
+using vsxp::ensure_pinned;
 using vsxp::map4;
+using vsxe::Plan;
+using vsxe::plan_items;
+using vsxe::slot_of;
+using vsxe::words_of;
+using vsxe::table_size_for;
 
 #define WHO "vsx_search_exact"
 
@@ -51,56 +57,6 @@ struct VsxExactIndex {
 namespace {
 
 thread_local vsx_exact_stats g_stats;
-
-inline uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
-inline uint64_t words_of(uint32_t len) { return round_up(((uint64_t) len + VSX_EXACT_CHUNK - 1) / VSX_EXACT_CHUNK, 2); }
-inline uint64_t slot_of(uint32_t len) { return round_up(len, 16) + VSX_EXACT_TEXT_PAD; }
-
-template <typename T>
-hipError_t ensure_pinned(PinnedBuf<T> & b, size_t count) { return (b.p && count <= b.n) ? hipSuccess : b.alloc(count + count / 4); }
-
-// the reference's table: a power of two, at most 2/3 full (core/dbhash.cpp: dbhash_open)
-uint64_t table_size_for(uint64_t n)
-{
-  uint64_t size = 1;
-  while (3 * n > 2 * size) size *= 2;
-  return size;
-}
-
-uint64_t hash_mask_from_env()
-{
-  const char * e = std::getenv("VSX_EXACT_HASH_BITS");
-  if (!e) return ~0ull;
-  const long bits = std::strtol(e, nullptr, 10);
-  if (bits < 1 || bits >= 64) return ~0ull;
-  return (1ull << bits) - 1;
-}
-
-// the items of a window of sequences: text slots, word slots; both: items [n, 2n) are the minus strands, staged as text of
-// their own (own_minus: they are masked on their own) or read backwards from the plus strand's slot
-struct Plan { uint64_t n = 0, ns = 0, text_bytes = 0, words = 0; bool both = false, own_minus = false; };
-
-template <typename FLen>
-Plan plan_items(uint64_t n, FLen len, bool both, bool own_minus, VsxExactItem * items)
-{
-  Plan P;
-  P.n = n; P.ns = both ? 2 * n : n; P.both = both; P.own_minus = own_minus;
-  uint64_t t = 0, w = 0;
-  for (uint64_t k = 0; k < n; ++k)
-    {
-      items[k] = VsxExactItem {t, w, len(k), 0u};
-      t += slot_of(len(k)); w += words_of(len(k));
-    }
-  if (both)
-    for (uint64_t k = 0; k < n; ++k)
-      {
-        if (own_minus) { items[n + k] = VsxExactItem {t, w, len(k), 0u}; t += slot_of(len(k)); }
-        else items[n + k] = VsxExactItem {items[k].off, w, len(k), 1u};
-        w += words_of(len(k));
-      }
-  P.text_bytes = t; P.words = w;
-  return P;
-}
 
 // the window's text: the plus strands copied, the minus strands (own_minus) reverse-complemented from the UNMASKED query and
 // every strand masked on its own (core/search.cpp:294-303)
@@ -174,7 +130,7 @@ int build_device_index(vsx_searcher * S, VsxExactIndex & X)
   hipStream_t st = vsx_internal_stream(S->ctx);
   VSX_HIP_AS(WHO, hipEventCreate(&X.ev_a));
   VSX_HIP_AS(WHO, hipEventCreate(&X.ev_b));
-  X.hash_mask = hash_mask_from_env();
+  X.hash_mask = vsxe::hash_mask_from_env("VSX_EXACT_HASH_BITS");
   X.table_size = table_size_for(n);
   VSX_HIP_AS(WHO, X.table.alloc(X.table_size));
   VSX_HIP_AS(WHO, hipMemsetAsync(X.table.p, 0xFF, X.table_size * sizeof(VsxExactSlot), st));

@@ -1,4 +1,5 @@
-// vsx_exact_internal.h -- shared between the exact-search kernels (vsx_exact.hip) and their host side (vsx_exact.cpp).
+// vsx_exact_internal.h -- shared between the exact-search kernels (vsx_exact.hip), their host side (vsx_exact.cpp) and
+// dereplication (vsx_derep.hip, vsx_derep.cpp), which reuses the hash kernel and the staging plan.
 #ifndef VSX_EXACT_INTERNAL_H
 #define VSX_EXACT_INTERNAL_H
 
@@ -53,6 +54,62 @@ hipError_t vsx_launch_exact_probe(const VsxExactItem * d_items, uint32_t n_items
                                   hipStream_t st);
 #ifdef __cplusplus
 }
+#endif
+
+#ifdef __cplusplus
+// ---- the staging plan of a window of sequences, shared by the hosts of the kernels (vsx_exact.cpp, vsx_derep.cpp) -----------------
+#include <cstdlib>
+namespace vsxe {
+
+inline uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
+inline uint64_t words_of(uint32_t len) { return round_up(((uint64_t) len + VSX_EXACT_CHUNK - 1) / VSX_EXACT_CHUNK, 2); }
+inline uint64_t slot_of(uint32_t len) { return round_up(len, 16) + VSX_EXACT_TEXT_PAD; }
+
+// the reference's table: a power of two, at most 2/3 full (core/dbhash.cpp: dbhash_open)
+inline uint64_t table_size_for(uint64_t n)
+{
+  uint64_t size = 1;
+  while (3 * n > 2 * size) size *= 2;
+  return size;
+}
+
+// the hashes cut to the low `bits` bits named by the variable (tests: the comparison alone decides); unset or out of range: all 64
+inline uint64_t hash_mask_from_env(const char * name)
+{
+  const char * e = std::getenv(name);
+  if (!e) return ~0ull;
+  const long bits = std::strtol(e, nullptr, 10);
+  if (bits < 1 || bits >= 64) return ~0ull;
+  return (1ull << bits) - 1;
+}
+
+// the items of a window of sequences: text slots, word slots; both: items [n, 2n) are the minus strands, staged as text of
+// their own (own_minus: they are masked on their own) or read backwards from the plus strand's slot
+struct Plan { uint64_t n = 0, ns = 0, text_bytes = 0, words = 0; bool both = false, own_minus = false; };
+
+template <typename FLen>
+Plan plan_items(uint64_t n, FLen len, bool both, bool own_minus, VsxExactItem * items)
+{
+  Plan P;
+  P.n = n; P.ns = both ? 2 * n : n; P.both = both; P.own_minus = own_minus;
+  uint64_t t = 0, w = 0;
+  for (uint64_t k = 0; k < n; ++k)
+    {
+      items[k] = VsxExactItem {t, w, len(k), 0u};
+      t += slot_of(len(k)); w += words_of(len(k));
+    }
+  if (both)
+    for (uint64_t k = 0; k < n; ++k)
+      {
+        if (own_minus) { items[n + k] = VsxExactItem {t, w, len(k), 0u}; t += slot_of(len(k)); }
+        else items[n + k] = VsxExactItem {items[k].off, w, len(k), 1u};
+        w += words_of(len(k));
+      }
+  P.text_bytes = t; P.words = w;
+  return P;
+}
+
+}  // namespace vsxe
 #endif
 
 #endif

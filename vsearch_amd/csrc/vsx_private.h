@@ -195,6 +195,10 @@ struct PinnedBuf {
   }
 };
 
+// grow-only, with a quarter of headroom: a staging buffer that is filled again window after window
+template <typename T>
+hipError_t ensure_pinned(PinnedBuf<T> & b, size_t count) { return (b.p && count <= b.n) ? hipSuccess : b.alloc(count + count / 4); }
+
 // the error probability of a Phred quality value, as the reference tabulates it (the device never evaluates it: tables are host-built)
 inline double phred_error_probability(int value) { return std::pow(10.0, -value / 10.0); }
 
