@@ -177,7 +177,9 @@ int vsx_plan_describe(const vsx_plan * plan, vsx_plan_info * info);
    copies n_pairs records of VSX_HIT_RECORD_BYTES each {int16 score; uint16 aligned, matches,
    mismatches, gaps, pad; uint32 n_cigar_runs; uint64 cigar_run_offset} into device memory `d_dst`
    (asynchronously on the plan's stream, then waits).  Records of pairs resolved on the host
-   (sentinels / empty query) are filled from the host copy. */
+   (sentinels / empty query) are filled from the host copy.  Both exports first settle the plan's run buffer the way
+   vsx_plan_fetch does: a plan whose alignments needed more run words than the buffer held is resized and run again,
+   so every cigar_run_offset handed out lies inside the exported words (no fetch is needed before an export). */
 #define VSX_HIT_RECORD_BYTES 24
 int vsx_plan_export_hits(vsx_plan * plan, void * d_dst, uint64_t dst_bytes);
 /* The dense run buffer those records point into (cigar_run_offset, n_cigar_runs): n_runs words of (length << 2) | op,

@@ -402,6 +402,8 @@ def load():
     lib.vsx_plan_destroy.argtypes = [vp]
     lib.vsx_plan_destroy.restype = None
     lib.vsx_plan_describe.argtypes = [vp, C.POINTER(PlanInfo)]
+    lib.vsx_internal_settle_counts.argtypes = [vp, C.POINTER(C.c_uint64 * 2)]
+    lib.vsx_internal_export_host.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.vsx_align_pairs.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(Results)]
     lib.vsx_align_pairs_filtered.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(Filter), C.POINTER(Results)]
     lib.vsx_align_pairs_ranked.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(Filter), C.c_int, C.POINTER(Ranked)]

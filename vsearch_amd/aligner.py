@@ -239,6 +239,18 @@ class Plan:
               "vsx_plan_export_runs")
         return int(n.value)
 
+    def export_host(self):
+        """vsx_internal_export_host (tests): vsx_plan_export_hits, then vsx_plan_export_runs, into device scratch of the context, copied
+        to the host -> ((n, 24) uint8 hit records, uint32 run words)"""
+        lib = _lib.load()
+        rec = np.zeros((self.qidx.size, 24), np.uint8)
+        n = C.c_uint64(0)
+        check(lib.vsx_internal_export_host(self.h, _ptr(rec), None, 0, C.byref(n)), "vsx_internal_export_host")
+        runs = np.zeros(int(n.value), np.uint32)
+        if runs.size:
+            check(lib.vsx_internal_export_host(self.h, _ptr(rec), _ptr(runs), runs.size, C.byref(n)), "vsx_internal_export_host")
+        return rec, runs
+
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             _lib.load().vsx_plan_destroy(self.h)
@@ -377,6 +389,13 @@ class Aligner:
             return out
         finally:
             lib.vsx_ranked_free(C.byref(res))
+
+    def settle_counts(self):
+        """vsx_internal_settle_counts: (plans run again because their run buffer overflowed, text kernels run again because the
+        text buffer overflowed) on this context so far; the tests of the VSX_TEST_RUNS_CAP / VSX_TEST_TEXT_CAP hooks read it"""
+        out = (C.c_uint64 * 2)()
+        check(_lib.load().vsx_internal_settle_counts(self.h, C.byref(out)), "vsx_internal_settle_counts")
+        return int(out[0]), int(out[1])
 
     def align(self, q, t):
         """one pair -> (score, aligned, matches, mismatches, gaps, cigar)"""

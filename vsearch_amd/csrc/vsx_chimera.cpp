@@ -466,17 +466,8 @@ int align_pairs(vsx_searcher * S, CallBufs & B, const vsx_seqset * qset, const s
   rc = vsx_plan_export_hits(G.plan, d_hits.p, npairs * sizeof(VsxPairOut));
   if (rc != VSX_OK) return rc;
   uint64_t nruns = 0;
-  if (vsx_plan_export_runs(G.plan, nullptr, 0, &nruns) != VSX_OK)
-    {
-      // the run buffer overflowed: vsx_plan_fetch resizes it and runs the traceback again
-      vsx_results tmp {};
-      rc = vsx_plan_fetch(G.plan, &tmp);
-      vsx_results_free(&tmp);
-      if (rc != VSX_OK) return rc;
-      rc = vsx_plan_export_hits(G.plan, d_hits.p, npairs * sizeof(VsxPairOut));
-      if (rc == VSX_OK) rc = vsx_plan_export_runs(G.plan, nullptr, 0, &nruns);
-      if (rc != VSX_OK) return rc;
-    }
+  rc = vsx_plan_export_runs(G.plan, nullptr, 0, &nruns);          // (the exports themselves re-run a plan whose run buffer overflowed)
+  if (rc != VSX_OK) return rc;
   DevBuf<uint32_t> & d_runs = B.runs;
   VSX_HIP_AS(who, d_runs.ensure(std::max<uint64_t>(nruns, 1)));
   if (nruns) { rc = vsx_plan_export_runs(G.plan, d_runs.p, nruns * 4, &nruns); if (rc != VSX_OK) return rc; }

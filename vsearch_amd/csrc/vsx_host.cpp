@@ -258,6 +258,8 @@ struct vsx_ctx {
   uint8_t * stage = nullptr;
   size_t stage_bytes = 0;
   std::vector<unsigned long long *> cursor_slots;   // idle pinned {run cursor, text cursor} pairs of finished plans
+  // what settle_runs() / settle() had to repeat: [0] plans run again for the run buffer, [1] text kernels run again (vsx_internal_settle_counts)
+  std::atomic<uint64_t> settle_counts[2] {{0}, {0}};
   ~vsx_ctx()
   {
     for (hipEvent_t e : ev_tb) if (e) (void) hipEventDestroy(e);
@@ -934,6 +936,16 @@ int vsx_internal_mask_bits(vsx_ctx * ctx, uint64_t n, const char * blob, uint64_
   return rc;
 }
 
+// test observable (tests/test_gpu_marshal.py): how often this context ran a plan again for its run buffer (out[0]) and a text
+// kernel again for its text buffer (out[1]) since it was created
+int vsx_internal_settle_counts(const vsx_ctx * ctx, uint64_t out[2])
+{
+  if (!ctx || !out) return fail(VSX_EINVAL, "vsx_internal_settle_counts: null argument");
+  out[0] = ctx->settle_counts[0].load();
+  out[1] = ctx->settle_counts[1].load();
+  return VSX_OK;
+}
+
 int vsx_seqset_create_from_device(vsx_ctx * ctx, vsx_seqset ** out, uint64_t n, const void * d_blob,
                                   uint64_t blob_bytes, const uint64_t * offsets, const uint32_t * lengths)
 {
@@ -1531,6 +1543,8 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
     }
   const size_t ngp = pl->pair_ids.size();
   pl->runs_capacity = std::min<uint64_t>(worst_runs, std::max<uint64_t>(16ull << 20, 48ull * ngp)) + 1;
+  // tests: a smaller first capacity (words, the capacity itself) forces settle_runs() to resize and run the plan again
+  if (const char * c = std::getenv("VSX_TEST_RUNS_CAP")) pl->runs_capacity = std::min<uint64_t>(pl->runs_capacity, std::max<uint64_t>(1, std::strtoull(c, nullptr, 10)));
   VSX_HIP(pl->d_tasks.alloc(&ctx->pool, pl->tasks.size()));
   VSX_HIP(pl->d_pair_slot.alloc(&ctx->pool, ngp));
   VSX_HIP(pl->d_pair_ids.alloc(&ctx->pool, ngp));
@@ -1574,6 +1588,8 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
   VSX_HIP(pl->d_runs.alloc(&ctx->pool, pl->runs_capacity));
   // text: <= 6 bytes per run (5 digits + op) + NUL + padding per pair in the worst case; typical alignments need ~2 per run
   pl->text_capacity = std::min<uint64_t>(6 * worst_runs + 8 * (uint64_t) ngp, std::max<uint64_t>(32ull << 20, 128ull * ngp)) + 16;
+  // tests: the same for the text (bytes): settle() resizes and runs the text kernel again
+  if (const char * c = std::getenv("VSX_TEST_TEXT_CAP")) pl->text_capacity = std::min<uint64_t>(pl->text_capacity, std::max<uint64_t>(4, std::strtoull(c, nullptr, 10)));
   VSX_HIP(pl->d_text.alloc(&ctx->pool, pl->text_capacity));
   if (!pl->tasks.empty())
     VSX_HIP(hipMemcpyAsync(pl->d_tasks.p, pl->tasks.data(), pl->tasks.size() * sizeof(VsxTask), hipMemcpyHostToDevice, ctx->stream_up));
@@ -1763,31 +1779,42 @@ struct FetchDest {
   char ** blob; uint64_t * blob_used;      // text is appended at *blob_used (the blob is realloc'ed); offsets are rebased by it
 };
 
-// wait for a plan's kernels; re-run what overflowed (run buffer: the whole plan; text buffer: the formatting kernel)
-static int settle(vsx_plan * pl, unsigned long long & used, unsigned long long & text_used)
+// wait for a plan's kernels; run the whole plan again if its run buffer overflowed (the fetches and the exports share this)
+static int settle_runs(vsx_plan * pl, unsigned long long & used, unsigned long long & text_used)
 {
   vsx_ctx * ctx = pl->ctx;
   if (!pl->ran) { int rc = vsx_plan_run(pl); if (rc != VSX_OK) return rc; }
   int rc = vsx_plan_sync(pl, nullptr);
   if (rc != VSX_OK) return rc;
   VSX_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   used = pl->h_cursor[0]; text_used = pl->h_cursor[1];
   if (used > pl->runs_capacity)
     {
       // the dense run buffer was sized for typical alignments; size it exactly and run again
       pl->runs_capacity = used + 1;
       VSX_HIP(pl->d_runs.alloc(&pl->ctx->pool, pl->runs_capacity));
+      ctx->settle_counts[0].fetch_add(1);
       if ((rc = vsx_plan_run(pl)) != VSX_OK) return rc;
       if ((rc = vsx_plan_sync(pl, nullptr)) != VSX_OK) return rc;
       used = pl->h_cursor[0]; text_used = pl->h_cursor[1];
-      if (used > pl->runs_capacity) return fail(VSX_EHIP, "vsx_plan_fetch: run buffer overflow after resize");
+      if (used > pl->runs_capacity) return fail(VSX_EHIP, "vsx_plan: run buffer overflow after resize");          // (fetches and exports alike)
     }
+  return VSX_OK;
+}
+
+// settle_runs(), then the same for the text buffer: only the formatting kernel runs again
+static int settle(vsx_plan * pl, unsigned long long & used, unsigned long long & text_used)
+{
+  vsx_ctx * ctx = pl->ctx;
+  int rc = settle_runs(pl, used, text_used);
+  if (rc != VSX_OK) return rc;
+  hipStream_t st = ctx->stream;
   if (text_used > pl->text_capacity)
     {
       // same for the text: only the formatting kernel runs again
       pl->text_capacity = text_used + 16;
       VSX_HIP(pl->d_text.alloc(&pl->ctx->pool, pl->text_capacity));
+      ctx->settle_counts[1].fetch_add(1);
       VSX_HIP(hipMemsetAsync(pl->d_cursor.p + 1, 0, sizeof(unsigned long long), st));
       VSX_HIP(vsx_launch_cigar_text(pl->d_out.p, pl->d_pair_ids.p, (uint32_t) pl->pair_ids.size(), pl->d_runs.p, pl->runs_capacity,
                                    pl->d_text.p, pl->text_capacity, pl->d_cursor.p + 1, pl->soa, st));
@@ -2048,15 +2075,16 @@ int vsx_plan_export_hits(vsx_plan * pl, void * d_dst, uint64_t dst_bytes)
   if (!pl || !d_dst) return fail(VSX_EINVAL, "vsx_plan_export_hits: null argument");
   if (!pl->ran) return fail(VSX_EINVAL, "vsx_plan_export_hits: plan has not been run");
   if (dst_bytes < pl->n_pairs * sizeof(VsxPairOut)) return fail(VSX_EINVAL, "vsx_plan_export_hits: destination too small");
-  VSX_HIP(hipSetDevice(pl->ctx->device));
+  // the records are written on the traceback stream; a plan whose run buffer overflowed runs again first (their run offsets
+  // would point past the buffer)
+  unsigned long long used = 0, text_used = 0;
+  const int src = settle_runs(pl, used, text_used);
+  if (src != VSX_OK) return src;
   hipStream_t st = pl->ctx->stream;
-  VSX_HIP(hipEventSynchronize(pl->ev_end));          // the records are written on the traceback stream
   if (!pl->host_patched)
     {
       // pairs answered without DP live on the host: patch them into the device array once; their CIGARs (the Q == 0 closed
       // form, one 'I' run) follow the device runs in the exported run buffer (vsx_plan_export_runs)
-      VSX_HIP(hipEventSynchronize(pl->ev_end));
-      const uint64_t used = pl->h_cursor[0];
       for (size_t h = 0, hc = 0; h < pl->host_pairs.size(); ++h)
         {
           VsxPairOut o = pl->host_out[h];
@@ -2074,10 +2102,9 @@ int vsx_plan_export_runs(vsx_plan * pl, void * d_dst, uint64_t dst_bytes, uint64
 {
   if (!pl || !n_runs) return fail(VSX_EINVAL, "vsx_plan_export_runs: null argument");
   if (!pl->ran) return fail(VSX_EINVAL, "vsx_plan_export_runs: plan has not been run");
-  VSX_HIP(hipSetDevice(pl->ctx->device));
-  VSX_HIP(hipEventSynchronize(pl->ev_end));
-  const uint64_t used = pl->h_cursor[0];
-  if (used > pl->runs_capacity) return fail(VSX_EINVAL, "vsx_plan_export_runs: the run buffer overflowed; call vsx_plan_fetch first (it resizes and re-runs)");
+  unsigned long long used = 0, text_used = 0;
+  const int src = settle_runs(pl, used, text_used);          // (an overflowed run buffer: resized, the plan runs again)
+  if (src != VSX_OK) return src;
   const uint64_t extra = pl->host_cigar_run.size();          // run words of the pairs answered on the host, behind the device's
   *n_runs = used + extra;
   if (!d_dst) return VSX_OK;                     // size query
@@ -2085,6 +2112,29 @@ int vsx_plan_export_runs(vsx_plan * pl, void * d_dst, uint64_t dst_bytes, uint64
   if (used) VSX_HIP(hipMemcpyAsync(d_dst, pl->d_runs.p, used * 4, hipMemcpyDeviceToDevice, pl->ctx->stream));
   if (extra) VSX_HIP(hipMemcpyAsync(static_cast<uint32_t *>(d_dst) + used, pl->host_cigar_run.data(), extra * 4, hipMemcpyHostToDevice, pl->ctx->stream));
   VSX_HIP(hipStreamSynchronize(pl->ctx->stream));
+  return VSX_OK;
+}
+
+// test hook (tests/test_gpu_marshal.py): both exports in the order a rank of the gather makes them -- records, size query, run
+// words -- into device scratch of the plan's context, then copied to the host.  rec_out: n_pairs records; runs_out: room for
+// runs_cap words (nullptr: only *n_runs is reported).
+int vsx_internal_export_host(vsx_plan * pl, void * rec_out, uint32_t * runs_out, uint64_t runs_cap, uint64_t * n_runs)
+{
+  if (!pl || !rec_out || !n_runs) return fail(VSX_EINVAL, "vsx_internal_export_host: null argument");
+  VSX_HIP(hipSetDevice(pl->ctx->device));
+  PoolBuf<uint8_t> d_rec;
+  PoolBuf<uint32_t> d_runs;
+  const uint64_t rec_bytes = pl->n_pairs * sizeof(VsxPairOut);
+  VSX_HIP(d_rec.alloc(&pl->ctx->pool, rec_bytes));
+  int rc = pl->n_pairs ? vsx_plan_export_hits(pl, d_rec.p, rec_bytes) : VSX_OK;
+  if (rc == VSX_OK) rc = vsx_plan_export_runs(pl, nullptr, 0, n_runs);
+  if (rc != VSX_OK) return rc;
+  if (rec_bytes) VSX_HIP(hipMemcpy(rec_out, d_rec.p, rec_bytes, hipMemcpyDeviceToHost));
+  if (!runs_out || *n_runs == 0) return VSX_OK;
+  if (runs_cap < *n_runs) return fail(VSX_EINVAL, "vsx_internal_export_host: destination too small");
+  VSX_HIP(d_runs.alloc(&pl->ctx->pool, *n_runs));
+  if ((rc = vsx_plan_export_runs(pl, d_runs.p, *n_runs * 4, n_runs)) != VSX_OK) return rc;
+  VSX_HIP(hipMemcpy(runs_out, d_runs.p, *n_runs * 4, hipMemcpyDeviceToHost));
   return VSX_OK;
 }
 
