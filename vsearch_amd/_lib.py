@@ -50,6 +50,10 @@ FASTQ_STATS_SYMBOLS = ["vsx_fastq_stats_opts_default", "vsx_fastq_stats", "vsx_f
 # include/vsx_derep.h
 DEREP_SYMBOLS = ["vsx_derep_opts_default", "vsx_derep", "vsx_derep_out_free", "vsx_derep_last_stats", "vsx_internal_derep_thresholds"]
 DEREP_THRESHOLDS = 129             # VSX_DEREP_THRESHOLDS
+# include/vsx_sintax.h
+SINTAX_SYMBOLS = ["vsx_sintax_opts_default", "vsx_sintax", "vsx_sintax_result_free", "vsx_sintax_last_stats", "vsx_internal_sintax_host",
+                  "vsx_internal_sintax_intern"]
+SINTAX_RANKS, SINTAX_ROUNDS, SINTAX_NONE = 9, 100, 0xffffffff
 
 
 class Candidates(C.Structure):
@@ -308,6 +312,29 @@ class ExactStats(C.Structure):
                                           "candidates_compared", "hits", "queries_matched")]
 
 
+class SintaxOpts(C.Structure):
+    """vsx_sintax_opts (include/vsx_sintax.h)"""
+    _fields_ = [("strand_both", C.c_int32), ("sintax_random", C.c_int32), ("want_candidates", C.c_int32), ("pad", C.c_int32),
+                ("randseed", C.c_uint64), ("window", C.c_int64)]
+
+
+class SintaxRecord(C.Structure):
+    _fields_ = [("strand", C.c_int32), ("classified", C.c_int32), ("boot_count", C.c_uint32 * 2), ("best_count", C.c_uint32 * 2),
+                ("rank_seq", C.c_uint32 * SINTAX_RANKS), ("rank_count", C.c_uint32 * SINTAX_RANKS)]
+
+
+class SintaxResult(C.Structure):
+    _fields_ = [("n_queries", C.c_uint64), ("n_classified", C.c_uint64), ("rec", C.POINTER(SintaxRecord)),
+                ("candidates", C.POINTER(C.c_uint32))]
+
+
+class SintaxStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("queries_device", "queries_host_random", "queries_host_wordlength", "queries_host_dblen",
+                                          "queries_host_forced", "windows", "strands_sampled", "rounds_counted", "tiles")] + \
+               [(n, C.c_double) for n in ("seconds_stage", "seconds_sample", "seconds_count", "seconds_vote", "seconds_output",
+                                          "seconds_index", "seconds_total")]
+
+
 class Scoring(C.Structure):
     """vsx_scoring: the 14 post-fixup values in search16_init order + n_mismatch."""
     _fields_ = [(n, C.c_int64) for n in (
@@ -504,6 +531,17 @@ def load():
     lib.vsx_derep_last_stats.restype = None
     lib.vsx_internal_derep_thresholds.argtypes = [C.POINTER(C.c_double)]
     lib.vsx_internal_derep_thresholds.restype = None
+    lib.vsx_sintax_opts_default.argtypes = [C.POINTER(SintaxOpts)]
+    lib.vsx_sintax_opts_default.restype = None
+    lib.vsx_sintax.argtypes = [vp, C.POINTER(SintaxOpts), C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(SintaxResult)]
+    lib.vsx_sintax_result_free.argtypes = [C.POINTER(SintaxResult)]
+    lib.vsx_sintax_result_free.restype = None
+    lib.vsx_sintax_last_stats.argtypes = [C.POINTER(SintaxStats)]
+    lib.vsx_sintax_last_stats.restype = None
+    lib.vsx_internal_sintax_host.argtypes = [C.POINTER(SearchOpts), C.POINTER(SintaxOpts), C.c_uint64, vp, C.c_uint64, vp, vp,
+                                             C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp,
+                                             C.POINTER(SintaxResult)]
+    lib.vsx_internal_sintax_intern.argtypes = [C.c_uint64, C.POINTER(C.c_char_p), vp, vp, vp]
     _lib = lib
     return lib
 

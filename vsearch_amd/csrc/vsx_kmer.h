@@ -45,4 +45,15 @@ int vsx_kmer_count_batch(VsxKmerIndex * ix, uint64_t nq, const uint64_t * qk_sta
                          VsxKmerStats * stats_out = nullptr, bool want_increments = false /* stats.increments costs a serial pass over qk */);
 const VsxKmerStats * vsx_kmer_stats(const VsxKmerIndex * ix);
 
+// a read-only view of a built whole-set index for kernels outside vsx_kmer.hip (vsx_sintax.hip): the bucket table (word-major,
+// bucket = word * ntiles + tile, in 16-byte units, nbuckets + 1 entries) and the units; device pointers, valid until the next
+// rebuild.  packed: the byte-gap format of vsx_kmer_pack.h (word lengths 3..8), tiles of tile_seqs sequences.
+struct VsxKmerView {
+  const void * units = nullptr;
+  const uint64_t * bucket_start = nullptr;
+  uint32_t ntiles = 0, nseq = 0, tile_seqs = 0;
+  bool packed = false;
+};
+int vsx_kmer_index_view(const VsxKmerIndex * ix, VsxKmerView * out);
+
 #endif

@@ -264,6 +264,18 @@ void vsx_kmer_index_destroy(VsxKmerIndex * ix)
 
 const VsxKmerStats * vsx_kmer_stats(const VsxKmerIndex * ix) { return ix ? &ix->stats : nullptr; }
 
+int vsx_kmer_index_view(const VsxKmerIndex * ix, VsxKmerView * out)
+{
+  if (!ix || !out) { vsx_internal_set_error("vsx_kmer_index_view: null argument"); return VSX_EINVAL; }
+  out->units = ix->d_post.p;
+  out->bucket_start = ix->d_start.p;
+  out->ntiles = ix->ntiles;
+  out->nseq = ix->nseq;
+  out->packed = ix->packed;
+  out->tile_seqs = ix->packed ? vsx_kmer_packed_tile_seqs() : (1u << vsx_kmer_tile_shift());
+  return VSX_OK;
+}
+
 namespace {
 
 // one counting + selection pass over `nslots` query slots (slot -> query through qlist, or identity); appends to recs

@@ -89,6 +89,11 @@ void vsx_internal_denovo_commit(VsxDenovo * D, const std::vector<uint32_t> & seq
 struct VsxExactIndex;
 void vsx_internal_exact_index_destroy(VsxExactIndex * X);
 
+// ---- vsx_sintax.cpp ----------------------------------------------------------------------------------------------------------
+// what a searcher keeps for vsx_sintax: the per-rank name ids of its labels (dropped when the labels change) and window buffers
+struct VsxSintaxIndex;
+void vsx_internal_sintax_index_destroy(VsxSintaxIndex * X);
+
 // ---- vsx_mask.cpp ------------------------------------------------------------------------------------------------------------
 // DUST of one sequence, for the dispatch layer's per-query masking (the caller owns the scratch copy; hard: --hardmask)
 void vsx_internal_dust_one(char * seq, int64_t len, std::vector<char> & scratch, bool hard = false);

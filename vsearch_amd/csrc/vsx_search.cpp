@@ -612,6 +612,8 @@ int vsx_searcher_set_meta(vsx_searcher * S, const vsx_seq_meta * meta)
   if (!S) return fail(VSX_EINVAL, "vsx_searcher_set_meta: null searcher");
   S->tsize.clear();
   S->tlabel.clear();
+  vsx_internal_sintax_index_destroy(S->sidx);          // its name ids were cut from the old labels
+  S->sidx = nullptr;
   if (!meta) return VSX_OK;
   const uint64_t n = S->len.size();
   if (meta->abundance) S->tsize.assign(meta->abundance, meta->abundance + n);
@@ -636,6 +638,7 @@ void vsx_searcher_destroy(vsx_searcher * s)
   if (!s) return;
   vsx_kmer_index_destroy(s->kidx);
   vsx_internal_exact_index_destroy(s->xidx);
+  vsx_internal_sintax_index_destroy(s->sidx);
   vsx_seqset_destroy(s->dbset);
   vsx_destroy(s->ctx2);
   vsx_destroy(s->ctx3);
