@@ -54,6 +54,10 @@ DEREP_THRESHOLDS = 129             # VSX_DEREP_THRESHOLDS
 SINTAX_SYMBOLS = ["vsx_sintax_opts_default", "vsx_sintax", "vsx_sintax_result_free", "vsx_sintax_last_stats", "vsx_internal_sintax_host",
                   "vsx_internal_sintax_intern"]
 SINTAX_RANKS, SINTAX_ROUNDS, SINTAX_NONE = 9, 100, 0xffffffff
+# include/vsx_orient.h
+ORIENT_SYMBOLS = ["vsx_orient_opts_default", "vsx_orient_result_free", "vsx_orient_last_stats", "vsx_orient", "vsx_internal_orient_host",
+                  "vsx_internal_orient_matchcounts"]
+ORIENT_MAX_QLEN, ORIENT_CLASSES, ORIENT_CLASS_QLEN = 16384, 3, (512, 4096, 16384)      # VSX_ORIENT_MAX_QLEN, the count kernel's length classes
 
 
 class Candidates(C.Structure):
@@ -335,6 +339,28 @@ class SintaxStats(C.Structure):
                                           "seconds_index", "seconds_total")]
 
 
+class OrientOpts(C.Structure):
+    """vsx_orient_opts (include/vsx_orient.h)"""
+    _fields_ = [("qmask", C.c_int32), ("want_text", C.c_int32), ("window", C.c_int64)]
+
+
+class OrientRecord(C.Structure):
+    _fields_ = [("count_fwd", C.c_uint32), ("count_rev", C.c_uint32), ("strand", C.c_int32)]
+
+
+class OrientResult(C.Structure):
+    _fields_ = [("n_queries", C.c_uint64), ("n_fwd", C.c_uint64), ("n_rev", C.c_uint64), ("n_none", C.c_uint64),
+                ("rec", C.POINTER(OrientRecord)), ("text", C.c_void_p), ("qual", C.c_void_p)]
+
+
+class OrientStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("queries_device", "queries_host_wordlength", "queries_host_qlen", "queries_host_forced")] + \
+               [("queries_class", C.c_uint64 * ORIENT_CLASSES)] + \
+               [(n, C.c_uint64) for n in ("windows", "words_distinct", "build_chunks", "build_keys")] + \
+               [(n, C.c_double) for n in ("seconds_build", "seconds_stage", "seconds_count", "seconds_emit", "seconds_output",
+                                          "seconds_total")]
+
+
 class Scoring(C.Structure):
     """vsx_scoring: the 14 post-fixup values in search16_init order + n_mismatch."""
     _fields_ = [(n, C.c_int64) for n in (
@@ -542,6 +568,16 @@ def load():
                                              C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp,
                                              C.POINTER(SintaxResult)]
     lib.vsx_internal_sintax_intern.argtypes = [C.c_uint64, C.POINTER(C.c_char_p), vp, vp, vp]
+    lib.vsx_orient_opts_default.argtypes = [C.POINTER(OrientOpts)]
+    lib.vsx_orient_opts_default.restype = None
+    lib.vsx_orient.argtypes = [vp, C.POINTER(OrientOpts), C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.POINTER(OrientResult)]
+    lib.vsx_orient_result_free.argtypes = [C.POINTER(OrientResult)]
+    lib.vsx_orient_result_free.restype = None
+    lib.vsx_orient_last_stats.argtypes = [C.POINTER(OrientStats)]
+    lib.vsx_orient_last_stats.restype = None
+    lib.vsx_internal_orient_host.argtypes = [C.POINTER(SearchOpts), C.POINTER(OrientOpts), C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp,
+                                             C.c_uint64, vp, vp, vp, C.POINTER(OrientResult)]
+    lib.vsx_internal_orient_matchcounts.argtypes = [vp, vp, C.c_uint64, vp]
     _lib = lib
     return lib
 

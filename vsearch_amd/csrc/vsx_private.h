@@ -94,6 +94,11 @@ void vsx_internal_exact_index_destroy(VsxExactIndex * X);
 struct VsxSintaxIndex;
 void vsx_internal_sintax_index_destroy(VsxSintaxIndex * X);
 
+// ---- vsx_orient.cpp ----------------------------------------------------------------------------------------------------------
+// what a searcher keeps for vsx_orient: the match-count table of its database (device and host) and window buffers
+struct VsxOrientIndex;
+void vsx_internal_orient_index_destroy(VsxOrientIndex * X);
+
 // ---- vsx_mask.cpp ------------------------------------------------------------------------------------------------------------
 // DUST of one sequence, for the dispatch layer's per-query masking (the caller owns the scratch copy; hard: --hardmask)
 void vsx_internal_dust_one(char * seq, int64_t len, std::vector<char> & scratch, bool hard = false);
