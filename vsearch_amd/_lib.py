@@ -50,6 +50,8 @@ FASTQ_STATS_SYMBOLS = ["vsx_fastq_stats_opts_default", "vsx_fastq_stats", "vsx_f
 # include/vsx_derep.h
 DEREP_SYMBOLS = ["vsx_derep_opts_default", "vsx_derep", "vsx_derep_out_free", "vsx_derep_last_stats", "vsx_internal_derep_thresholds"]
 DEREP_THRESHOLDS = 129             # VSX_DEREP_THRESHOLDS
+# include/vsx_derep_prefix.h
+DEREP_PREFIX_SYMBOLS = ["vsx_derep_prefix_opts_default", "vsx_derep_prefix", "vsx_derep_prefix_out_free", "vsx_derep_prefix_last_stats"]
 # include/vsx_sintax.h
 SINTAX_SYMBOLS = ["vsx_sintax_opts_default", "vsx_sintax", "vsx_sintax_result_free", "vsx_sintax_last_stats", "vsx_internal_sintax_host",
                   "vsx_internal_sintax_intern"]
@@ -282,6 +284,28 @@ class DerepStats(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_hash", "seconds_group", "seconds_account",
                                           "seconds_quality", "seconds_output", "seconds_total")] + \
                [(n, C.c_uint64) for n in ("windows", "slots_visited", "candidates_compared", "reads_host")]
+
+
+class DerepPrefixOpts(C.Structure):
+    """vsx_derep_prefix_opts (include/vsx_derep_prefix.h)"""
+    _fields_ = [("sizein", C.c_int32), ("pad", C.c_int32)] + \
+               [(n, C.c_int64) for n in ("minseqlength", "maxseqlength", "minuniquesize", "maxuniquesize", "topn", "window")]
+
+
+class DerepPrefixOut(C.Structure):
+    """vsx_derep_prefix_out (include/vsx_derep_prefix.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n", "kept", "nucleotides", "shortest", "longest", "discarded_short", "discarded_long",
+                                          "sumsize", "maxsize")] + \
+               [("median", C.c_double), ("selected", C.c_uint64), ("n_clusters", C.c_uint64)] + \
+               [(n, C.POINTER(C.c_uint64)) for n in ("rep", "size", "count", "member_start", "member", "rank")]
+
+
+class DerepPrefixStats(C.Structure):
+    """vsx_derep_prefix_stats (include/vsx_derep_prefix.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_rank", "seconds_stage", "seconds_h2d", "seconds_hash", "seconds_group", "seconds_claim",
+                                          "seconds_resolve", "seconds_output", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("windows", "nodes", "distinct_lengths", "probes", "candidates_compared", "reads_host",
+                                          "host_no_context", "host_environment", "host_read_count", "host_memory")]
 
 
 class SeqMeta(C.Structure):
@@ -557,6 +581,13 @@ def load():
     lib.vsx_derep_last_stats.restype = None
     lib.vsx_internal_derep_thresholds.argtypes = [C.POINTER(C.c_double)]
     lib.vsx_internal_derep_thresholds.restype = None
+    lib.vsx_derep_prefix_opts_default.argtypes = [C.POINTER(DerepPrefixOpts)]
+    lib.vsx_derep_prefix_opts_default.restype = None
+    lib.vsx_derep_prefix.argtypes = [vp, C.POINTER(DerepPrefixOpts), C.c_uint64, C.POINTER(FilterReads), vp, vp, C.POINTER(DerepPrefixOut)]
+    lib.vsx_derep_prefix_out_free.argtypes = [C.POINTER(DerepPrefixOut)]
+    lib.vsx_derep_prefix_out_free.restype = None
+    lib.vsx_derep_prefix_last_stats.argtypes = [C.POINTER(DerepPrefixStats)]
+    lib.vsx_derep_prefix_last_stats.restype = None
     lib.vsx_sintax_opts_default.argtypes = [C.POINTER(SintaxOpts)]
     lib.vsx_sintax_opts_default.restype = None
     lib.vsx_sintax.argtypes = [vp, C.POINTER(SintaxOpts), C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(SintaxResult)]
