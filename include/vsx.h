@@ -104,6 +104,8 @@ typedef struct vsx_timing {
   uint32_t traceback_launches;
   uint64_t cells;           /* sum over pairs of qlen*tlen (DP cells)   */
   uint64_t dir_bytes;       /* direction bytes written by the DP kernel */
+  uint64_t steps_skipped;   /* DP steps the kernel did not run: tasks ended once the rest was a proven right-terminal gap,
+                               summed over the wavefront tasks (0 when no task of the plan is in such a class)      */
 } vsx_timing;
 
 /* How a plan was mapped onto kernel classes (for measurement code: which row body does the dominant launch issue?). */

@@ -429,7 +429,7 @@ class PlanInfo(C.Structure):
 class Timing(C.Structure):
     _fields_ = [("forward_ms", C.c_float), ("traceback_ms", C.c_float), ("total_ms", C.c_float),
                 ("forward_launches", C.c_uint32), ("traceback_launches", C.c_uint32),
-                ("cells", C.c_uint64), ("dir_bytes", C.c_uint64)]
+                ("cells", C.c_uint64), ("dir_bytes", C.c_uint64), ("steps_skipped", C.c_uint64)]
 
 
 class ClusterOut(C.Structure):

@@ -209,6 +209,8 @@ class Plan:
         check(_lib.load().vsx_plan_run(self.h), "vsx_plan_run")
 
     def sync(self):
+        """vsx_plan_sync -> Timing of the last run; its last field, steps_skipped, counts the DP steps the kernel did not run because the
+        rest of a task was a proven right-terminal gap (vsx_forward_kernel EARLY)"""
         t = Timing()
         check(_lib.load().vsx_plan_sync(self.h, C.byref(t)), "vsx_plan_sync")
         return t

@@ -867,6 +867,78 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
           t_switch = __builtin_amdgcn_readfirstlane(dmin == 0x7fffffff ? 0 : dmin - 1) & ~1;
           if (t_switch > steps) t_switch = steps & ~1;
         }
+      // EARLY (the whole-wave single-strip MAX3 classes, with and without SPLIT; planner flag P.es_on): end the task once the rest of
+      // every target is PROVEN to be the right-terminal gap (tests/test_early_stop_math.py).  After step t - 1 a path to
+      // (Q-1, D-1) leaves the computed staircase through a frontier cell p: a cell of a position's current column, its bottom row one
+      // column back (hnext[R-1]: the diagonal successor belongs to the next position) or the top border cell (-1, t - 1).  With rows /
+      // cols = the rows / columns left from p, W0 = M + e (M = the largest score, e = the smallest gap extension) such a path scores
+      // at most  min(H(p) + W0 rows - e cols, H(p) + W0 cols - e rows),  and  LB = E(Q-1, c+1) - (D-2-c) R_q(right), c = t - 1 - l_last,
+      // is the score of extending the last row's own run.  If every p but (Q-1, c) stays strictly below LB, the full run ends with
+      // score = LB and leave = lv1.  Tilted: un-tilting makes the row term linear in the row, so a position's maxima are two Horner
+      // passes over hprev[] in 16-bit halves (weights W0 + g and g - e: the planner proves they cannot wrap); the rest is 32-bit per
+      // lane and half, both sides carrying the common term g (Q-1) + bias.  Looked at only BETWEEN unrolled blocks: first the top
+      // border cell alone (it must pass, and while LB stands still it falls short by P.es_rate per step at most: the next look is
+      // scheduled accordingly), then all positions.  Returns 0 = end the task (score set), else the steps until the next look.
+      constexpr bool EARLY = TILT && MAX3 && ONE && NQ == 1 && !PAIR && !TRACK && R >= 4;
+      bool es_fired = false;
+      const int da_ = DA, db_ = DB;
+      auto early_check = [&](const int tn) __attribute__((always_inline)) -> int {
+        if constexpr (EARLY)
+          {
+            // (per-lane values pass through an empty asm: whatever the check derives from them is formed here, between two blocks, and
+            //  not hoisted into registers held across the unrolled block)
+            int ln = lane, DA = da_, DB = db_;
+            asm volatile("" : "+v"(ln), "+v"(DA), "+v"(DB));
+            const int l = ln & 15;
+            const int t1 = tn - 1, ll = total_lanes - 1, c = t1 - ll;
+            const int W0 = P.es_w0, e = P.es_e, W1 = W0 + tl, W2 = tl - e, rr = P.es_rr;
+            const u32 el = (u32) __builtin_amdgcn_ds_bpermute((ln - l + ll) << 2, (int) E[R - 1]);   // E*(Q-1, c+1) of both targets of the group
+            const int eA = (int) (el & 0xffffu), eB = (int) (el >> 16);
+            const int lbA = eA - tl * (c + 1) - (DA - 2 - c) * rr, lbB = eB - tl * (c + 1) - (DB - 2 - c) * rr;
+            const int top = (int) P.htop[t1] + (int) BIAS16;                       // H*(-1, t1), biased
+            {
+              const int a1 = top + W1 * Q - tl * t1, a2 = top + W2 * Q - tl * t1;
+              const int cA = DA - 1 - t1, cB = DB - 1 - t1;
+              const int uA = a1 - e * cA < a2 + W0 * cA ? a1 - e * cA : a2 + W0 * cA;
+              const int uB = a1 - e * cB < a2 + W0 * cB ? a1 - e * cB : a2 + W0 * cB;
+              const int dA = DA > 0 ? uA - lbA : -1, dB = DB > 0 ? uB - lbB : -1;
+              int d = dA > dB ? dA : dB;                                           // (the same in all 16 lanes of a group)
+              const int d1 = __builtin_amdgcn_readlane(d, 16), d2 = __builtin_amdgcn_readlane(d, 32), d3 = __builtin_amdgcn_readlane(d, 48);
+              d = __builtin_amdgcn_readlane(d, 0);
+              d = d > d1 ? d : d1; d = d > d2 ? d : d2; d = d > d3 ? d : d3;
+              if (d >= 0) { const int w = (d / P.es_rate) & ~15; return w < 16 ? 16 : w; }
+            }
+            const u32 w1pk = pack16(W1), w2pk = pack16(W2);
+            u32 m1 = hprev[0], m2 = hprev[0];
+#pragma unroll
+            for (int r = 1; r < R - 1; ++r) { m1 = pmaxu(m1 + w1pk, hprev[r]); m2 = pmaxu(m2 + w2pk, hprev[r]); }
+            m1 += w1pk; m2 += w2pk;                                                // rows 0 .. R-2: (Q-1, c) itself is the run LB extends
+            if (l < ll)
+              {
+                m1 = pmaxu(pmaxu(m1, hprev[R - 1]), hnext[R - 1] + pack16(tl - e));
+                m2 = pmaxu(pmaxu(m2, hprev[R - 1]), hnext[R - 1] + pack16(tl + W0));
+              }
+            if (l == 0)
+              {
+                m1 = pmaxu(m1, pack16(top + W1 * rc0));
+                m2 = pmaxu(m2, pack16(top + W2 * rc0));
+              }
+            const int j = t1 - l, rb = (ll - l) * R;
+            const int b1 = W1 * rb - tl * j, b2 = W2 * rb - tl * j;
+            const int cA = DA - 1 - j, cB = DB - 1 - j;
+            const int f1A = (int) (m1 & 0xffffu) + b1 - e * cA, f2A = (int) (m2 & 0xffffu) + b2 + W0 * cA;
+            const int f1B = (int) (m1 >> 16) + b1 - e * cB, f2B = (int) (m2 >> 16) + b2 + W0 * cB;
+            const bool okA = DA == 0 || (f1A < f2A ? f1A : f2A) < lbA;
+            const bool okB = DB == 0 || (f1B < f2B ? f1B : f2B) < lbB;
+            if (!__all((l > ll) || (okA && okB))) return 16;
+            // closed form: H*(Q-1, D-1) = E*(Q-1, c+1) - (D-2-c) R'_q(right); an empty slot keeps 0
+            const int sA = DA > 0 ? eA - (DA - 2 - c) * (rr - tl) : 0, sB = DB > 0 ? eB - (DB - 2 - c) * (rr - tl) : 0;
+            score = ((u32) sA & 0xffffu) | ((u32) sB << 16);
+            if (ln == 0 && P.es_skipped != nullptr) atomicAdd(P.es_skipped, (unsigned long long) (steps - tn));
+            return 0;
+          }
+        return 16;
+      };
       int t = 0;
       qrt = qrt_i_pk; rt = pack16(P.rt_i);
       for (; t < t_switch && (TRACK || t < 16); t += 2)       // the pipeline fills (TRACK: the whole interior phase)
@@ -887,8 +959,18 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
           // whole 16-step blocks whose successor block is steady too (t is a multiple of 16 here: the fill loop stops at 16 or at
           // t_switch): every feed slot, the block-boundary work and the row checkpoint offsets are fixed per unrolled step, and the
           // next feed block is built lean
+          int es_next = (EARLY && P.es_on) ? ((Q + 15) & ~15) : 0x7fffffff;      // from t >= Q on: a square-ish task never looks
           for (; t + 32 <= t_switch; t += 16)
             {
+              if constexpr (EARLY)
+                {
+                  if (__builtin_expect(t >= es_next, 0))
+                    {
+                      const int w = early_check(t);
+                      if (w == 0) { es_fired = true; t = steps; break; }          // no further step: the loops below find nothing to do
+                      es_next = t + w;
+                    }
+                }
               const int tb = t & ~15;
 #pragma unroll
               for (int k = 0; k < 16; k += 2)
@@ -903,6 +985,8 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               step(t + 1, hnext, hprev, profB, profA, std::true_type {}, std::true_type {}, std::true_type {});
             }
           lv1 = psubw(lv1, lpk);
+          // EARLY: left(D-1) holds and no column beyond c changes lv1, so the leave column is lv1 as it stands (an empty slot keeps 0)
+          if constexpr (EARLY) { if (es_fired) leave = lv1 & ((DA > 0 ? 0x0000ffffu : 0u) | (DB > 0 ? 0xffff0000u : 0u)); }
         }
       for (; t < steps; t += 2)
         {

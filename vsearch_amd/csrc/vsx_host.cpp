@@ -446,7 +446,7 @@ struct vsx_plan {
   PoolBuf<uint2> d_strip;
   PoolBuf<VsxSlotOut> d_slot;
   PoolBuf<VsxPairOut> d_out;
-  PoolBuf<unsigned long long> d_cursor;  // [0] run words used, [1] text bytes used
+  PoolBuf<unsigned long long> d_cursor;  // [0] run words used, [1] text bytes used, [2] DP steps skipped (vsx_forward_kernel EARLY)
   PoolBuf<uint8_t> d_text, d_soa;        // CIGAR text and the output arrays, written by vsx_cigar_text_kernel (vsx_tbtext.hip)
   // r06, ranked plans: the lists the traceback's epilogue fills (VsxFilterDev::rank_counts ...), see plan_set_ranked()
   PoolBuf<uint32_t> d_rank_counts, d_kept_pair, d_refused_pair;
@@ -800,6 +800,22 @@ int vsx_create(vsx_ctx ** out, const vsx_scoring * s, int device)
           return fail(VSX_EHIP, "vsx_create: %s", hipGetErrorString(e));
         }
       T.htop = c->d_htop_t.p; T.hleft = c->d_hleft_t.p; T.matrix = c->d_matrix_t.p;
+      // EARLY (vsx_forward_kernel): the whole-wave single-strip MAX3 kernels end a task once the rest is a proven right-terminal gap.
+      // The proof prices every move of an unseen path at M = the largest matrix entry (the ambiguous symbols' 0 included) per diagonal and
+      // e = the smallest of the six extensions per gap column or row, charging no open: all twelve gap penalties must be >= 0.  The
+      // kernel's 16-bit sums add at most (M + e + g) (R - 1) <= 31 (M + e + g), (M + e + g) rows of position 0 <= 32 (M + e + g) or
+      // g + M + e to a value <= 0x7BFF: they stay inside a half when 32 (M + e + g) <= 0xFFFF - 0x7BFF.
+      {
+        bool ok = true;
+        for (int k = 0; k < 12; ++k) ok = ok && c->pen[k] >= 0;
+        const int e_min = std::min({geql, getl, geqi, geti, geqr, getr});
+        const int w0 = std::max({match, mism, 0}) + e_min;
+        if (ok && 32 * (w0 + g) <= 0xFFFF - 0x7BFF)
+          {
+            T.es_on = 1; T.es_w0 = w0; T.es_e = e_min; T.es_rr = geqr;
+            T.es_rate = std::max(1, w0 + geql);
+          }
+      }
     }
   { std::lock_guard<std::mutex> lk(g_ctx_mu); g_ctxs.push_back(c); }
   *out = c;
@@ -1551,7 +1567,7 @@ int vsx_plan_create(vsx_ctx * ctx, vsx_plan ** out, const vsx_seqset * queries, 
   VSX_HIP(pl->d_slab_off.alloc(&ctx->pool, ngp));
   VSX_HIP(pl->d_slot.alloc(&ctx->pool, pl->tasks.size() * VSX_TASK_SLOTS));
   VSX_HIP(pl->d_out.alloc(&ctx->pool, n_pairs));
-  VSX_HIP(pl->d_cursor.alloc(&ctx->pool, 2));
+  VSX_HIP(pl->d_cursor.alloc(&ctx->pool, 3));
   {
     // output arrays, 16-byte aligned sections of one block: score, aligned, matches, mismatches, gaps (2 B), verdict (1 B), text offset (8 B)
     const uint64_t np = std::max<uint64_t>(n_pairs, 1);
@@ -1655,7 +1671,7 @@ int vsx_plan_run(vsx_plan * pl)
   VSX_HIP(hipSetDevice(ctx->device));
   hipStream_t st = pl->alt_fwd ? ctx->stream_b : ctx->stream, st2 = ctx->stream2;
   const int slot = pl->dir_slot;
-  VSX_HIP(hipMemsetAsync(pl->d_cursor.p, 0, 2 * sizeof(unsigned long long), st));
+  VSX_HIP(hipMemsetAsync(pl->d_cursor.p, 0, 3 * sizeof(unsigned long long), st));
   if (pl->filter.rank_counts) VSX_HIP(hipMemsetAsync(pl->d_rank_counts.p, 0, 2 * sizeof(uint32_t), st));      // (every run: settle() may run a plan twice)
   VSX_HIP(hipEventRecord(pl->ev_begin, st));
   // DP kernels on `st`, tracebacks + text on `st2`.  A plan's DP waits only for the last traceback that read ITS checkpoint
@@ -1671,6 +1687,7 @@ int vsx_plan_run(vsx_plan * pl)
         {
           VsxDevParams Pf = L.tilt ? ctx->Pt : ctx->P;
           Pf.max3 = (L.tilt == 2) ? 1 : 0;
+          Pf.es_skipped = pl->d_cursor.p + 2;
           static const bool one_off = std::getenv("VSX_ONESTRIP") && std::strcmp(std::getenv("VSX_ONESTRIP"), "0") == 0;      // A/B, tests: the general kernels
           VSX_HIP(vsx_launch_forward(L.rows, L.track, L.nq, (L.multi || (one_off && L.nq < 8)) ? 0 : 1, Pf, pl->d_tasks.p + L.first, L.count,
                                     pl->Q->codes(), pl->T->codes(), dir, pl->d_strip.p,
@@ -1704,7 +1721,7 @@ int vsx_plan_run(vsx_plan * pl)
   // run lists -> CIGAR text, records -> output arrays (pushop / finishop are part of the reference's timed path); st2 is in order
   VSX_HIP(vsx_launch_cigar_text(pl->d_out.p, pl->d_pair_ids.p, (uint32_t) pl->pair_ids.size(), pl->d_runs.p, pl->runs_capacity,
                                pl->d_text.p, pl->text_capacity, pl->d_cursor.p + 1, pl->soa, st2));
-  VSX_HIP(hipMemcpyAsync(pl->h_cursor, pl->d_cursor.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st2));
+  VSX_HIP(hipMemcpyAsync(pl->h_cursor, pl->d_cursor.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st2));
   VSX_HIP(hipEventRecord(pl->ev_end, st2));
   pl->ran = true;
   pl->host_patched = false;            // the exported records of host-answered pairs point behind THIS run's device runs
@@ -1733,6 +1750,7 @@ int vsx_plan_sync(vsx_plan * pl, vsx_timing * tm)
       VSX_HIP(hipEventElapsedTime(&tm->total_ms, pl->ev_begin, pl->ev_end));
       tm->cells = pl->cells;
       tm->dir_bytes = pl->dir_bytes_total;
+      tm->steps_skipped = pl->h_cursor[2];
     }
   return VSX_OK;
 }

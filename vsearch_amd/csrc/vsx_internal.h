@@ -48,6 +48,12 @@ struct VsxDevParams {
                                   // the original minus g, matrix = original + 2g, htop[j] / hleft[i] = original + (j - 1) g / (i - 1) g;
                                   // top_open / top_step stay the originals.  0: plain coordinates
   int32_t  max3;                  // TILT only: 1 = the MAX3 sub-class (values biased into [0, 0x7BFF]: H = max(h0, F, E) is ONE v_pk_maximum3_f16)
+  // EARLY (vsx_forward_kernel, the whole-wave single-strip MAX3 classes): es_on = 1 when all twelve gap penalties are >= 0 and the
+  // 16-bit sums of the check provably stay inside a half; es_w0 = max(match, mismatch, 0) + es_e, es_e = the smallest of the six gap
+  // extensions, es_rr = the extension of the query's right end (all un-tilted), es_rate = es_w0 + the query-left extension (>= 1):
+  // what the top border cell's bound loses per step at most; es_skipped (device, may be null): DP steps not run, summed over the waves
+  int32_t  es_on, es_w0, es_e, es_rr, es_rate;
+  unsigned long long * es_skipped;
   const int16_t * htop;           // H(-1, j), j >= 0: top border chain (:1895-1910, :2043-2051)
   const int16_t * hleft;          // H(i, -1), i >= 0: left border chain (:844-859, :881-887)
   const int16_t * matrix;         // 16x16 score matrix S[target code][query code] (:1319-1342)
