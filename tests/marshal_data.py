@@ -164,9 +164,9 @@ def oracle_rows(case, oracle):
 
 def filtered_rows(case, rows, flt=FILTER_FULL):
     """what a plan with the accept filter returns: (rows, verdicts) -- the oracle's rows with the restated verdict
-    (tests/test_gpu_parity.py _verdict_py: align_trim + search_acceptable_aligned); a rejected pair keeps its numbers and loses its
+    (tests/aligner_data.py verdict_py: align_trim + search_acceptable_aligned); a rejected pair keeps its numbers and loses its
     CIGAR, a pair the host answers or the 16-bit aligner refuses (sentinel score) stays undecided"""
-    from tests.test_gpu_parity import _verdict_py
+    from tests.aligner_data import verdict_py as _verdict_py
     out, verdicts = [], []
     host = set(case["host"])
     for k, row in enumerate(rows):

@@ -16,13 +16,13 @@ import numpy as np
 import pytest
 
 from tests import common
+from tests.mask_data import COMP, masked_families as _masked_families, queries as _queries
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "vsearch_ref")
 FIELDS = ["query", "target", "id", "alnlen", "mism", "opens", "exts", "raw", "caln", "qstrand"]
-COMP = {"A": "T", "C": "G", "G": "C", "T": "A", "a": "t", "c": "g", "g": "c", "t": "a", "N": "N", "R": "Y", "Y": "R"}
 
 
 def _need_ref():
@@ -40,51 +40,6 @@ def _first_diff(got, exp):
 def _write(path, names, seqs):
     with open(path, "w") as f:
         f.write("".join(f">{n}\n{s}\n" for n, s in zip(names, seqs)))
-
-
-def _low_complexity(rng, n):
-    p = rng.choice([1, 2, 3, 4])
-    u = "".join(rng.choice("ACGT") for _ in range(p))
-    return (u * (n // p + 1))[:n]
-
-
-def _masked_families(rng, n_families, members, length, div, lower_case):
-    """families whose ancestors carry low-complexity stretches (shared ACROSS families, so unmasked they drag unrelated
-    targets into the candidate lists) and, with lower_case, soft-masked stretches of ordinary sequence"""
-    shared = [_low_complexity(rng, rng.randint(30, 70)) for _ in range(3)]
-    db = []
-    for _ in range(n_families):
-        parts, left = [], length
-        while left > 0:
-            if rng.random() < 0.35:
-                seg = rng.choice(shared)
-            else:
-                seg = common.rnd_seq(rng, rng.randint(20, 90))
-                if lower_case and rng.random() < 0.3:
-                    seg = seg.lower()
-            parts.append(seg)
-            left -= len(seg)
-        anc = "".join(parts)
-        for _ in range(members):
-            m = common.mutate(rng, anc.upper(), div)
-            # keep the ancestor's case pattern position by position where the lengths still agree (soft masking is about case)
-            if lower_case:
-                m = "".join(c.lower() if k < len(anc) and anc[k].islower() else c for k, c in enumerate(m))
-            db.append(m)
-    return db
-
-
-def _queries(rng, db, n, qlen, div, lower_case):
-    qs = []
-    for _ in range(n):
-        s = db[rng.randrange(len(db))]
-        a = rng.randrange(max(1, len(s) - qlen))
-        frag = s[a:a + qlen]
-        m = common.mutate(rng, frag.upper(), div)
-        if lower_case:
-            m = "".join(c.lower() if k < len(frag) and frag[k].islower() else c for k, c in enumerate(m))
-        qs.append(m)
-    return qs
 
 
 def _reference_userout(tmp, db, qs, mask_args, extra):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import common
+from tests.aligner_data import torture_pairs, verdict_py as _verdict_py
 
 pytestmark = pytest.mark.gpu
 
@@ -94,21 +95,7 @@ def test_torture_slice(gpu_required, oracle):
     """IUPAC codes, lower case, unknown symbols, length-1 and ragged lengths, all scoring sets"""
     from vsearch_amd import Aligner
     doc = common.load_golden()
-    rng = random.Random(77)
-    pairs = []
-    for _ in range(300):
-        kind = rng.random()
-        if kind < 0.3:
-            a = common.rnd_seq(rng, rng.randint(1, 90), common.IUPAC + "acgtn-X")
-            b = common.mutate(rng, a, 0.15, common.IUPAC + "acgtn")
-        elif kind < 0.5:
-            a, b = common.rnd_seq(rng, rng.randint(1, 3)), common.rnd_seq(rng, rng.randint(1, 40))
-        elif kind < 0.7:
-            a = common.rnd_seq(rng, rng.randint(1, 200))
-            b = common.mutate(rng, a, 0.3, "ACGTN")
-        else:
-            a, b = common.rnd_seq(rng, rng.randint(0, 70)), common.rnd_seq(rng, rng.randint(0, 130))
-        pairs.append((a, b))
+    pairs = torture_pairs()
     for name, sc in doc["scorings"].items():
         rows = _align_cases(Aligner, sc["P"], sc["n_mismatch"], pairs)
         for (a, b), r in zip(pairs, rows):
@@ -142,40 +129,6 @@ def test_size_guard_and_sentinels(gpu_required):
 
 
 # ---- device-side accept filter (vsx_filter) vs a Python restatement of align_trim + search_acceptable_aligned ----
-def _verdict_py(q, t, row, f):
-    """core/searchcore.cpp:343-464 (align_trim) + :664-737 (search_acceptable_aligned), evaluated on one result row"""
-    import re
-    score, al, ma, mi, ga, cigar = row
-    runs = [(int(n) if n else 1, op) for n, op in re.findall(r"(\d*)([MID])", cigar)]
-    tql = ttl = tqr = ttr = 0
-    if runs and runs[0][1] != "M":
-        if runs[0][1] == "D": tql = runs[0][0]
-        else: ttl = runs[0][0]
-    if runs and runs[-1][1] != "M":
-        if runs[-1][1] == "D": tqr = runs[-1][0]
-        else: ttr = runs[-1][0]
-    if tql >= al: tqr = 0
-    if ttl >= al: ttr = 0
-    indels = al - ma - mi
-    ial = al - tql - ttl - tqr - ttr
-    iindels = indels - tql - ttl - tqr - ttr
-    igaps = ga - (1 if tql + ttl > 0 else 0) - (1 if tqr + ttr > 0 else 0)
-    Q, D = len(q), len(t)
-    shortest, longest = min(Q, D), max(Q, D)
-    iddef = f["iddef"]
-    if iddef == 0: idv = 100.0 * ma / shortest if shortest > 0 else 0.0
-    elif iddef == 2: idv = 100.0 * ma / ial if ial > 0 else 0.0
-    elif iddef == 3: idv = max(0.0, 100.0 * (1.0 - (1.0 * (mi + ga) / longest)))
-    else: idv = 100.0 * ma / al if al > 0 else 0.0
-    ok = (idv >= 100.0 * f["weak_id"] and mi <= f["maxsubs"] and igaps <= f["maxgaps"] and ial >= f["mincols"]
-          and (not f["leftjust"] or tql + ttl == 0) and (not f["rightjust"] or tqr + ttr == 0)
-          and ma + mi >= f["query_cov"] * Q and ma + mi >= f["target_cov"] * float(D) and idv <= 100.0 * f["maxid"]
-          and (ma + mi > 0 and 100.0 * ma / (ma + mi) >= f["mid"]) and mi + iindels <= f["maxdiffs"])
-    if not ok:
-        return 3
-    return 1 if idv >= 100.0 * f["id"] else 2
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("flt", [
     dict(iddef=2, id=0.9, weak_id=0.8),

@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 from tests import common
+from tests.msa_data import cluster_input, random_cluster as _random_cluster
 
 pytestmark = pytest.mark.gpu
 
@@ -227,15 +228,7 @@ def test_cluster_msa_consensus_profile_match_reference_cli(gpu_required, tmp_pat
     if not os.path.exists(REF_BIN):
         pytest.fail("oracle/_ref/vsearch_ref missing")
     from vsearch_amd import Aligner, SearchSession, msa_batch
-    rng = random.Random(17)
-    seqs = []
-    for f in range(8):
-        anc = common.rnd_seq(rng, rng.randint(150, 200))
-        for _ in range(rng.randint(1, 9)):
-            seqs.append(common.mutate(rng, anc, rng.choice([0.02, 0.06])))
-    seqs.append(common.mutate(rng, seqs[0], 0.03, "ACGTNRY"))
-    rng.shuffle(seqs)
-    names = [f"s{i:03d}" for i in range(len(seqs))]
+    seqs, names = cluster_input()
     order = sorted(range(len(seqs)), key=lambda i: (-len(seqs[i]), names[i]))
     sseqs, snames = [seqs[i] for i in order], [names[i] for i in order]
     tmp = str(tmp_path)
@@ -557,37 +550,6 @@ def test_strand_both_edge_cases_match_reference_cli(gpu_required, tmp_path, extr
     # the tie really occurs: some query reports the same target and identity on both strands
     keys = [tuple(l.split("\t")[:3]) for l in exp]
     assert len(keys) > len(set(keys)) or "weak_id" not in opts
-
-
-def _random_cluster(rng, n, clen, alphabet="ACGT", pins=0.03, pdel=0.03, long_ins=False):
-    """a centroid and n-1 members with CIGARs drawn directly (member = query, centroid = target: 'D' = symbols only the member has)"""
-    cen = "".join(rng.choice(alphabet) for _ in range(clen))
-    seqs, cigars = [cen], [None]
-    for _ in range(n - 1):
-        ops, mem = [], []
-        if rng.random() < 0.2:
-            k = rng.randint(1, 30 if long_ins else 4); ops.append(("D", k)); mem += [rng.choice(alphabet) for _ in range(k)]
-        p = 0
-        while p < clen:
-            r = rng.random()
-            if r < pdel:
-                k = min(clen - p, rng.randint(1, 5)); ops.append(("I", k)); p += k
-            elif r < pdel + pins and ops and ops[-1][0] != "D":
-                k = rng.randint(1, 30 if long_ins else 3); ops.append(("D", k)); mem += [rng.choice(alphabet) for _ in range(k)]
-            else:
-                k = min(clen - p, rng.randint(1, 40)); ops.append(("M", k))
-                mem += [cen[p + j] if rng.random() < 0.9 else rng.choice(alphabet) for j in range(k)]; p += k
-        if rng.random() < 0.2 and ops[-1][0] != "D":
-            k = rng.randint(1, 6); ops.append(("D", k)); mem += [rng.choice(alphabet) for _ in range(k)]
-        merged = []
-        for op, k in ops:
-            if merged and merged[-1][0] == op:
-                merged[-1][1] += k
-            else:
-                merged.append([op, k])
-        cigars.append("".join((str(k) if k > 1 else "") + op for op, k in merged))
-        seqs.append("".join(mem))
-    return seqs, cigars
 
 
 def test_msa_device_equals_host(gpu_required):

@@ -480,6 +480,10 @@ def load():
     lib.vsx_plan_destroy.restype = None
     lib.vsx_plan_describe.argtypes = [vp, C.POINTER(PlanInfo)]
     lib.vsx_internal_settle_counts.argtypes = [vp, C.POINTER(C.c_uint64 * 2)]
+    lib.vsx_internal_poison_byte.restype = C.c_int                   # VSX_POISON: -1 off, else the fill byte (tests)
+    lib.vsx_internal_msa_row_tile.restype = C.c_uint32               # rows of one profile tile of the device MSA (tests)
+    lib.vsx_internal_ckpt_bytes_estimate.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.vsx_internal_ckpt_bytes_estimate.restype = C.c_uint64
     lib.vsx_internal_export_host.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.vsx_align_pairs.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(Results)]
     lib.vsx_align_pairs_filtered.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(Filter), C.POINTER(Results)]

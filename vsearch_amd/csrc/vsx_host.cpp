@@ -13,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cerrno>
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -479,10 +480,29 @@ struct vsx_plan {
 
 extern "C" {
 
+// VSX_POISON (vsx_private.h): -1 = off, else the fill byte.  The environment is read once per process.
+int vsx_internal_poison_byte(void)
+{
+  static const int byte = [] {
+    if (!std::getenv("VSX_POISON")) return -1;
+    int b = 0xA5;
+    if (const char * s = std::getenv("VSX_POISON_BYTE"))
+      {
+        char * end = nullptr;
+        errno = 0;
+        const bool hex = s[0] == '0' && (s[1] == 'x' || s[1] == 'X');
+        const long v = std::strtol(s, &end, hex ? 16 : 10);
+        if (end != s && *end == '\0' && errno == 0 && v >= 0 && v <= 255) b = (int) v;
+        else std::fprintf(stderr, "vsx: VSX_POISON_BYTE=%s is not a byte (0 .. 255, decimal or 0x..): filling with 0x%02X\n", s, b);
+      }
+    return b;
+  }();
+  return byte;
+}
 void vsx_internal_poison(void * p, size_t bytes)
 {
-  static const bool on = std::getenv("VSX_POISON") != nullptr;
-  if (on && p && bytes) { (void) hipMemset(p, 0xA5, bytes); (void) hipDeviceSynchronize(); }
+  const int byte = vsx_internal_poison_byte();
+  if (byte >= 0 && p && bytes) { (void) hipMemset(p, byte, bytes); (void) hipDeviceSynchronize(); }
 }
 // the host worker pool of the dispatch layer, vsx_search.cpp and the commands on its searcher (fn(0) runs on the caller, which also helps with queued jobs while it waits)
 void vsx_internal_run_threads(int nth, void (*fn)(int, void *), void * arg) { run_threads(nth, [&](int t) { fn(t, arg); }); }
@@ -587,7 +607,7 @@ uint64_t vsx_internal_ckpt_bytes_estimate(const vsx_ctx * ctx, uint64_t ntasks, 
   const int rows = pick_rows((int) qlen);
   const uint64_t total_lanes = ((uint64_t) qlen + (uint64_t) rows - 1) / (uint64_t) rows, nstrips = (total_lanes + 15) / 16;
   const uint64_t steps = (((uint64_t) tlen + 3) & ~3ull) + 16;
-  const int tilt = (ctx->Pt.tilt != 0 && rows >= 4) ? 1 : 0;
+  const int tilt = ((!ctx || ctx->Pt.tilt != 0) && rows >= 4) ? 1 : 0;      // no context (tests without a device): the compressed layout, the smaller one
   return (ntasks * vsx_ckpt_dwords(nstrips, steps, (uint64_t) rows, tilt) + 2 * VSX_CK_SLACK_DW) * 4;
 }
 hipStream_t vsx_internal_stream(const vsx_ctx * ctx) { return ctx->stream; }
@@ -1671,6 +1691,7 @@ int vsx_plan_run(vsx_plan * pl)
   VSX_HIP(hipSetDevice(ctx->device));
   hipStream_t st = pl->alt_fwd ? ctx->stream_b : ctx->stream, st2 = ctx->stream2;
   const int slot = pl->dir_slot;
+  const int poison = vsx_internal_poison_byte();      // -1: off, and no stream operation is added below
   VSX_HIP(hipMemsetAsync(pl->d_cursor.p, 0, 3 * sizeof(unsigned long long), st));
   if (pl->filter.rank_counts) VSX_HIP(hipMemsetAsync(pl->d_rank_counts.p, 0, 2 * sizeof(uint32_t), st));      // (every run: settle() may run a plan twice)
   VSX_HIP(hipEventRecord(pl->ev_begin, st));
@@ -1682,6 +1703,13 @@ int vsx_plan_run(vsx_plan * pl)
       uint32_t * dir = pl->d_dir[0].p;
       if (k >= 1) VSX_HIP(hipStreamWaitEvent(st, pl->chunks[k - 1].e2, 0));      // buffer reuse: the previous traceback is done
       else if (ctx->ev_tb_used[slot]) VSX_HIP(hipStreamWaitEvent(st, ctx->ev_tb[slot], 0));
+      // VSX_POISON: what this chunk is about to use of the SHARED checkpoint block (SharedSlot::acquire hands the current block out
+      // untouched) and of the strip buffer; stream-ordered, behind the wait for the last traceback that read the block
+      if (poison >= 0)
+        {
+          VSX_HIP(hipMemsetAsync(dir, poison, (c.dir_dwords + VSX_CK_SLACK_DW) * sizeof(uint32_t), st));
+          if (c.strip_elems) VSX_HIP(hipMemsetAsync(pl->d_strip.p, poison, c.strip_elems * sizeof(uint2), st));
+        }
       VSX_HIP(hipEventRecord(c.e0, st));
       for (const Launch & L : c.launches)
         {
@@ -1695,6 +1723,7 @@ int vsx_plan_run(vsx_plan * pl)
         }
       VSX_HIP(hipEventRecord(c.e1, st));
       VSX_HIP(hipStreamWaitEvent(st2, c.e1, 0));
+      if (poison >= 0 && c.slab_words) VSX_HIP(hipMemsetAsync(pl->d_slab.p, poison, c.slab_words * sizeof(uint32_t), st2));      // the shared slab
       VSX_HIP(hipEventRecord(c.e1b, st2));
       for (size_t li = 0; li < c.launches.size();)      // the recompute traceback is specialised on R like the DP kernel
         {

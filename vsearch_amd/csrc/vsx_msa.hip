@@ -26,6 +26,8 @@
 
 namespace {
 
+constexpr uint32_t kRowTile = 4096;      // rows of one profile tile (vsx_msa_profile_kernel); vsx_internal_msa_row_tile()
+
 struct MsaRow {            // one output row (centroid, member)
   uint64_t out;            // byte offset of the row in the rows blob
   uint64_t seq;            // byte offset of its sequence in the sequence blob
@@ -242,8 +244,8 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
         }
       const uint64_t ab_first = ab.size() - n;
       for (uint32_t col0 = 0; col0 < alnlen; col0 += 64)
-        for (uint64_t r0 = 0; r0 < n; r0 += 4096)
-          tiles.push_back(MsaTile {rows_bytes, prof_count, ab_first, alnlen, col0, (uint32_t) r0, (uint32_t) std::min<uint64_t>(n, r0 + 4096)});
+        for (uint64_t r0 = 0; r0 < n; r0 += kRowTile)
+          tiles.push_back(MsaTile {rows_bytes, prof_count, ab_first, alnlen, col0, (uint32_t) r0, (uint32_t) std::min<uint64_t>(n, r0 + kRowTile)});
       for (uint32_t col0 = 0; col0 <= alnlen; col0 += 256) { cb_cluster.push_back(c - c0); cb_col0.push_back(col0); }
       rows_bytes += (n + 1) * ((uint64_t) alnlen + 1);
       prof_count += (uint64_t) alnlen * 6;
@@ -305,6 +307,8 @@ int msa_chunk(hipStream_t st, uint32_t c0, uint32_t c1, const uint64_t * cstart,
 }
 
 }  // namespace
+
+extern "C" uint32_t vsx_internal_msa_row_tile(void) { return kRowTile; }
 
 extern "C" int vsx_msa_device_batch(vsx_ctx * ctx, uint32_t n_clusters, const uint64_t * cluster_start, const char * const * seqs,
                                     const uint32_t * lens, const char * const * cigars, const uint64_t * abundances, vsx_msa_out * outs)

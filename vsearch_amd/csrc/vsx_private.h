@@ -28,8 +28,14 @@ hipStream_t vsx_internal_stream(const vsx_ctx * ctx);
 int vsx_internal_usable_cpus(void);
 // the library's host worker pool: fn(0) runs on the caller, which also helps with queued jobs while it waits
 void vsx_internal_run_threads(int nth, void (*fn)(int, void *), void * arg);
-// VSX_POISON=1 (debugging aid): every device block this library hands out is filled with 0xA5 first, so a read of memory nobody
-// has written gives the same junk in every run instead of whatever an earlier plan, index or process left there
+// VSX_POISON=1 (debugging aid, tests/test_gpu_poison.py): every device block this library hands out (scratch pool, DevBuf::alloc) is
+// filled with 0xA5 first, so a read of memory nobody has written gives the same junk in every run instead of whatever an earlier
+// plan, index or process left there.  VSX_POISON_BYTE (0 .. 255, decimal or 0x..) chooses another byte; anything else is refused
+// with a line on stderr and the default stays.  The blocks the plans of a context SHARE (checkpoints, traceback slab) and a plan's
+// strip buffer are handed out untouched when they are large enough, so vsx_plan_run fills the part each chunk is about to use,
+// stream-ordered, before that chunk's first kernel.  A grow-only DevBuf is not filled again on reuse (some are built once and kept).
+// Unset: nothing is filled and nothing is issued.  The environment is read once per process.
+int vsx_internal_poison_byte(void);      // -1: off, else the byte
 void vsx_internal_poison(void * p, size_t bytes);
 // device memory under pressure: every live context of the device drops the stream-ordered blocks no plan holds and frees its idle
 // pool.  Whoever meets hipErrorOutOfMemory calls this once and retries (vsxp::device_malloc does).  Returns the bytes released.
@@ -42,7 +48,7 @@ int vsx_internal_scratch_reserve(vsx_ctx * ctx, const uint64_t want[4]);
 // what the plans of a context asked for since the last reset: {checkpoint block, slab} bytes
 void vsx_internal_scratch_requests(vsx_ctx * ctx, uint64_t out[2], int reset);
 // what the checkpoint block of ONE plan of `ntasks` whole-wave tasks (a query of qlen rows against up to eight targets of tlen
-// columns) will ask for
+// columns) will ask for; ctx == NULL: as under a scoring that can be tilted (the compressed layout, a lower bound)
 uint64_t vsx_internal_ckpt_bytes_estimate(const vsx_ctx * ctx, uint64_t ntasks, uint32_t qlen, uint32_t tlen);
 void vsx_internal_seqset_device(const vsx_seqset * s, const uint8_t ** codes, const uint64_t ** off, const uint32_t ** len, uint64_t * n);
 // host copies of the set's lengths (the k-mer index build of long words lays its key slots out by their running sum)
@@ -98,6 +104,10 @@ void vsx_internal_sintax_index_destroy(VsxSintaxIndex * X);
 // what a searcher keeps for vsx_orient: the match-count table of its database (device and host) and window buffers
 struct VsxOrientIndex;
 void vsx_internal_orient_index_destroy(VsxOrientIndex * X);
+
+// ---- vsx_msa.hip -------------------------------------------------------------------------------------------------------------
+// rows of one tile of the device MSA's profile kernel: a cluster of n members takes ceil(n / this) row tiles per 64 columns (tests)
+extern "C" uint32_t vsx_internal_msa_row_tile(void);
 
 // ---- vsx_mask.cpp ------------------------------------------------------------------------------------------------------------
 // DUST of one sequence, for the dispatch layer's per-query masking (the caller owns the scratch copy; hard: --hardmask)
