@@ -1,7 +1,8 @@
 """profiles/tb_stats.py -- structure of the checkpoint traceback on a bench-shaped workload, from a -DVSX_TB_STATS=1 build
 (make -C vsearch_amd/csrc VARIANT=stats EXTRA=-DVSX_TB_STATS=1; VSX_LIBRARY=vsearch_amd/libvsx_stats.so python profiles/tb_stats.py
 --qlen 250 --dlen 1000 --db 1000000 --queries 100000): wave iterations, busy (pair, tile) visits, distinct tiles per task and
-iteration (= separate sets of checkpoint lines), cells walked."""
+iteration (= separate sets of checkpoint lines), cells walked, walk trips per position.  -DVSX_TB_STATS=3 adds the phase cycles
+(bit 1 = the counts, bit 2 = the s_memtime marks); -DVSX_TB_WALK_BATCH=1 beside it gives the one-cell walk's figures."""
 import argparse
 import ctypes as C
 import json
@@ -44,6 +45,8 @@ print(json.dumps({"shape": [a.qlen, a.dlen], "pairs": pairs, "tasks": info["task
                   "iterations_per_wave": round(it / max(pairs / 64, 1), 2), "lane_utilisation": round(busy / max(it * 64, 1), 3),
                   "distinct_task_tiles": distinct, "pairs_per_distinct_tile": round(busy / max(distinct, 1), 2),
                   "cells_walked": walked, "cells_walked_per_pair_tile": round(walked / max(busy, 1), 2),
+                  # vsx_traceback_tilt_kernel: trips of the walk loop as the wave runs them (its slowest lane's, both tiles of a position)
+                  "walk_trips": trips, "walk_trips_per_position": round(trips / max(it, 1), 2),
                   "traceback_ms_instrumented": round(tm.traceback_ms, 3),
                   "phase_cycles_per_wave_iteration(load1,recompute1,walk1,load2,recompute2,walk2)": [round(int(out[8 + k]) / max(it, 1)) for k in range(6)],
                   "kernel_cycles_per_wave": round(int(out[15]) / max(pairs / 64, 1))}))

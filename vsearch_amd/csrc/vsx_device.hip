@@ -1110,7 +1110,8 @@ struct __attribute__((aligned(4))) Trio { u32 x, y, z; };
 
 // -DVSX_TB_STATS=1 (A/B build, measurements only): what the checkpoint traceback does per launch -- [0] wave iterations of the
 // tile loop, [1] busy (pair, tile) visits, [2] distinct tiles among the <= 8 lanes of a task summed over the iterations (= how
-// many separate sets of checkpoint lines a task's lanes ask for), [3] cells walked, [4] walk-loop trips (wave level), [5] pairs;
+// many separate sets of checkpoint lines a task's lanes ask for), [3] cells walked, [4] walk-loop trips as the wave runs them (its
+// slowest lane's; vsx_traceback_tilt_kernel, any non-zero VSX_TB_STATS), [5] pairs;
 // vsx_traceback_tilt_kernel also: [8 ..] wave cycles (s_memtime) per phase of an iteration: loads of tile 1 until they have landed,
 // recompute 1, walk 1, loads of tile 2, recompute 2, walk 2, the rest; [15] = the whole kernel per wave (out16: 16 values)
 #ifndef VSX_TB_STATS
@@ -1702,6 +1703,14 @@ DEV u32 pk_sub(u32 a, u32 b) { return psubw(a, b); }                            
 #ifndef VSX_TB_LDSSTAGE_FOR
 #define VSX_TB_LDSSTAGE_FOR(R_) ((R_) == 14 || (R_) == 16 || (R_) >= 26)
 #endif
+// VSX_TB_WALK_BATCH: cells a trip of the walk may consume (1 = one cell per trip, the walk as it was up to r05; see walk() below).
+// Same-box A/B, three runs each (profiles/walk_batch/INDEX.md): 250 x 1000 (R = 16) 3.72-3.74 ms with 1, 3.51-3.54 with 4, 3.54-3.56 with
+// 8 -- 30 / 11.1 / 8.4 trips per position, but every cell ahead costs a trip 13-15 VALU whether it is consumed or not (the loop at R = 16: 51 / 95 / 141), issued
+// beside the other waves' recompute.  Registers and scratch are the same for 1, 4 and 8 in every row class.
+#ifndef VSX_TB_WALK_BATCH
+#define VSX_TB_WALK_BATCH 4
+#endif
+static_assert(VSX_TB_WALK_BATCH >= 1 && VSX_TB_WALK_BATCH <= 16, "a batch stays inside one 16-column tile");
 template <int R, bool MID>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VSX_TB2_WAVES(R, MID), 8)))
 vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const VsxTask * __restrict__ tasks,
@@ -1717,6 +1726,7 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
   constexpr int HR = (RT + 1) / 2;                 // row pairs: rows x and x + HR share a register (row RT of an odd tile is junk)
   constexpr int NG = (HR + 3) / 4;                 // bits dwords per column slot
   constexpr int XL = RT - 1 - HR;                  // the row pair whose HIGH half is the tile's last row
+  constexpr int WB = VSX_TB_WALK_BATCH;            // cells per trip of the walk
   constexpr int NBQ = MID ? VSX_COLCK_NBH(RT) : VSX_COLCK_NB(R, true);      // 16-byte blocks of one (half-)column checkpoint
   // One wave per workgroup: 14.5 KB of LDS each = 11 waves per CU (the wave's own arrays are lane-minor: no bank conflicts)
   __shared__ uint8_t Ssh[512];                     // S'[target code][query code], row stride 32; query "code" 16 = a dummy row of position 0
@@ -1808,7 +1818,7 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
 
 #if VSX_TB_STATS
   const unsigned long long t_kernel0 = __builtin_readcyclecounter();
-  unsigned n_iter = 0;
+  unsigned n_iter = 0, n_trips = 0, n_cells = 0;
   unsigned long long tphase[6] = {0, 0, 0, 0, 0, 0};
 #endif
   for (;;)
@@ -2122,14 +2132,46 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
         else          { if (fastV) sweep(std::false_type {}, std::true_type {}); else sweep(std::false_type {}, std::false_type {}); }
       };
       // ---- walk inside the tile (backtrack16 :1137-1211); matches are counted from the finished CIGAR below ----
+      // A trip handles up to WB cells: cell 0 under the cursor by the full rule, cells k = 1 .. WB - 1 at (r - k, j - k) for as long as the
+      // path stays diagonal.  After a diagonal move the state is M, where the five-way choice collapses (inI = inD = 0): the move is
+      // diagonal exactly when neither LEFT nor UP of the cell is set, and where the next cells of a diagonal lie depends on no value
+      // read -- so all WB words are asked for before the first is used (one LDS round trip instead of WB) and consumed with bit
+      // arithmetic.  The first cell that is not a plain diagonal move, or lies outside the tile or the pair, ends the trip BEFORE itself
+      // and is cell 0 of the next trip (or of the next tile).  Model and proof of equivalence: tests/test_walk_batch_math.py.
       auto walk = [&](const int cst) __attribute__((always_inline)) {
+#if VSX_TB_STATS
+        unsigned ntrip = 0;
+#endif
         while (r >= r0h && j >= cst && i >= 0)
           {
             const int cw = j - cst;
             const int rv = r - r0h;
+            // dword and shift of a cell.  Each cell forms its own: a diagonal crosses the HR boundary (the column slot + 1, the byte + 8 bits,
+            // the group of four row pairs restarts)
             const bool up_half = rv >= HR;
             const int rx = up_half ? rv - HR : rv;
-            const u32 w = bitsL[((cw + (up_half ? 1 : 0)) * NG + (rx >> 2)) * 64 + tid] >> ((rx & 3) + (up_half ? 8 : 0));
+            u32 wk[WB], shk[WB];
+            shk[0] = (u32) ((rx & 3) + (up_half ? 8 : 0));
+            wk[0] = bitsL[((cw + (up_half ? 1 : 0)) * NG + (rx >> 2)) * 64 + tid];
+            const int kmax = min(min(rv, cw), min(i, WB - 1));                // cells 1 .. kmax are inside the tile and the pair
+            // cells 1 .. WB - 1, the same index in fewer instructions: with the virtual row v = row (low half) or 4 NG + row - HR (high half)
+            // the dword is slot * NG + (v >> 2) -- the high half's "+ 1 slot" is the NG that v >> 2 carries -- and bit 4 NG of v selects the
+            // byte.  A cell past kmax re-reads cell kmax: no index leaves the part of bitsL this tile wrote, and kmax masks the result out
+            static_assert(NG <= 2, "4 NG is a single bit of the virtual row");
+#pragma unroll
+            for (int k2 = 1; k2 < WB; ++k2)
+              {
+                const int kk = min(k2, kmax);
+                const int rvk = rv - kk;
+                const int v = (4 * NG != HR && rvk >= HR) ? rvk + (4 * NG - HR) : rvk;
+                shk[k2] = (u32) ((v & 3) | ((v & (4 * NG)) << (NG == 2 ? 0 : 1)));
+                wk[k2] = bitsL[((cw - kk) * NG + (v >> 2)) * 64 + tid];
+              }
+            if (WB > 1) __builtin_amdgcn_sched_barrier(0);                    // every read is issued before the first is waited for: one LDS round trip
+            const u32 w = wk[0] >> shk[0];
+#if VSX_TB_STATS
+            ++ntrip;
+#endif
             ++al;
             // backtrack16's five-way choice without divergence (r03: ~50 instructions per cell walked as nested branches): continue-I on
             // ext-left > continue-D on ext-up > left > up > diagonal; only the run hand-over to the slab is a branch
@@ -2152,10 +2194,24 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
                 runlen = 0;
               }
             ++runlen;
+            u32 nd = 0;                                                       // cells 1 .. nd: plain diagonal moves of the M run cell 0 continued or began
+            if (WB > 1)
+              {
+                u32 stop = 0;                                                 // bit k - 1: UP, bit 16 + k - 1: LEFT of cell k
+#pragma unroll
+                for (int k2 = 1; k2 < WB; ++k2) stop |= ((wk[k2] >> shk[k2]) & 0x00010001u) << (k2 - 1);
+                stop |= (stop >> 16) | (1u << kmax);                          // (bits 16 .. stay: they lie above bit kmax <= WB - 1)
+                nd = (newop == 0) ? (u32) __builtin_ctz(stop) : 0u;
+                al += nd; runlen += nd;
+                i -= (int) nd; r -= (int) nd; j -= (int) nd;
+              }
 #if VSX_TB_STATS & 1
-            atomicAdd(&vsx_tb_stats_dev[3], 1ull);
+            n_cells += 1u + nd;
 #endif
           }
+#if VSX_TB_STATS
+        return ntrip;
+#endif
       };
 
 #if VSX_TB_STATS & 2
@@ -2182,16 +2238,22 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
           const bool tile_int = tno ? true : !__any(busy && (c0 + cmax >= D - 1));
           recompute(in, tno ? (m <= 1) : (m == 0), cst, rmax_raw, cmax, tile_int);
           TBMARK(3 * tno + 1);
+#if VSX_TB_STATS
+          n_trips += (unsigned) wave_max_i32(need ? (int) walk(cst) : 0);     // the wave runs its slowest lane's trips
+#else
           if (need) walk(cst);
+#endif
           TBMARK(3 * tno + 2);
         }
       if (busy && r < 0 && L > 0) { --L; r = R - 1; }
     }
 #if VSX_TB_STATS
   if (valid) atomicAdd(&vsx_tb_stats_dev[5], 1ull);
+  if (n_cells) atomicAdd(&vsx_tb_stats_dev[3], (unsigned long long) n_cells);
   if (tid == 0)
     {
       atomicAdd(&vsx_tb_stats_dev[15], __builtin_readcyclecounter() - t_kernel0); atomicAdd(&vsx_tb_stats_dev[0], (unsigned long long) n_iter);
+      atomicAdd(&vsx_tb_stats_dev[4], (unsigned long long) n_trips);
       for (int k2 = 0; k2 < 6; ++k2) atomicAdd(&vsx_tb_stats_dev[8 + k2], tphase[k2]);
     }
 #endif
