@@ -51,6 +51,7 @@ FASTQ_STATS_SYMBOLS = ["vsx_fastq_stats_opts_default", "vsx_fastq_stats", "vsx_f
 DEREP_SYMBOLS = ["vsx_derep_opts_default", "vsx_derep", "vsx_derep_out_free", "vsx_derep_last_stats", "vsx_internal_derep_thresholds"]
 DEREP_THRESHOLDS = 129             # VSX_DEREP_THRESHOLDS
 # include/vsx_derep_prefix.h
+OTUTAB_SYMBOLS = ["vsx_otutab_opts_default", "vsx_otutab", "vsx_otutab_result_free", "vsx_otutab_last_stats", "vsx_internal_otutab_host"]
 DEREP_PREFIX_SYMBOLS = ["vsx_derep_prefix_opts_default", "vsx_derep_prefix", "vsx_derep_prefix_out_free", "vsx_derep_prefix_last_stats"]
 # include/vsx_sintax.h
 SINTAX_SYMBOLS = ["vsx_sintax_opts_default", "vsx_sintax", "vsx_sintax_result_free", "vsx_sintax_last_stats", "vsx_internal_sintax_host",
@@ -306,6 +307,33 @@ class DerepPrefixStats(C.Structure):
                                           "seconds_resolve", "seconds_output", "seconds_total")] + \
                [(n, C.c_uint64) for n in ("windows", "nodes", "distinct_lengths", "probes", "candidates_compared", "reads_host",
                                           "host_no_context", "host_environment", "host_read_count", "host_memory")]
+
+
+class Labels(C.Structure):
+    """vsx_labels (include/vsx_otutab.h): label k = blob[offsets[k] .. offsets[k] + lengths[k])"""
+    _fields_ = [("n", C.c_uint64), ("blob", C.c_void_p), ("bytes", C.c_uint64), ("offsets", C.c_void_p), ("lengths", C.c_void_p)]
+
+
+class OtutabOpts(C.Structure):
+    """vsx_otutab_opts (include/vsx_otutab.h)"""
+    _fields_ = [("threads", C.c_int32), ("pad", C.c_int32)]
+
+
+class OtutabResult(C.Structure):
+    """vsx_otutab_result (include/vsx_otutab.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_queries", "n_targets", "n_samples", "n_otus")] + [("has_tax", C.c_int32), ("pad", C.c_int32)] + \
+               [f for s in ("sample", "otu", "tax") for f in ((s + "_blob", C.POINTER(C.c_char)), (s + "_bytes", C.c_uint64),
+                                                              (s + "_off", C.POINTER(C.c_uint64)), (s + "_len", C.POINTER(C.c_uint32)))] + \
+               [("n_cells", C.c_uint64), ("nz_otu", C.POINTER(C.c_uint32)), ("nz_sample", C.POINTER(C.c_uint32)),
+                ("nz_count", C.POINTER(C.c_uint64)), ("q_sample", C.POINTER(C.c_uint32)), ("t_otu", C.POINTER(C.c_uint32))]
+
+
+class OtutabStats(C.Structure):
+    """vsx_otutab_stats (include/vsx_otutab.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_scan", "seconds_group", "seconds_rank", "seconds_accumulate",
+                                          "seconds_output", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("query_groups", "target_groups", "targets_in_adds", "adds_sorted", "labels_device", "labels_host",
+                                          "host_no_context", "host_environment", "host_label_count", "host_memory")]
 
 
 class SeqMeta(C.Structure):
@@ -613,6 +641,14 @@ def load():
     lib.vsx_internal_orient_host.argtypes = [C.POINTER(SearchOpts), C.POINTER(OrientOpts), C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp,
                                              C.c_uint64, vp, vp, vp, C.POINTER(OrientResult)]
     lib.vsx_internal_orient_matchcounts.argtypes = [vp, vp, C.c_uint64, vp]
+    lib.vsx_otutab_opts_default.argtypes = [C.POINTER(OtutabOpts)]
+    lib.vsx_otutab_opts_default.restype = None
+    lib.vsx_otutab.argtypes = [vp, C.POINTER(OtutabOpts), C.POINTER(Labels), vp, vp, C.POINTER(Labels), vp, C.POINTER(OtutabResult)]
+    lib.vsx_otutab_result_free.argtypes = [C.POINTER(OtutabResult)]
+    lib.vsx_otutab_result_free.restype = None
+    lib.vsx_otutab_last_stats.argtypes = [C.POINTER(OtutabStats)]
+    lib.vsx_otutab_last_stats.restype = None
+    lib.vsx_internal_otutab_host.argtypes = [C.POINTER(OtutabOpts), C.POINTER(Labels), vp, vp, C.POINTER(Labels), vp, C.POINTER(OtutabResult)]
     _lib = lib
     return lib
 

@@ -611,6 +611,9 @@ uint64_t vsx_internal_ckpt_bytes_estimate(const vsx_ctx * ctx, uint64_t ntasks, 
   return (ntasks * vsx_ckpt_dwords(nstrips, steps, (uint64_t) rows, tilt) + 2 * VSX_CK_SLACK_DW) * 4;
 }
 hipStream_t vsx_internal_stream(const vsx_ctx * ctx) { return ctx->stream; }
+// a block of the context's scratch pool for a call that is no plan (vsx_otutab): `got` is what goes back with it
+hipError_t vsx_internal_scratch_get(vsx_ctx * ctx, size_t bytes, void ** out, size_t * got) { return ctx->pool.get(bytes, out, got); }
+void vsx_internal_scratch_put(vsx_ctx * ctx, void * p, size_t got) { ctx->pool.put(p, got); }
 // host copies of the set's lengths (the k-mer index build of long words lays its key slots out by their running sum)
 const uint32_t * vsx_internal_seqset_host_lengths(const vsx_seqset * s) { return s ? s->len.data() : nullptr; }
 void vsx_internal_seqset_device(const vsx_seqset * s, const uint8_t ** codes, const uint64_t ** off, const uint32_t ** len, uint64_t * n)

@@ -24,6 +24,10 @@ void vsx_internal_set_error(const char * msg);
 const vsx_scoring * vsx_internal_scoring(const vsx_ctx * ctx);
 int vsx_internal_device(const vsx_ctx * ctx);
 hipStream_t vsx_internal_stream(const vsx_ctx * ctx);
+// a block of the context's scratch pool (reused from call to call, poisoned under VSX_POISON) and its way back; `got` is the block's
+// real size, which put() wants again
+hipError_t vsx_internal_scratch_get(vsx_ctx * ctx, size_t bytes, void ** out, size_t * got);
+void vsx_internal_scratch_put(vsx_ctx * ctx, void * p, size_t got);
 // CPUs this process may really use: affinity mask, capped by a cgroup v2 CPU quota
 int vsx_internal_usable_cpus(void);
 // the library's host worker pool: fn(0) runs on the caller, which also helps with queued jobs while it waits
