@@ -60,6 +60,10 @@ SINTAX_RANKS, SINTAX_ROUNDS, SINTAX_NONE = 9, 100, 0xffffffff
 # include/vsx_orient.h
 ORIENT_SYMBOLS = ["vsx_orient_opts_default", "vsx_orient_result_free", "vsx_orient_last_stats", "vsx_orient", "vsx_internal_orient_host",
                   "vsx_internal_orient_matchcounts"]
+# include/vsx_hitout.h
+HITOUT_SYMBOLS = ["vsx_hitout_opts_default", "vsx_hits_render", "vsx_hit_text_free", "vsx_hits_render_last_stats",
+                  "vsx_internal_hits_render_host"]
+HITOUT_ROWS, HITOUT_SYMBOLS_ROW, HITOUT_SAM, HITOUT_NONE = 1, 2, 4, 0xFFFFFFFFFFFFFFFF      # VSX_HITOUT_ROWS / _SYMBOLS / _SAM / _NONE
 ORIENT_MAX_QLEN, ORIENT_CLASSES, ORIENT_CLASS_QLEN = 16384, 3, (512, 4096, 16384)      # VSX_ORIENT_MAX_QLEN, the count kernel's length classes
 
 
@@ -334,6 +338,30 @@ class OtutabStats(C.Structure):
                                           "seconds_output", "seconds_total")] + \
                [(n, C.c_uint64) for n in ("query_groups", "target_groups", "targets_in_adds", "adds_sorted", "labels_device", "labels_host",
                                           "host_no_context", "host_environment", "host_label_count", "host_memory")]
+
+
+class HitoutOpts(C.Structure):
+    """vsx_hitout_opts (include/vsx_hitout.h)"""
+    _fields_ = [("want", C.c_uint32), ("threads", C.c_int32), ("window", C.c_uint64)]
+
+
+class HitText(C.Structure):
+    """vsx_hit_text (include/vsx_hitout.h)"""
+    _fields_ = [("n_queries", C.c_uint64), ("n_hits", C.c_uint64), ("want", C.c_uint32), ("both", C.c_uint32),
+                ("row_blob", C.POINTER(C.c_char)), ("row_bytes", C.c_uint64), ("row_len", C.POINTER(C.c_uint32)),
+                ("qrow_off", C.POINTER(C.c_uint64)), ("trow_off", C.POINTER(C.c_uint64)),
+                ("sym_off", C.POINTER(C.c_uint64)), ("aln_off", C.POINTER(C.c_uint64)),
+                ("md_blob", C.POINTER(C.c_char)), ("md_bytes", C.c_uint64), ("md_off", C.POINTER(C.c_uint64)), ("md_len", C.POINTER(C.c_uint32)),
+                ("qtext", C.POINTER(C.c_char)), ("qtext_bytes", C.c_uint64), ("qplus_off", C.POINTER(C.c_uint64)),
+                ("qminus_off", C.POINTER(C.c_uint64))]
+
+
+class HitoutStats(C.Structure):
+    """vsx_hitout_stats (include/vsx_hitout.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_mask", "seconds_stage", "seconds_h2d", "seconds_rows", "seconds_md_count",
+                                          "seconds_md_fill", "seconds_d2h", "seconds_host", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("windows", "hits_device", "hits_host", "db_text_uploaded", "host_no_context",
+                                          "host_environment", "host_hit_count", "host_memory")]
 
 
 class SeqMeta(C.Structure):
@@ -649,6 +677,15 @@ def load():
     lib.vsx_otutab_last_stats.argtypes = [C.POINTER(OtutabStats)]
     lib.vsx_otutab_last_stats.restype = None
     lib.vsx_internal_otutab_host.argtypes = [C.POINTER(OtutabOpts), C.POINTER(Labels), vp, vp, C.POINTER(Labels), vp, C.POINTER(OtutabResult)]
+    lib.vsx_hitout_opts_default.argtypes = [C.POINTER(HitoutOpts)]
+    lib.vsx_hitout_opts_default.restype = None
+    lib.vsx_hits_render.argtypes = [vp, C.POINTER(HitoutOpts), C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(Hits), C.POINTER(HitText)]
+    lib.vsx_hit_text_free.argtypes = [C.POINTER(HitText)]
+    lib.vsx_hit_text_free.restype = None
+    lib.vsx_hits_render_last_stats.argtypes = [C.POINTER(HitoutStats)]
+    lib.vsx_hits_render_last_stats.restype = None
+    lib.vsx_internal_hits_render_host.argtypes = [C.POINTER(Scoring), C.POINTER(SearchOpts), C.POINTER(HitoutOpts), C.c_uint64, vp, C.c_uint64, vp, vp,
+                                                  C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(Hits), C.POINTER(HitText)]
     _lib = lib
     return lib
 

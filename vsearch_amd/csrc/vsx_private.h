@@ -109,6 +109,11 @@ void vsx_internal_sintax_index_destroy(VsxSintaxIndex * X);
 struct VsxOrientIndex;
 void vsx_internal_orient_index_destroy(VsxOrientIndex * X);
 
+// ---- vsx_hitout.cpp ----------------------------------------------------------------------------------------------------------
+// what a searcher keeps for vsx_hits_render: its database text on the device and the window buffers
+struct VsxHitoutIndex;
+void vsx_internal_hitout_index_destroy(VsxHitoutIndex * X);
+
 // ---- vsx_msa.hip -------------------------------------------------------------------------------------------------------------
 // rows of one tile of the device MSA's profile kernel: a cluster of n members takes ceil(n / this) row tiles per 64 columns (tests)
 extern "C" uint32_t vsx_internal_msa_row_tile(void);

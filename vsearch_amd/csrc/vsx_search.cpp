@@ -640,6 +640,7 @@ void vsx_searcher_destroy(vsx_searcher * s)
   vsx_internal_exact_index_destroy(s->xidx);
   vsx_internal_sintax_index_destroy(s->sidx);
   vsx_internal_orient_index_destroy(s->oidx);
+  vsx_internal_hitout_index_destroy(s->hidx);
   vsx_seqset_destroy(s->dbset);
   vsx_destroy(s->ctx2);
   vsx_destroy(s->ctx3);

@@ -53,6 +53,7 @@ struct vsx_searcher {
   VsxExactIndex * xidx = nullptr;    // exact-match index (vsx_exact.cpp), built on first use by vsx_search_exact
   VsxSintaxIndex * sidx = nullptr;   // name ids of the labels and the window buffers of vsx_sintax (vsx_sintax.cpp), made on first use
   VsxOrientIndex * oidx = nullptr;   // match-count table and the window buffers of vsx_orient (vsx_orient.cpp), made on first use
+  VsxHitoutIndex * hidx = nullptr;   // database text on the device and the window buffers of vsx_hits_render (vsx_hitout.cpp), made on first use
   std::vector<uint64_t> word_total;  // postings per word (statistics of the device index)
   std::vector<uint8_t> is_centroid;  // clustering: which sequences are in the growing index
   std::vector<uint64_t> tsize;       // Database::getabundance of the targets (empty: all 1)
