@@ -12,6 +12,14 @@ meets up to 16 candidates.  The reference aligns every query with each of them: 
 more than ten seconds.  A round the reference refuses counts as failing.  --reference-only counts the reference's lines without
 a device.  The output's "coverage" counts the rounds per command and length class and the rounds with --hardmask / --abskew.
 
+--commands names the commands a round draws from (default: the four above, so a seed's rounds stay what they were).  With
+chimeras_denovo in the list, such a round takes a tests/chimeras_long_data.seeded_set() of drawn sizes in a length class of 300-500,
+1 200-1 600 or 1 900-2 200 (the last one straddles the kernel's VSX_CHIMERAS_LONG_MAX_QLEN = 2 048), --chimeras_parts (unset, 2, 5,
+15), --abskew, the mask mode and --hardmask, and --chimeras_diff_pct 0, 1, 2.5 or 0.125 (the kernel's exact path) or, with
+probability 0.15, 0.1 (the host restatement answers: the stats must say so).  Compared: --tabbedout and the labels of --chimeras and
+--nonchimeras; then the device's records against the host restatement's (VSX_CHIMERA=host).  Coverage: the length class, "parts",
+"diff_pct_host".
+
     python oracle/soak_chimera.py --seconds 120 --seed 1 --out soak_chimera.json
 """
 import argparse
@@ -28,15 +36,53 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 
 from oracle import refcli  # noqa: E402
-from tests import common, denovo_data  # noqa: E402
+from tests import chimeras_long_data, common, denovo_data  # noqa: E402
 
 LENGTHS = [((60, 120), 1), ((300, 500), 1), ((1200, 1600), 3), ((3900, 4200), 8)]
 MASKS = {"none": 0, "soft": 1, "dust": 2}
+COMMANDS = ["uchime_ref", "uchime_denovo", "uchime2_denovo", "uchime3_denovo"]
+LONG_LENGTHS = [((300, 500), 1), ((1200, 1600), 3), ((1900, 2200), 6)]
 
 
-def draw(rng):
+def draw_long(rng):
+    """--chimeras_denovo -> ((length range, divisor of the counts), keywords of the session, the CLI's arguments, the set's sizes);
+    every number is drawn whether or not its option is then set"""
+    length = rng.choice(LONG_LENGTHS)
+    o, cli = {}, []
+    mask = rng.choice(["none", "soft", "dust"])
+    cli += ["--qmask", mask]
+    o["soft_mask"] = mask
+    if rng.random() < 0.25:
+        cli.append("--hardmask")
+        o["hardmask"] = 1
+    parts, abskew = rng.choice([2, 5, 15]), rng.choice([1.5, 2.0, 3.5])
+    if rng.random() < 0.5:
+        o["parts"] = parts
+        cli += ["--chimeras_parts", str(parts)]
+    if rng.random() < 0.3:
+        o["abskew"] = abskew
+        cli += ["--abskew", str(abskew)]
+    pct, host = rng.choice([0, 1, 2.5, 0.125]), rng.random() < 0.15
+    pct = 0.1 if host else pct
+    if pct:
+        o["diff_pct"] = float(pct)
+        cli += ["--chimeras_diff_pct", str(pct)]
+    w, sw = rng.choice([0, 1, 7, 50]), rng.choice([0, 5, 64])
+    if w:
+        o["window"] = w
+    if sw:
+        o["search_window"] = sw
+    div = length[1]
+    sizes = dict(seed=rng.randrange(1 << 30), n_families=max(2, rng.randint(8, 20) // div), n_chimeras=max(3, rng.randint(20, 50) // div),
+                 n_long=rng.randint(3, 4), length=length[0])
+    return length, o, cli, sizes
+
+
+def draw(rng, commands=COMMANDS):
     """-> (command, (length range, divisor of the counts), keywords of the session, the CLI's arguments)"""
-    cmd = rng.choice(["uchime_ref", "uchime_denovo", "uchime2_denovo", "uchime3_denovo"])
+    cmd = rng.choice(commands)
+    if cmd == "chimeras_denovo":
+        return (cmd,) + draw_long(rng)
     length = rng.choice(LENGTHS)
     o, cli = {}, []
     mask = rng.choice(["none", "soft", "dust"])
@@ -106,12 +152,16 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--max-rounds", type=int, default=0, help="stop after this many rounds (0: run for --seconds): a deterministic set of rounds for a given seed")
     ap.add_argument("--reference-only", action="store_true", help="run the reference alone and count its lines (no device)")
+    ap.add_argument("--commands", default=",".join(COMMANDS), help="the commands a round draws from, comma-separated (also: chimeras_denovo)")
     a = ap.parse_args()
+    commands = a.commands.split(",")
+    if not set(commands) <= set(COMMANDS + ["chimeras_denovo"]):
+        raise SystemExit(f"--commands: {a.commands}")
     if not refcli.available():
         raise SystemExit("oracle/_ref/vsearch_ref missing: make -C oracle ref_full")
     al = None
     if not a.reference_only:
-        from vsearch_amd import Aligner, ChimeraSession, DenovoChimeraSession
+        from vsearch_amd import Aligner, ChimerasDenovoSession, ChimeraSession, DenovoChimeraSession
         al = Aligner()
     rng = random.Random(a.seed)
     t_end = time.time() + a.seconds
@@ -122,7 +172,53 @@ def main():
     with tempfile.TemporaryDirectory(prefix="vsxsoakc_") as tmp:
         qf, df, uo = os.path.join(tmp, "q.fa"), os.path.join(tmp, "db.fa"), os.path.join(tmp, "u.tsv")
         while time.time() < t_end and (a.max_rounds <= 0 or rounds < a.max_rounds):
-            cmd, (length, div), o, cli = draw(rng)
+            cmd, (length, div), o, cli, *sizes = draw(rng, commands)
+            if cmd == "chimeras_denovo":
+                rounds += 1
+                for key in [f"{cmd}@{length[0]}-{length[1]}"] + [k for k in ("hardmask", "abskew", "parts") if k in o] + \
+                        ["diff_pct_host"] * (o.get("diff_pct") == 0.1):
+                    coverage[key] = coverage.get(key, 0) + 1
+                labels, seqs = chimeras_long_data.seeded_set(**sizes[0])
+                full = [cmd] + cli + [f"length={length}", f"n={len(seqs)}"] + [f"{k}={o[k]}" for k in ("window", "search_window") if k in o]
+                t0 = time.time()
+                try:
+                    exp = chimeras_long_data.ref_outputs(tmp, labels, seqs, cli)
+                except Exception as e:
+                    exp = None
+                    bad += 1
+                    if len(failing) < 10:
+                        failing.append({"cli": full, "round": rounds - 1, "error": str(e)[-300:]})
+                ref_seconds += time.time() - t0
+                if exp is None:
+                    continue
+                lines += sum(len(v) for v in exp.values())
+                if a.reference_only:
+                    continue
+                s = ChimerasDenovoSession(al, seqs, labels, **o)
+                recs = s.chimeras_denovo()
+                got = dict(tabbedout=s.tabbedout(), chimeras=s.chimeras, nonchimeras=s.nonchimeras)
+                diff = next(({"what": k, "lines": [len(got[k]), len(exp[k])],
+                              "first_diff": next((i for i, (x, y) in enumerate(zip(got[k], exp[k])) if x != y), min(len(got[k]), len(exp[k])))}
+                             for k in exp if got[k] != exp[k]), None)
+                if diff is None and o.get("diff_pct") == 0.1 and s.stats["queries_kernel"] != 0:
+                    diff = {"what": "diff_pct 0.1 is the host restatement's, the stats count kernel queries", "stats": dict(s.stats)}
+                if diff is None and o.get("diff_pct") != 0.1 and s.stats["queries_kernel"] == 0:
+                    diff = {"what": "no query reached the kernel", "stats": dict(s.stats)}
+                s.close()
+                if diff is None:
+                    os.environ["VSX_CHIMERA"] = "host"
+                    try:
+                        h = ChimerasDenovoSession(al, seqs, labels, **o)
+                        if h.chimeras_denovo() != recs or h.stats["queries_kernel"] != 0:
+                            diff = {"what": "device and host records differ"}
+                        h.close()
+                    finally:
+                        del os.environ["VSX_CHIMERA"]
+                if diff is not None:
+                    bad += 1
+                    if len(failing) < 10:
+                        failing.append({"cli": full, "round": rounds - 1, **diff})
+                continue
             if cmd == "uchime_ref":
                 tn, db, qn, qs = ref_data(rng, length, div)
                 refcli.write_fasta(df, tn, db)
@@ -161,7 +257,8 @@ def main():
         al.close()
     out = {"rounds": rounds, "lines": lines, "failing_rounds": bad, "failures": failing, "seed": a.seed, "seconds": a.seconds,
            "reference_seconds": round(ref_seconds, 3), "coverage": coverage,
-           "what": "vsx_uchime_ref / vsx_uchime_denovo vs vsearch_ref --uchime_ref / --uchime*_denovo --uchimeout with the same randomly drawn options"}
+           "what": "vsx_uchime_ref / vsx_uchime_denovo vs vsearch_ref --uchime_ref / --uchime*_denovo --uchimeout with the same randomly drawn options"
+                   + ("; vsx_chimeras_denovo vs --chimeras_denovo --tabbedout / --chimeras / --nonchimeras, device vs VSX_CHIMERA=host" if "chimeras_denovo" in commands else "")}
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:

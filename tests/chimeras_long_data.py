@@ -177,13 +177,14 @@ def _chimera(rng, parents):
     return "".join(p[edges[i]:edges[i + 1]] for i, p in enumerate(parents))
 
 
-def seeded_set(seed=31, n_families=24, members=(3, 7), n_chimeras=70, n_long=4):
-    """(labels, sequences) in a shuffled input order: fewer than 300 sequences"""
+def seeded_set(seed=31, n_families=24, members=(3, 7), n_chimeras=70, n_long=4, length=(150, 450)):
+    """(labels, sequences) in a shuffled input order: fewer than 300 sequences.  length: the range of the families' lengths (the
+    default is the golden set's)"""
     rng = random.Random(seed)
     seqs, sizes = [], []
     good = []
     for f in range(n_families):
-        anc = common.rnd_seq(rng, rng.randint(150, 450))
+        anc = common.rnd_seq(rng, rng.randint(*length))
         for m in range(rng.randint(*members)):
             good.append(common.mutate(rng, anc, 0.03))
     lanc = common.rnd_seq(rng, 1500)

@@ -172,8 +172,9 @@ def _set(name, opts, quals, commands=None):
     return {"name": name, "opts": opts, "quals": list(quals), "commands": list(commands or BOTH)}
 
 
-def declining(rng, n, read_len, ascii=33):
-    """n reads of lengths 0 .. read_len (most of them full length) whose qualities decay toward the 3' end, with dips"""
+def declining(rng, n, read_len, ascii=33, qrange=(0, 41)):
+    """n reads of lengths 0 .. read_len (most of them full length) whose qualities decay toward the 3' end, with dips, clipped to
+    qrange (the default changes nothing)"""
     quals = []
     for _ in range(n):
         L = int(rng.integers(0, read_len + 1)) if rng.random() < 0.3 else read_len
@@ -181,12 +182,13 @@ def declining(rng, n, read_len, ascii=33):
         q = np.clip(np.rint(start - drop * (np.arange(L) / max(L, 1)) ** 2 + rng.normal(0, 3.0, L)), 0, 41).astype(int)
         if L and rng.random() < 0.3:
             q[rng.integers(0, L, rng.integers(1, 4))] = rng.integers(0, 12)
+        q = np.clip(q, qrange[0], qrange[1])
         quals.append("".join(chr(ascii + int(v)) for v in q))
     return quals
 
 
-def generate(seed, n, read_len=150, opts=None):
-    return _set(f"generate_{seed}", opts or {}, declining(np.random.default_rng(seed), n, read_len))
+def generate(seed, n, read_len=150, opts=None, ascii=33, qrange=(0, 41)):
+    return _set(f"generate_{seed}", opts or {}, declining(np.random.default_rng(seed), n, read_len, ascii=ascii, qrange=qrange))
 
 
 UNSORTED_CUTOFFS = [3.0, 0.25, 1.0, 0.05, 10.0, 0.5, 2.0, 0.001]

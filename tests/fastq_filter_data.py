@@ -327,9 +327,10 @@ def draw_opts(rng, read_len):
     return o
 
 
-def generate(seed, n, read_len=150, paired=False, opts=None):
+def generate(seed, n, read_len=150, paired=False, opts=None, ascii=33, qrange=(0, 41)):
     """-> a set of n seeded random reads (lengths 0 .. read_len, qualities decaying toward the 3' end with dips, Ns, lower case,
-    abundances 1 .. 50) with drawn options (draw_opts) unless `opts` is given"""
+    abundances 1 .. 50) with drawn options (draw_opts) unless `opts` is given; qualities inside qrange, written at offset `ascii`
+    (the defaults leave every seeded set as it was: the clip to (0, 41) changes nothing and no random number is drawn for it)"""
     rng = np.random.default_rng(seed)
 
     def side(tag):
@@ -340,13 +341,14 @@ def generate(seed, n, read_len=150, paired=False, opts=None):
             q = np.clip(np.rint(start - drop * (np.arange(L) / max(L, 1)) ** 2 + rng.normal(0, 3.0, L)), 0, 41).astype(int)
             if L and rng.random() < 0.3:
                 q[rng.integers(0, L, rng.integers(1, 4))] = rng.integers(0, 12)
+            q = np.clip(q, qrange[0], qrange[1])
             s = _seq(rng, L)
             if L and rng.random() < 0.3:
                 for p in rng.integers(0, L, rng.integers(1, 5)):
                     s = _put(s, int(p), "Nn"[int(p) % 2])
             if rng.random() < 0.1:
                 s = s.lower()
-            reads.append((f"{tag}{k}", s, "".join(chr(33 + int(v)) for v in q), int(rng.integers(1, 51)) if rng.random() < 0.5 else 1))
+            reads.append((f"{tag}{k}", s, "".join(chr(ascii + int(v)) for v in q), int(rng.integers(1, 51)) if rng.random() < 0.5 else 1))
         return reads
 
     o = draw_opts(rng, read_len) if opts is None else opts

@@ -219,10 +219,10 @@ def _q(values, ascii=33):
     return "".join(chr(ascii + v) for v in values)
 
 
-def generate(seed, n, read_len=150, opts=None, tail=4):
+def generate(seed, n, read_len=150, opts=None, tail=4, ascii=33, qrange=(0, 41)):
     """n reads of lengths 0 .. read_len with declining qualities (eestats_data.declining); every fifth read ends in a quality tail"""
     rng = np.random.default_rng(seed)
-    quals = eestats_data.declining(rng, n, read_len)
+    quals = eestats_data.declining(rng, n, read_len, ascii=ascii, qrange=qrange)
     for k in range(0, n, 5):
         t = int(rng.integers(1, 9))
         if len(quals[k]) >= t:

@@ -22,6 +22,8 @@ import tempfile
 
 import numpy as np
 
+from tests import common
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 GOLDEN = os.path.join(HERE, "golden", "hitout_golden.json")
@@ -588,6 +590,30 @@ def cli_sets():
             _cli("dust_hardmask", opts=dict(dust, hardmask=1), fmt=dict(output_no_hits=1), inputs=pick(0, 5, 6, 7), search_args=two),
             _cli("n_mismatch", opts=dict(n_mismatch=1), inputs=pick(8), search_args=two),
             _cli("exact", command="search_exact", search_args=(), fmt=dict(output_no_hits=1), inputs=pick(0, 5, 7))]
+
+
+def live_inputs(seed, n_db=2000, n_q=2000):
+    """families of four (3 % apart) with a low-complexity stretch in every fifth family; queries: mutated members on either strand,
+    some with overhangs, a twentieth random"""
+    rng = random.Random(seed)
+    db = []
+    for f in range(n_db // 4):
+        anc = common.rnd_seq(rng, rng.randrange(180, 260))
+        if f % 5 == 0:
+            p = rng.randrange(20, 100)
+            anc = anc[:p] + rng.choice(("AC", "A", "TTG")) * 12 + anc[p:]
+        db += [anc] + [common.mutate(rng, anc, 0.03) for _ in range(3)]
+    qs = []
+    for _ in range(n_q):
+        if rng.random() < 0.05:
+            qs.append(common.rnd_seq(rng, 200))
+            continue
+        q = common.mutate(rng, db[rng.randrange(len(db))], 0.02)
+        q = q[rng.randrange(0, 12):len(q) - rng.randrange(0, 12)]
+        if rng.random() < 0.2:
+            q = common.rnd_seq(rng, 5) + q
+        qs.append(revcomp(q) if rng.random() < 0.4 else q)
+    return db, qs
 
 
 INPUT_KEYS = ("name", "command", "db", "queries", "opts", "fmt", "search_args", "names", "db_names")

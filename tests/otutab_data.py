@@ -125,7 +125,10 @@ def seq_ids(s):
 def inputs(s):
     """-> (query labels, target labels, q_target, sizes or None, matched or None): what vsx_otutab is given"""
     q = [cut(l) for l in s["q"]] if s["trunc"] else s["q"]
-    sizes = s["sizes"] if s["sizes"] is not None else (sizes_of(q) if s["sizein"] else None)
+    # a search command hands otutable_add the header's ;size= annotation with or without --sizein (commands/search_exact.cpp:489,
+    # usearch_global.cpp:448: fastx_get_abundance); only the clustering commands resolve --sizein first (core/cluster.cpp)
+    annotated = s["sizein"] or s["kind"] == "search"
+    sizes = s["sizes"] if s["sizes"] is not None else (sizes_of(q) if annotated else None)
     if s["kind"] == "cluster":
         ncl = max(s["clusterno"]) + 1 if s["clusterno"] else 0
         centroid = {}

@@ -12,7 +12,6 @@ import sys
 import numpy as np
 import pytest
 
-from tests import common
 from tests import hitout_data as hd
 from vsearch_amd import hitout as ho
 
@@ -162,32 +161,8 @@ def test_digest_under_poisoned_memory(aligners):
 
 
 # ---- against the live CLI -----------------------------------------------------------------------------------------------------------
-def live_inputs(seed, n_db=2000, n_q=2000):
-    """families of four (3 % apart) with a low-complexity stretch in every fifth family; queries: mutated members on either strand,
-    some with overhangs, a twentieth random"""
-    rng = random.Random(seed)
-    db = []
-    for f in range(n_db // 4):
-        anc = common.rnd_seq(rng, rng.randrange(180, 260))
-        if f % 5 == 0:
-            p = rng.randrange(20, 100)
-            anc = anc[:p] + rng.choice(("AC", "A", "TTG")) * 12 + anc[p:]
-        db += [anc] + [common.mutate(rng, anc, 0.03) for _ in range(3)]
-    qs = []
-    for _ in range(n_q):
-        if rng.random() < 0.05:
-            qs.append(common.rnd_seq(rng, 200))
-            continue
-        q = common.mutate(rng, db[rng.randrange(len(db))], 0.02)
-        q = q[rng.randrange(0, 12):len(q) - rng.randrange(0, 12)]
-        if rng.random() < 0.2:
-            q = common.rnd_seq(rng, 5) + q
-        qs.append(hd.revcomp(q) if rng.random() < 0.4 else q)
-    return db, qs
-
-
 def live_set(name, command, opts, fmt, search_args, seed):
-    db, qs = live_inputs(seed)
+    db, qs = hd.live_inputs(seed)
     return hd._cli(name, opts=opts, fmt=fmt, search_args=search_args, command=command, inputs=(db, qs))
 
 
@@ -219,7 +194,7 @@ def test_usearch_global_against_the_live_cli(aligners, tmp_path, hardmask):
 
 @needs_cli
 def test_search_exact_against_the_live_cli(aligners, tmp_path):
-    db, qs = live_inputs(491)
+    db, qs = hd.live_inputs(491)
     rng = random.Random(499)
     qs = [(hd.revcomp(db[rng.randrange(len(db))]) if k % 3 == 0 else db[rng.randrange(len(db))]) if k % 10 else q for k, q in enumerate(qs)]
     db = db + db[:40]                                                                 # duplicates: second hits

@@ -68,6 +68,19 @@ def test_the_issues_worked_examples(golden):
     assert by["recorded_cluster_relabel"]["ref"]["otutabout"] == "#OTU ID\ts1\ts1_a\ts2\nOTU_1\t0\t4\t2\nOTU_2\t1\t0\t0\n"
 
 
+def test_annotated_abundance_counts_without_sizein():
+    """found by oracle/soak_commands.py --command otutab: --search_exact and --usearch_global hand otutable_add the header's
+    ;size= annotation whether or not --sizein is given; inputs() used to count 1 per query without --sizein.  The expected text is
+    the reference CLI's own for this input, with and without --sizein."""
+    import os
+    for sizein in (False, True):
+        s = od.search_set("annotated", ["a;sample=s;size=5", "b;sample=s"], ["o1"], [0, 0], sizein=sizein)
+        assert od.inputs(s)[3] == [5, 1]
+        assert od.texts(od.call(None, s, host=True))["otutabout"] == "#OTU ID\ts\no1\t6\n"
+        if os.path.exists(od.ref_binary()):
+            assert od.run_reference(s)["otutabout"] == "#OTU ID\ts\no1\t6\n"
+
+
 def test_random_label_sets():
     for seed in range(3000):
         q, t, q_target, sizes, matched = od.random_label_set(seed)

@@ -89,7 +89,8 @@ def _names(blob, nbytes, off, lens, n, none_ok=False):
 
 def otutab(qlabels, tlabels, q_target, sizes=None, matched=None, aligner=None, threads=0, _host=False):
     """Build the table.  qlabels / tlabels: lists of str or bytes, or LabelBlob.  q_target: per query the number of its first hit's
-    target, NONE without a hit.  sizes: the queries' abundances (--sizein; default 1 each).  matched: per target whether any hit
+    target, NONE without a hit.  sizes: the queries' abundances (default 1 each; the reference's search commands pass the header's
+    ;size= annotation with or without --sizein, its clustering commands only with --sizein).  matched: per target whether any hit
     reached it (a search: the others enter the table with no counts), or None (a clustering: no such pass).  aligner: an Aligner
     (its device runs the kernels), or None for the host restatement.  A value the library refuses raises VsxError (VSX_EINVAL)."""
     lib = _lib.load()
