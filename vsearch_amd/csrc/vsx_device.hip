@@ -1107,6 +1107,7 @@ struct __attribute__((aligned(4))) Quad { u32 x, y, z, w; };
 struct __attribute__((aligned(4))) Trio { u32 x, y, z; };
 
 #include "vsx_accept.h"
+#include "vsx_tbtext.h"
 
 // -DVSX_TB_STATS=1 (A/B build, measurements only): what the checkpoint traceback does per launch -- [0] wave iterations of the
 // tile loop, [1] busy (pair, tile) visits, [2] distinct tiles among the <= 8 lanes of a task summed over the iterations (= how
@@ -1147,7 +1148,7 @@ vsx_traceback_ck_kernel(const VsxDevParams P, const VsxFilterDev FL, const VsxTa
                         const u32 * __restrict__ ck, const VsxSlotOut * __restrict__ slot,
                         u32 * __restrict__ slab, const uint64_t * __restrict__ slab_off,
                         u32 * __restrict__ runs, uint64_t runs_capacity, unsigned long long * cursor,
-                        VsxPairOut * __restrict__ out)
+                        VsxPairOut * __restrict__ out, const VsxTextOut TX)
 {
   typedef TbOps<FAST> A;
   static_assert(VSX_RB == 1, "the tile staging below reads row checkpoints as two-step (16-byte) pairs");
@@ -1578,76 +1579,89 @@ vsx_traceback_ck_kernel(const VsxDevParams P, const VsxFilterDev FL, const VsxTa
 #if VSX_TB_STATS
   if (valid) atomicAdd(&vsx_tb_stats_dev[5], 1ull);
 #endif
-  if (!valid) return;
-
+  // (no lane leaves before the end: the marshalling forms a prefix over the whole wave)
+  const u32 pid = valid ? pair_ids[k] : 0u;
+  bool have_runs = true;
+  u32 tlen = 1;                                          // bytes of the pair's CIGAR text, the NUL included
   VsxPairOut o;
   o.pad = 0; o.nruns = 0; o.run_off = 0;
-  if (so.overflow)
+  o.score = 32767; o.aligned = 0; o.matches = 0; o.mismatches = 0; o.gaps = 0;
+  if (valid && so.overflow)
     {
-      o.score = 32767; o.aligned = 0; o.matches = 0; o.mismatches = 0; o.gaps = 0;
-      out[pair_ids[k]] = o;
-      rank_note(FL, pair_ids[k], 0u, 32767, 0.0);
-      return;
+      out[pid] = o;
+      rank_note(FL, pid, 0u, 32767, 0.0);
     }
-  if (i >= 0) { al += (u32) (i + 1); if (op != 2) ++ga; push_n(2, (u32) (i + 1)); }     // left-terminal runs
-  if (j >= 0) { al += (u32) (j + 1); if (op != 1) ++ga; push_n(1, (u32) (j + 1)); }
-  if (op >= 0) my[nruns++] = (runlen << 2) | (u32) op;
+  if (live)
+    {
+      if (i >= 0) { al += (u32) (i + 1); if (op != 2) ++ga; push_n(2, (u32) (i + 1)); }     // left-terminal runs
+      if (j >= 0) { al += (u32) (j + 1); if (op != 1) ++ga; push_n(1, (u32) (j + 1)); }
+      if (op >= 0) my[nruns++] = (runlen << 2) | (u32) op;
 
-  // matches / mismatches of the M runs (the walk above makes no dependent global loads): replay the runs from the end
-  u32 ma = 0, mi = 0;
-  {
-    int qi = Q - 1, tj = D - 1;
-    for (u32 x = 0; x < nruns; ++x)
+      // matches / mismatches of the M runs (the walk above makes no dependent global loads): replay the runs from the end
+      u32 ma = 0, mi = 0;
       {
-        const u32 w = my[x];
-        const int len = (int) (w >> 2);
-        const u32 o2 = w & 3u;
-        if (o2 == 0)
+        int qi = Q - 1, tj = D - 1;
+        for (u32 x = 0; x < nruns; ++x)
           {
-            // eight cells per trip: the symbols are the 8 bytes ENDING at q[qi - b] / d[tj - b] (unaligned 64-bit loads, the
-            // code buffers have slack in front); byte u of a chunk is cell kk = 7 - u of the trip
-            for (int b = 0; b < len; b += 8)
+            const u32 w = my[x];
+            const int len = (int) (w >> 2);
+            if (VSX_TB_FUSED_TEXT) tlen += vsx_cigar_run_len(w);
+            const u32 o2 = w & 3u;
+            if (o2 == 0)
               {
-                const int rem = (len - b < 8) ? len - b : 8;
-                const unsigned long long aw = *reinterpret_cast<const u64_unaligned *>(q + (qi - b - 7));
-                const unsigned long long cw = *reinterpret_cast<const u64_unaligned *>(d + (tj - b - 7));
-                const unsigned long long ones = 0x0101010101010101ull;
-                const unsigned long long x = aw & cw;
-                unsigned long long t = (x | (x >> 1) | (x >> 2) | (x >> 3)) & ones;            // codes share a nucleotide
-                if (P.n_mismatch)
+                // eight cells per trip: the symbols are the 8 bytes ENDING at q[qi - b] / d[tj - b] (unaligned 64-bit loads, the
+                // code buffers have slack in front); byte u of a chunk is cell kk = 7 - u of the trip
+                for (int b = 0; b < len; b += 8)
                   {
-                    const unsigned long long a15 = aw & (aw >> 1) & (aw >> 2) & (aw >> 3);
-                    const unsigned long long c15 = cw & (cw >> 1) & (cw >> 2) & (cw >> 3);
-                    t &= ~(a15 | c15);                                                         // N never matches (:1191-1206)
+                    const int rem = (len - b < 8) ? len - b : 8;
+                    const unsigned long long aw = *reinterpret_cast<const u64_unaligned *>(q + (qi - b - 7));
+                    const unsigned long long cw = *reinterpret_cast<const u64_unaligned *>(d + (tj - b - 7));
+                    const unsigned long long ones = 0x0101010101010101ull;
+                    const unsigned long long x = aw & cw;
+                    unsigned long long t = (x | (x >> 1) | (x >> 2) | (x >> 3)) & ones;            // codes share a nucleotide
+                    if (P.n_mismatch)
+                      {
+                        const unsigned long long a15 = aw & (aw >> 1) & (aw >> 2) & (aw >> 3);
+                        const unsigned long long c15 = cw & (cw >> 1) & (cw >> 2) & (cw >> 3);
+                        t &= ~(a15 | c15);                                                         // N never matches (:1191-1206)
+                      }
+                    t &= ~0ull << (8 * (8 - rem));
+                    const u32 m8 = (u32) __builtin_popcountll(t);
+                    ma += m8;
+                    mi += (u32) rem - m8;
                   }
-                t &= ~0ull << (8 * (8 - rem));
-                const u32 m8 = (u32) __builtin_popcountll(t);
-                ma += m8;
-                mi += (u32) rem - m8;
+                qi -= len; tj -= len;
               }
-            qi -= len; tj -= len;
+            else if (o2 == 1) tj -= len;
+            else qi -= len;
           }
-        else if (o2 == 1) tj -= len;
-        else qi -= len;
       }
-  }
 
-  u32 verdict = 0;
-  double idv = 0.0;
-  if (FL.enabled && nruns > 0) verdict = accept_verdict(FL, Q, D, (int) al, (int) ma, (int) mi, (int) ga, my[nruns - 1], my[0], &idv);
-  if (verdict == 3u) nruns = 0;                          // rejected: the runs never leave the device
-  rank_note(FL, pair_ids[k], verdict, (int) so.score, idv);
+      u32 verdict = 0;
+      double idv = 0.0;
+      if (FL.enabled && nruns > 0) verdict = accept_verdict(FL, Q, D, (int) al, (int) ma, (int) mi, (int) ga, my[nruns - 1], my[0], &idv);
+      if (verdict == 3u) nruns = 0;                          // rejected: the runs never leave the device
+      rank_note(FL, pid, verdict, (int) so.score, idv);
 
-  const unsigned long long base = atomicAdd(cursor, (unsigned long long) nruns);
-  if (base + nruns <= runs_capacity)
-    for (u32 x = 0; x < nruns; ++x) runs[base + x] = my[x];
+      const unsigned long long base = atomicAdd(cursor, (unsigned long long) nruns);
+      have_runs = base + nruns <= runs_capacity;
+      if (!VSX_TB_FUSED_TEXT && have_runs)               // (fused: vsx_marshal_pair copies the words while it formats them)
+        for (u32 x = 0; x < nruns; ++x) runs[base + x] = my[x];
 
-  o.score = so.score;
-  o.aligned = (uint16_t) al; o.matches = (uint16_t) ma; o.mismatches = (uint16_t) mi; o.gaps = (uint16_t) ga;
-  o.pad = (uint16_t) verdict;
-  o.nruns = nruns;
-  o.run_off = base;
-  out[pair_ids[k]] = o;
+      o.score = so.score;
+      o.aligned = (uint16_t) al; o.matches = (uint16_t) ma; o.mismatches = (uint16_t) mi; o.gaps = (uint16_t) ga;
+      o.pad = (uint16_t) verdict;
+      o.nruns = nruns;
+      o.run_off = base;
+      out[pid] = o;
+    }
+#if VSX_TB_FUSED_TEXT
+  // run words -> dense run buffer and CIGAR text in one pass, record -> output arrays (vsx_tbtext.h); the record above and the dense
+  // run words are still written: the exports, the hit writers and a re-run of the text alone read them
+  vsx_marshal_pair(valid, pid, o, my, have_runs ? o.nruns : 0u, tlen, runs, TX);
+#else
+  (void) tlen;           // (vsx_cigar_text_kernel reads the record and the dense run words)
+#endif
 }
 
 
@@ -1719,7 +1733,7 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
                           const u32 * __restrict__ ck, const VsxSlotOut * __restrict__ slot,
                           u32 * __restrict__ slab, const uint64_t * __restrict__ slab_off,
                           u32 * __restrict__ runs, uint64_t runs_capacity, unsigned long long * cursor,
-                          VsxPairOut * __restrict__ out)
+                          VsxPairOut * __restrict__ out, const VsxTextOut TX)
 {
   static_assert(R >= 4 && (!MID || R % 2 == 0), "R = 1 keeps the first kernel");
   constexpr int RT = MID ? R / 2 : R;              // rows of a tile
@@ -2257,74 +2271,85 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
       for (int k2 = 0; k2 < 6; ++k2) atomicAdd(&vsx_tb_stats_dev[8 + k2], tphase[k2]);
     }
 #endif
-  if (!valid) return;
-
+  // (no lane leaves before the end: the marshalling forms a prefix over the whole wave)
+  const u32 pid = valid ? pair_ids[k] : 0u;
+  bool have_runs = true;
+  u32 tlen = 1;                                          // bytes of the pair's CIGAR text, the NUL included
   VsxPairOut o;
   o.pad = 0; o.nruns = 0; o.run_off = 0;
-  if (so.overflow)
+  o.score = 32767; o.aligned = 0; o.matches = 0; o.mismatches = 0; o.gaps = 0;
+  if (valid && so.overflow)
     {
-      o.score = 32767; o.aligned = 0; o.matches = 0; o.mismatches = 0; o.gaps = 0;
-      out[pair_ids[k]] = o;
-      rank_note(FL, pair_ids[k], 0u, 32767, 0.0);
-      return;
+      out[pid] = o;
+      rank_note(FL, pid, 0u, 32767, 0.0);
     }
-  if (i >= 0) { al += (u32) (i + 1); if (op != 2) ++ga; push_n(2, (u32) (i + 1)); }     // left-terminal runs
-  if (j >= 0) { al += (u32) (j + 1); if (op != 1) ++ga; push_n(1, (u32) (j + 1)); }
-  if (op >= 0) my[nruns++] = (runlen << 2) | (u32) op;
+  if (live)
+    {
+      if (i >= 0) { al += (u32) (i + 1); if (op != 2) ++ga; push_n(2, (u32) (i + 1)); }     // left-terminal runs
+      if (j >= 0) { al += (u32) (j + 1); if (op != 1) ++ga; push_n(1, (u32) (j + 1)); }
+      if (op >= 0) my[nruns++] = (runlen << 2) | (u32) op;
 
-  // matches / mismatches of the M runs: replay the runs from the end, eight symbols a trip (see the first kernel)
-  u32 ma = 0, mi = 0;
-  {
-    int qi = Q - 1, tj = D - 1;
-    for (u32 x = 0; x < nruns; ++x)
+      // matches / mismatches of the M runs: replay the runs from the end, eight symbols a trip (see the first kernel)
+      u32 ma = 0, mi = 0;
       {
-        const u32 w = my[x];
-        const int len = (int) (w >> 2);
-        const u32 o2 = w & 3u;
-        if (o2 == 0)
+        int qi = Q - 1, tj = D - 1;
+        for (u32 x = 0; x < nruns; ++x)
           {
-            for (int b = 0; b < len; b += 8)
+            const u32 w = my[x];
+            const int len = (int) (w >> 2);
+            if (VSX_TB_FUSED_TEXT) tlen += vsx_cigar_run_len(w);
+            const u32 o2 = w & 3u;
+            if (o2 == 0)
               {
-                const int rem = (len - b < 8) ? len - b : 8;
-                const unsigned long long aw = *reinterpret_cast<const u64_unaligned *>(q + (qi - b - 7));
-                const unsigned long long cw = *reinterpret_cast<const u64_unaligned *>(d + (tj - b - 7));
-                const unsigned long long ones = 0x0101010101010101ull;
-                const unsigned long long x2 = aw & cw;
-                unsigned long long t = (x2 | (x2 >> 1) | (x2 >> 2) | (x2 >> 3)) & ones;
-                if (P.n_mismatch)
+                for (int b = 0; b < len; b += 8)
                   {
-                    const unsigned long long a15 = aw & (aw >> 1) & (aw >> 2) & (aw >> 3);
-                    const unsigned long long c15 = cw & (cw >> 1) & (cw >> 2) & (cw >> 3);
-                    t &= ~(a15 | c15);
+                    const int rem = (len - b < 8) ? len - b : 8;
+                    const unsigned long long aw = *reinterpret_cast<const u64_unaligned *>(q + (qi - b - 7));
+                    const unsigned long long cw = *reinterpret_cast<const u64_unaligned *>(d + (tj - b - 7));
+                    const unsigned long long ones = 0x0101010101010101ull;
+                    const unsigned long long x2 = aw & cw;
+                    unsigned long long t = (x2 | (x2 >> 1) | (x2 >> 2) | (x2 >> 3)) & ones;
+                    if (P.n_mismatch)
+                      {
+                        const unsigned long long a15 = aw & (aw >> 1) & (aw >> 2) & (aw >> 3);
+                        const unsigned long long c15 = cw & (cw >> 1) & (cw >> 2) & (cw >> 3);
+                        t &= ~(a15 | c15);
+                      }
+                    t &= ~0ull << (8 * (8 - rem));
+                    const u32 m8 = (u32) __builtin_popcountll(t);
+                    ma += m8;
+                    mi += (u32) rem - m8;
                   }
-                t &= ~0ull << (8 * (8 - rem));
-                const u32 m8 = (u32) __builtin_popcountll(t);
-                ma += m8;
-                mi += (u32) rem - m8;
+                qi -= len; tj -= len;
               }
-            qi -= len; tj -= len;
+            else if (o2 == 1) tj -= len;
+            else qi -= len;
           }
-        else if (o2 == 1) tj -= len;
-        else qi -= len;
       }
-  }
 
-  u32 verdict = 0;
-  double idv = 0.0;
-  if (FL.enabled && nruns > 0) verdict = accept_verdict(FL, Q, D, (int) al, (int) ma, (int) mi, (int) ga, my[nruns - 1], my[0], &idv);
-  if (verdict == 3u) nruns = 0;
-  rank_note(FL, pair_ids[k], verdict, (int) so.score, idv);
+      u32 verdict = 0;
+      double idv = 0.0;
+      if (FL.enabled && nruns > 0) verdict = accept_verdict(FL, Q, D, (int) al, (int) ma, (int) mi, (int) ga, my[nruns - 1], my[0], &idv);
+      if (verdict == 3u) nruns = 0;
+      rank_note(FL, pid, verdict, (int) so.score, idv);
 
-  const unsigned long long base = atomicAdd(cursor, (unsigned long long) nruns);
-  if (base + nruns <= runs_capacity)
-    for (u32 x = 0; x < nruns; ++x) runs[base + x] = my[x];
+      const unsigned long long base = atomicAdd(cursor, (unsigned long long) nruns);
+      have_runs = base + nruns <= runs_capacity;
+      if (!VSX_TB_FUSED_TEXT && have_runs)               // (fused: vsx_marshal_pair copies the words while it formats them)
+        for (u32 x = 0; x < nruns; ++x) runs[base + x] = my[x];
 
-  o.score = so.score;
-  o.aligned = (uint16_t) al; o.matches = (uint16_t) ma; o.mismatches = (uint16_t) mi; o.gaps = (uint16_t) ga;
-  o.pad = (uint16_t) verdict;
-  o.nruns = nruns;
-  o.run_off = base;
-  out[pair_ids[k]] = o;
+      o.score = so.score;
+      o.aligned = (uint16_t) al; o.matches = (uint16_t) ma; o.mismatches = (uint16_t) mi; o.gaps = (uint16_t) ga;
+      o.pad = (uint16_t) verdict;
+      o.nruns = nruns;
+      o.run_off = base;
+      out[pid] = o;
+    }
+#if VSX_TB_FUSED_TEXT
+  vsx_marshal_pair(valid, pid, o, my, have_runs ? o.nruns : 0u, tlen, runs, TX);      // as in the first kernel
+#else
+  (void) tlen;
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2546,11 +2571,11 @@ template <int R, bool MID>
 static hipError_t launch_tbtilt(const VsxDevParams & P, const VsxFilterDev & F, const VsxTask * d_tasks, const uint32_t * d_pair_slot,
                                 const uint32_t * d_pair_ids, uint32_t npairs, const uint8_t * q, const uint8_t * t,
                                 const uint32_t * ck, const VsxSlotOut * slot, uint32_t * slab, const uint64_t * slab_off,
-                                uint32_t * runs, uint64_t cap, unsigned long long * cursor, VsxPairOut * out, hipStream_t st)
+                                uint32_t * runs, uint64_t cap, unsigned long long * cursor, VsxPairOut * out, const VsxTextOut & tx, hipStream_t st)
 {
   if constexpr (R >= 4)
     hipLaunchKernelGGL((vsx_traceback_tilt_kernel<R, MID>), dim3((npairs + 63) / 64), dim3(64), 0, st,
-                       P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, cap, cursor, out);
+                       P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, cap, cursor, out, tx);
   return hipGetLastError();
 }
 
@@ -2558,10 +2583,10 @@ template <int R, bool FAST, bool CK8 = false, bool MID = false>
 static hipError_t launch_tbck(const VsxDevParams & P, const VsxFilterDev & F, const VsxTask * d_tasks, const uint32_t * d_pair_slot,
                               const uint32_t * d_pair_ids, uint32_t npairs, const uint8_t * q, const uint8_t * t,
                               const uint32_t * ck, const VsxSlotOut * slot, uint32_t * slab, const uint64_t * slab_off,
-                              uint32_t * runs, uint64_t cap, unsigned long long * cursor, VsxPairOut * out, hipStream_t st)
+                              uint32_t * runs, uint64_t cap, unsigned long long * cursor, VsxPairOut * out, const VsxTextOut & tx, hipStream_t st)
 {
   hipLaunchKernelGGL((vsx_traceback_ck_kernel<R, FAST, CK8, MID>), dim3((npairs + 127) / 128), dim3(128), 0, st,
-                     P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, cap, cursor, out);
+                     P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, cap, cursor, out, tx);
   return hipGetLastError();
 }
 
@@ -2571,16 +2596,16 @@ extern "C" hipError_t vsx_launch_traceback_ck(int rows, int fast16, VsxDevParams
                                               const uint32_t * ck, const VsxSlotOut * slot,
                                               uint32_t * slab, const uint64_t * slab_off,
                                               uint32_t * runs, uint64_t runs_capacity, unsigned long long * cursor,
-                                              VsxPairOut * out, hipStream_t st)
+                                              VsxPairOut * out, VsxTextOut tx, hipStream_t st)
 {
   if (npairs == 0) return hipSuccess;
   int dev_now = 0;
   if (hipGetDevice(&dev_now) != hipSuccess) { (void) hipGetLastError(); dev_now = 64; }
   const bool v2 = g_tb_v1_dev[dev_now < 0 || dev_now > 64 ? 64 : dev_now].load(std::memory_order_relaxed) == 0;
-#define TBCK(RR) case RR: return (fast16 && P.tilt != 0 && v2 && RR >= 4) ? launch_tbtilt<RR, VSX_MID(RR, true)>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st) \
-                                 : (fast16 && P.tilt != 0) ? launch_tbck<RR, true, true, VSX_MID(RR, true)>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st) \
-                                 : fast16 ? launch_tbck<RR, true>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st) \
-                                        : launch_tbck<RR, false>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, st)
+#define TBCK(RR) case RR: return (fast16 && P.tilt != 0 && v2 && RR >= 4) ? launch_tbtilt<RR, VSX_MID(RR, true)>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, tx, st) \
+                                 : (fast16 && P.tilt != 0) ? launch_tbck<RR, true, true, VSX_MID(RR, true)>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, tx, st) \
+                                 : fast16 ? launch_tbck<RR, true>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, tx, st) \
+                                        : launch_tbck<RR, false>(P, F, d_tasks, d_pair_slot, d_pair_ids, npairs, q, t, ck, slot, slab, slab_off, runs, runs_capacity, cursor, out, tx, st)
   switch (rows)
     {
     TBCK(1); TBCK(4); TBCK(8); TBCK(10); TBCK(12); TBCK(14); TBCK(16); TBCK(18); TBCK(20); TBCK(22); TBCK(24); TBCK(26); TBCK(28); TBCK(32);

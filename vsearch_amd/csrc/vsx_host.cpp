@@ -448,7 +448,7 @@ struct vsx_plan {
   PoolBuf<VsxSlotOut> d_slot;
   PoolBuf<VsxPairOut> d_out;
   PoolBuf<unsigned long long> d_cursor;  // [0] run words used, [1] text bytes used, [2] DP steps skipped (vsx_forward_kernel EARLY)
-  PoolBuf<uint8_t> d_text, d_soa;        // CIGAR text and the output arrays, written by vsx_cigar_text_kernel (vsx_tbtext.hip)
+  PoolBuf<uint8_t> d_text, d_soa;        // CIGAR text and the output arrays, written by the traceback epilogues (vsx_tbtext.h)
   // r06, ranked plans: the lists the traceback's epilogue fills (VsxFilterDev::rank_counts ...), see plan_set_ranked()
   PoolBuf<uint32_t> d_rank_counts, d_kept_pair, d_refused_pair;
   PoolBuf<double> d_kept_id;
@@ -1698,6 +1698,7 @@ int vsx_plan_run(vsx_plan * pl)
   VSX_HIP(hipMemsetAsync(pl->d_cursor.p, 0, 3 * sizeof(unsigned long long), st));
   if (pl->filter.rank_counts) VSX_HIP(hipMemsetAsync(pl->d_rank_counts.p, 0, 2 * sizeof(uint32_t), st));      // (every run: settle() may run a plan twice)
   VSX_HIP(hipEventRecord(pl->ev_begin, st));
+  const VsxTextOut tx {pl->d_text.p, pl->text_capacity, pl->d_cursor.p + 1, pl->soa};
   // DP kernels on `st`, tracebacks + text on `st2`.  A plan's DP waits only for the last traceback that read ITS checkpoint
   // block (the context alternates two), so it overlaps the previous plan's traceback; inside a plan the chunks share the block.
   for (size_t k = 0; k < pl->chunks.size(); ++k)
@@ -1742,7 +1743,7 @@ int vsx_plan_run(vsx_plan * pl)
           VSX_HIP(vsx_launch_traceback_ck(L.rows, L.track == 0 ? 1 : 0, Pb, pl->filter, pl->d_tasks.p, pl->d_pair_slot.p + L.pair_first,
                                          pl->d_pair_ids.p + L.pair_first, pair_count, pl->Q->codes(), pl->T->codes(),
                                          dir, pl->d_slot.p, pl->d_slab.p, pl->d_slab_off.p + L.pair_first,
-                                         pl->d_runs.p, pl->runs_capacity, pl->d_cursor.p, pl->d_out.p, st2));
+                                         pl->d_runs.p, pl->runs_capacity, pl->d_cursor.p, pl->d_out.p, tx, st2));
           li = lj;
         }
       VSX_HIP(hipEventRecord(c.e2, st2));
@@ -1750,9 +1751,13 @@ int vsx_plan_run(vsx_plan * pl)
   if (pl->chunks.empty()) VSX_HIP(hipStreamWaitEvent(st2, pl->ev_begin, 0));          // (the cursor memset precedes the text kernel)
   VSX_HIP(hipEventRecord(ctx->ev_tb[slot], st2));
   ctx->ev_tb_used[slot] = true;
-  // run lists -> CIGAR text, records -> output arrays (pushop / finishop are part of the reference's timed path); st2 is in order
-  VSX_HIP(vsx_launch_cigar_text(pl->d_out.p, pl->d_pair_ids.p, (uint32_t) pl->pair_ids.size(), pl->d_runs.p, pl->runs_capacity,
-                               pl->d_text.p, pl->text_capacity, pl->d_cursor.p + 1, pl->soa, st2));
+  // run lists -> CIGAR text, records -> output arrays (pushop / finishop are part of the reference's timed path).  The traceback
+  // epilogues have done that for every pair they visited, and every device pair (pair_ids) belongs to a task of a chunk, whose class
+  // has a traceback launch above: nothing is left for the text kernel (settle() still runs it when only the text buffer was short).
+  // A build without VSX_TB_FUSED_TEXT launches it here for all of them; st2 is in order
+  if (!VSX_TB_FUSED_TEXT || pl->chunks.empty())
+    VSX_HIP(vsx_launch_cigar_text(pl->d_out.p, pl->d_pair_ids.p, (uint32_t) pl->pair_ids.size(), pl->d_runs.p, pl->runs_capacity,
+                                 pl->d_text.p, pl->text_capacity, pl->d_cursor.p + 1, pl->soa, st2));
   VSX_HIP(hipMemcpyAsync(pl->h_cursor, pl->d_cursor.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st2));
   VSX_HIP(hipEventRecord(pl->ev_end, st2));
   pl->ran = true;

@@ -29,6 +29,12 @@
 // Row counts that have a split-profile DP kernel (vsx_forward_kernel SPLIT; the planner's class 16): the ones measured faster than the
 // byte profile.  R = 16 holds 8 KB of tables + 2 KB of feed = 10 240 B of LDS per wave (16 waves per CU), R = 10 6 KB + 2 KB.
 #define VSX_SPLIT_ROWS(R_) ((R_) == 10 || (R_) == 16)
+// VSX_TB_FUSED_TEXT: 1 = the traceback kernels format the CIGAR text and write the output arrays in their epilogue (vsx_tbtext.h
+// vsx_marshal_pair) and vsx_plan_run launches no text kernel behind them; 0 (A/B build) = the traceback leaves records and run words
+// and vsx_cigar_text_kernel does the rest in a launch of its own.  Same-box A/B: profiles/fused_text/INDEX.md.
+#ifndef VSX_TB_FUSED_TEXT
+#define VSX_TB_FUSED_TEXT 1
+#endif
 
 // Device-side constants derived from the 14 post-fixup penalties (reference search16_init,
 // core/align_simd.cpp:1282-1376 and the QR/R vectors at :1629-1649).  "pk" = the int16 value
@@ -108,12 +114,21 @@ struct VsxPairOut {
 };
 
 // The reference's five output arrays (align_simd.hpp:99-108) + verdict + text offset, indexed by pair id, in HBM:
-// written by vsx_cigar_text_kernel, copied to the host as they are.
+// written by the traceback epilogues (or vsx_cigar_text_kernel), copied to the host as they are.
 struct VsxSoaOut {
   int16_t  * score;
   uint16_t * aligned, * matches, * mismatches, * gaps;
   uint8_t  * verdict;
   uint64_t * text_off;
+};
+
+// Where the marshalling of a plan writes (vsx_tbtext.h vsx_marshal_pair): the text buffer, its size in bytes, the cursor the waves
+// allocate their strings from, and the output arrays
+struct VsxTextOut {
+  uint8_t * text;
+  uint64_t text_capacity;
+  unsigned long long * text_cursor;
+  VsxSoaOut soa;
 };
 
 // Ranked, compacted hits in HBM (vsx_rank.hip): entry j = the j-th kept pair in report order
@@ -204,13 +219,14 @@ hipError_t vsx_launch_forward(int rows, int track, int nq, int one /* every task
                               const uint8_t * d_qcodes, const uint8_t * d_tcodes,
                               uint32_t * d_dir, uint2 * d_strip, VsxSlotOut * d_slot, hipStream_t st);
 // fast16: the tasks never saturate (planner's TRACK = 0 class) -> biased-u16 VOP2 arithmetic in the tile recompute
+// tx: where the epilogue writes the CIGAR text and the output arrays (VSX_TB_FUSED_TEXT; not touched in a build without it)
 hipError_t vsx_launch_traceback_ck(int rows, int fast16, VsxDevParams P, VsxFilterDev F, const VsxTask * d_tasks, const uint32_t * d_pair_slot,
                                    const uint32_t * d_pair_ids, uint32_t npairs,
                                    const uint8_t * d_qcodes, const uint8_t * d_tcodes,
                                    const uint32_t * d_ck, const VsxSlotOut * d_slot,
                                    uint32_t * d_slab, const uint64_t * d_slab_off,
                                    uint32_t * d_runs, uint64_t runs_capacity, unsigned long long * d_cursor,
-                                   VsxPairOut * d_out, hipStream_t st);
+                                   VsxPairOut * d_out, VsxTextOut tx, hipStream_t st);
 // bad[0] += disagreements of v_pk_maximum3_f16 with the integer maximum over the MAX3 class's value range (must stay 0)
 hipError_t vsx_launch_max3_selftest(uint32_t * d_bad /* [2]: max3, v_perm sign selectors */, hipStream_t st);
 void vsx_internal_set_tb_v2(int device, int on);      // on == 0: the first traceback kernel for the TILT class on that device

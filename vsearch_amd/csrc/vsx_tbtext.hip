@@ -2,23 +2,18 @@
 //
 // The reference builds the CIGAR string inside its traceback (pushop / finishop, src/core/align_simd.cpp:1013-1049:
 // run-length text written right to left, the count omitted when it is 1) and hands every caller five arrays
-// (pscores / paligned / pmatches / pmismatches / pgaps, align_simd.hpp:99-108).  Here the traceback kernel leaves
-// 24-byte records and a dense buffer of run words ((length << 2) | op, traceback order = last column first);
-// this kernel turns them into exactly those outputs in HBM, so the host only copies (r01 formatted the text with
-// host threads: 0.25 s per 800 k pairs, 8x the kernels).  HBM-bound byte work: ~80 B of runs read and ~60 B of text
-// written per pair, one lane per pair, strings dword-aligned so every store is a full dword.
+// (pscores / paligned / pmatches / pmismatches / pgaps, align_simd.hpp:99-108).  Here the traceback kernels
+// (vsx_device.hip) do the same in their epilogue (vsx_tbtext.h) and also leave 24-byte records and a dense buffer of
+// run words ((length << 2) | op, traceback order = last column first); the kernel below makes the text and the arrays
+// from those: after settle() has enlarged a text buffer that was too small, and in a build without VSX_TB_FUSED_TEXT
+// after every traceback.  HBM-bound byte work, one lane per pair, strings dword-aligned so every store is a full dword.
 #include <hip/hip_runtime.h>
 #include "vsx_internal.h"
+#include "vsx_tbtext.h"
 
 typedef unsigned int u32;
 
-#define DEV __device__ __forceinline__
-
-DEV u32 ndigits(u32 v) { return v >= 10000u ? 5u : v >= 1000u ? 4u : v >= 100u ? 3u : v >= 10u ? 2u : 1u; }
-
-// One lane per GPU pair (k-th entry of pair_ids).  Text bytes of a pair: for each run in TEXT order (= reverse run order)
-// the decimal length if > 1, then 'M' / 'I' / 'D'; a terminating NUL; padded to a multiple of 4.  A wave allocates the
-// strings of its 64 pairs with ONE atomic on the text cursor (they end up back to back in lane order).
+// One lane per GPU pair (k-th entry of pair_ids): the pair's record and its words of the dense run buffer -> text and arrays
 __global__ void __launch_bounds__(256)
 vsx_cigar_text_kernel(const VsxPairOut * __restrict__ out, const u32 * __restrict__ pair_ids, u32 npairs,
                       const u32 * __restrict__ runs, uint64_t runs_capacity,
@@ -33,63 +28,19 @@ vsx_cigar_text_kernel(const VsxPairOut * __restrict__ out, const u32 * __restric
   const bool have_runs = valid && (o.run_off + o.nruns <= runs_capacity);    // an overflowed run buffer is re-run by the host
   const u32 * __restrict__ my = runs + o.run_off;
   const u32 nruns = have_runs ? o.nruns : 0u;
-
-  u32 len = 1;                                           // NUL
-  for (u32 x = 0; x < nruns; ++x)
-    {
-      const u32 n = my[x] >> 2;
-      len += 1u + (n > 1u ? ndigits(n) : 0u);
-    }
-  const u32 len4 = valid ? ((len + 3u) & ~3u) : 0u;
-
-  // wave-level exclusive prefix of len4, one atomic per wave
-  u32 incl = len4;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-    {
-      const u32 v = (u32) __shfl_up((int) incl, d, 64);
-      if ((int) (threadIdx.x & 63) >= d) incl += v;
-    }
-  const u32 total = (u32) __shfl((int) incl, 63, 64);
-  unsigned long long base = 0;
-  if ((threadIdx.x & 63) == 0 && total) base = atomicAdd(text_cursor, (unsigned long long) total);
-  base = (unsigned long long) __shfl((long long) base, 0, 64);
+  const u32 len4 = valid ? ((vsx_cigar_len(my, nruns) + 3u) & ~3u) : 0u;
+  const unsigned long long off = vsx_text_alloc(len4, text_cursor);
   if (!valid) return;
-  const unsigned long long off = base + (unsigned long long) (incl - len4);
+  if (off + len4 <= text_capacity) vsx_cigar_format(my, nruns, reinterpret_cast<u32 *>(text + off));
+  vsx_soa_store(soa, pid, o, off);
+}
 
-  if (off + len4 <= text_capacity)
-    {
-      u32 * __restrict__ dst = reinterpret_cast<u32 *>(text + off);
-      u32 acc = 0, have = 0;                             // bytes waiting to be stored, lowest byte first
-      auto put = [&](u32 ch) {
-        acc |= ch << (8u * have);
-        if (++have == 4u) { *dst++ = acc; acc = 0; have = 0; }
-      };
-      for (u32 x = nruns; x-- > 0;)
-        {
-          const u32 w = my[x];
-          const u32 n = w >> 2;
-          if (n > 1u)
-            {
-              if (n >= 10000u) put('0' + n / 10000u);
-              if (n >= 1000u) put('0' + (n / 1000u) % 10u);
-              if (n >= 100u) put('0' + (n / 100u) % 10u);
-              if (n >= 10u) put('0' + (n / 10u) % 10u);
-              put('0' + n % 10u);
-            }
-          put((w & 3u) == 0u ? 'M' : (w & 3u) == 1u ? 'I' : 'D');
-        }
-      put(0u);
-      if (have) *dst = acc;                        // padding bytes are zero
-    }
-
-  soa.score[pid] = o.score;
-  soa.aligned[pid] = o.aligned;
-  soa.matches[pid] = o.matches;
-  soa.mismatches[pid] = o.mismatches;
-  soa.gaps[pid] = o.gaps;
-  soa.verdict[pid] = (uint8_t) o.pad;
-  soa.text_off[pid] = off;
+// the formatter on the host (tests): the string of runs[0 .. nruns) into dst if its padded size fits dst_bytes; returns that size
+extern "C" uint32_t vsx_internal_cigar_format(const uint32_t * runs, uint32_t nruns, uint8_t * dst, uint32_t dst_bytes)
+{
+  const uint32_t len4 = (vsx_cigar_len(runs, nruns) + 3u) & ~3u;
+  if (len4 <= dst_bytes) vsx_cigar_format(runs, nruns, reinterpret_cast<uint32_t *>(dst));
+  return len4;
 }
 
 // ---------------------------------------------------------------------------------------------
