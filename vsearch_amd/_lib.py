@@ -64,6 +64,9 @@ ORIENT_SYMBOLS = ["vsx_orient_opts_default", "vsx_orient_result_free", "vsx_orie
 HITOUT_SYMBOLS = ["vsx_hitout_opts_default", "vsx_hits_render", "vsx_hit_text_free", "vsx_hits_render_last_stats",
                   "vsx_internal_hits_render_host"]
 HITOUT_ROWS, HITOUT_SYMBOLS_ROW, HITOUT_SAM, HITOUT_NONE = 1, 2, 4, 0xFFFFFFFFFFFFFFFF      # VSX_HITOUT_ROWS / _SYMBOLS / _SAM / _NONE
+# include/vsx_mask.h
+MASK_SYMBOLS = ["vsx_fastx_mask_opts_default", "vsx_fastx_mask", "vsx_fastx_mask_out_free", "vsx_fastx_mask_last_stats"]
+MASK_WANT_TEXT, MASK_WANT_BITS = 1, 2                                                    # VSX_MASK_WANT_TEXT / _BITS
 ORIENT_MAX_QLEN, ORIENT_CLASSES, ORIENT_CLASS_QLEN = 16384, 3, (512, 4096, 16384)      # VSX_ORIENT_MAX_QLEN, the count kernel's length classes
 
 
@@ -441,6 +444,28 @@ class OrientStats(C.Structure):
                                           "seconds_total")]
 
 
+class MaskOpts(C.Structure):
+    """vsx_fastx_mask_opts (include/vsx_mask.h)"""
+    _fields_ = [("qmask", C.c_int32), ("hardmask", C.c_int32), ("min_unmasked_pct", C.c_double), ("max_unmasked_pct", C.c_double),
+                ("want", C.c_uint32), ("pad", C.c_uint32), ("window", C.c_int64)]
+
+
+class MaskRecord(C.Structure):
+    _fields_ = [("unmasked", C.c_uint32), ("verdict", C.c_uint32)]
+
+
+class MaskOut(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("rec", C.POINTER(MaskRecord)), ("text", C.c_void_p), ("bits", C.c_void_p), ("text_bytes", C.c_uint64),
+                ("kept", C.c_uint64), ("discarded_less", C.c_uint64), ("discarded_more", C.c_uint64)]
+
+
+class MaskStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_mask", "seconds_apply", "seconds_d2h_output",
+                                          "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("sequences", "sequences_short", "sequences_long", "sequences_device_plain", "sequences_host_forced",
+                                          "sequences_host_memory", "sequences_host_long", "windows", "dust_windows", "long_min", "segment")]
+
+
 class Scoring(C.Structure):
     """vsx_scoring: the 14 post-fixup values in search16_init order + n_mismatch."""
     _fields_ = [(n, C.c_int64) for n in (
@@ -686,6 +711,13 @@ def load():
     lib.vsx_hits_render_last_stats.restype = None
     lib.vsx_internal_hits_render_host.argtypes = [C.POINTER(Scoring), C.POINTER(SearchOpts), C.POINTER(HitoutOpts), C.c_uint64, vp, C.c_uint64, vp, vp,
                                                   C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(Hits), C.POINTER(HitText)]
+    lib.vsx_fastx_mask_opts_default.argtypes = [C.POINTER(MaskOpts)]
+    lib.vsx_fastx_mask_opts_default.restype = None
+    lib.vsx_fastx_mask.argtypes = [vp, C.POINTER(MaskOpts), C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(MaskOut)]
+    lib.vsx_fastx_mask_out_free.argtypes = [C.POINTER(MaskOut)]
+    lib.vsx_fastx_mask_out_free.restype = None
+    lib.vsx_fastx_mask_last_stats.argtypes = [C.POINTER(MaskStats)]
+    lib.vsx_fastx_mask_last_stats.restype = None
     _lib = lib
     return lib
 

@@ -91,7 +91,8 @@ int window_best(const char * s, int n, int & first, int & last)
 }
 
 // hard (--hardmask, core/mask.cpp:137-191 with use_hardmask): the text keeps its case and every symbol of a masked interval becomes 'N'
-void dust_one(char * seq, int64_t len, std::vector<char> & orig, bool hard = false)
+// (windows: the caller's count of windows visited, for the statistics of vsx_fastx_mask)
+void dust_one(char * seq, int64_t len, std::vector<char> & orig, bool hard = false, uint64_t * windows = nullptr)
 {
   orig.assign(seq, seq + len);
   if (!hard)
@@ -104,6 +105,7 @@ void dust_one(char * seq, int64_t len, std::vector<char> & orig, bool hard = fal
     {
       const int n = (int) (len > i + kWindow ? kWindow : len - i);
       int a = 0, b = 0;
+      if (windows) ++*windows;
       if (window_best(orig.data() + i, n, a, b) > kLevel)
         {
           if (hard) for (int64_t j = i + a; j <= i + b; ++j) seq[j] = 'N';
@@ -143,3 +145,37 @@ int vsx_dust_mask(char * blob, uint64_t n, const uint64_t * offsets, const uint3
 
 // one sequence, for the dispatch layer's per-query masking (the caller owns the scratch copy)
 void vsx_internal_dust_one(char * seq, int64_t len, std::vector<char> & scratch, bool hard) { dust_one(seq, len, scratch, hard); }
+
+// One sequence of vsx_fastx_mask (include/vsx_mask.h), restated from commands/fastx_mask.cpp:92-146 and core/mask.cpp:139-188, 248-262:
+// the masking of the mode, then the count of the symbols that stay unmasked.  `text` (or null) receives the len masked symbols; the
+// flags of the symbols that do not count are OR-ed into `bits` (or null) from bit `bit0` on, atomically by byte, because the neighbours
+// in a packed bitmap belong to other threads.  Returns the unmasked count.
+uint32_t vsx_internal_fastx_mask_one(const char * in, int64_t len, int qmask, int hard, char * text, uint8_t * bits, uint64_t bit0,
+                                     std::vector<char> & work, std::vector<char> & scratch, uint64_t * windows)
+{
+  work.assign(in, in + len);
+  if (qmask == 2) dust_one(work.data(), len, scratch, hard != 0, windows);
+  else if (qmask == 1 && hard)
+    for (int64_t i = 0; i < len; ++i)
+      if ((unsigned char) work[(size_t) i] & 0x20u) work[(size_t) i] = 'N';            // hardmask(), mask.cpp:248-262
+  uint32_t unmasked = 0;
+  unsigned acc = 0;
+  for (int64_t i = 0; i < len; ++i)
+    {
+      const unsigned char c = (unsigned char) work[(size_t) i];
+      const bool counts = qmask == 0 ? true : hard ? c != 'N' : (c >= 'A' && c <= 'Z');
+      unmasked += counts;
+      if (bits)
+        {
+          const uint64_t bit = bit0 + (uint64_t) i;
+          if (!counts) acc |= 1u << (bit & 7u);
+          if ((bit & 7u) == 7u || i + 1 == len)
+            {
+              if (acc) __atomic_fetch_or(&bits[bit >> 3], (uint8_t) acc, __ATOMIC_RELAXED);
+              acc = 0;
+            }
+        }
+    }
+  if (text && len) std::memcpy(text, work.data(), (size_t) len);
+  return unmasked;
+}

@@ -121,6 +121,10 @@ extern "C" uint32_t vsx_internal_msa_row_tile(void);
 // ---- vsx_mask.cpp ------------------------------------------------------------------------------------------------------------
 // DUST of one sequence, for the dispatch layer's per-query masking (the caller owns the scratch copy; hard: --hardmask)
 void vsx_internal_dust_one(char * seq, int64_t len, std::vector<char> & scratch, bool hard = false);
+// one sequence of vsx_fastx_mask on the host (vsx_fastx_mask.cpp: the host routes and what the device is compared to); qmask 0 none /
+// 1 soft / 2 dust.  text and bits may be null; the bits are OR-ed atomically from bit0 on; *windows counts the DUST windows visited
+uint32_t vsx_internal_fastx_mask_one(const char * in, int64_t len, int qmask, int hard, char * text, uint8_t * bits, uint64_t bit0,
+                                     std::vector<char> & work, std::vector<char> & scratch, uint64_t * windows);
 
 // ---- host helpers ------------------------------------------------------------------------------------------------------------
 #ifndef VSX_DEVICE_RESERVE_BYTES
