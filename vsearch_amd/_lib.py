@@ -66,6 +66,8 @@ HITOUT_SYMBOLS = ["vsx_hitout_opts_default", "vsx_hits_render", "vsx_hit_text_fr
 HITOUT_ROWS, HITOUT_SYMBOLS_ROW, HITOUT_SAM, HITOUT_NONE = 1, 2, 4, 0xFFFFFFFFFFFFFFFF      # VSX_HITOUT_ROWS / _SYMBOLS / _SAM / _NONE
 # include/vsx_mask.h
 MASK_SYMBOLS = ["vsx_fastx_mask_opts_default", "vsx_fastx_mask", "vsx_fastx_mask_out_free", "vsx_fastx_mask_last_stats"]
+# include/vsx_getseqs.h
+GETSEQS_SYMBOLS = ["vsx_getseqs_opts_default", "vsx_getseqs", "vsx_getseqs_out_free", "vsx_getseqs_last_stats"]
 MASK_WANT_TEXT, MASK_WANT_BITS = 1, 2                                                    # VSX_MASK_WANT_TEXT / _BITS
 ORIENT_MAX_QLEN, ORIENT_CLASSES, ORIENT_CLASS_QLEN = 16384, 3, (512, 4096, 16384)      # VSX_ORIENT_MAX_QLEN, the count kernel's length classes
 
@@ -341,6 +343,26 @@ class OtutabStats(C.Structure):
                                           "seconds_output", "seconds_total")] + \
                [(n, C.c_uint64) for n in ("query_groups", "target_groups", "targets_in_adds", "adds_sorted", "labels_device", "labels_host",
                                           "host_no_context", "host_environment", "host_label_count", "host_memory")]
+
+
+class GetseqsOpts(C.Structure):
+    """vsx_getseqs_opts (include/vsx_getseqs.h)"""
+    _fields_ = [("mode", C.c_int32), ("substr", C.c_int32), ("field", C.c_void_p), ("field_len", C.c_uint64), ("subseq_start", C.c_int64),
+                ("subseq_end", C.c_int64), ("window", C.c_int64), ("threads", C.c_int32), ("pad", C.c_int32)]
+
+
+class GetseqsOut(C.Structure):
+    """vsx_getseqs_out (include/vsx_getseqs.h); rec: n records of four uint32 (matched, ordinal, start, length)"""
+    _fields_ = [("n", C.c_uint64), ("rec", C.c_void_p), ("kept", C.c_uint64), ("discarded", C.c_uint64)]
+
+
+class GetseqsStats(C.Structure):
+    """vsx_getseqs_stats (include/vsx_getseqs.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_table", "seconds_match", "seconds_ordinals", "seconds_output",
+                                          "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("headers_device", "headers_host", "host_no_context", "host_environment", "host_count", "host_memory",
+                                          "host_needle_length", "host_header_length", "host_lengths", "labels_in_table", "distinct_lengths",
+                                          "table_slots", "probes", "verifications")]
 
 
 class HitoutOpts(C.Structure):
@@ -718,6 +740,13 @@ def load():
     lib.vsx_fastx_mask_out_free.restype = None
     lib.vsx_fastx_mask_last_stats.argtypes = [C.POINTER(MaskStats)]
     lib.vsx_fastx_mask_last_stats.restype = None
+    lib.vsx_getseqs_opts_default.argtypes = [C.POINTER(GetseqsOpts)]
+    lib.vsx_getseqs_opts_default.restype = None
+    lib.vsx_getseqs.argtypes = [vp, C.POINTER(GetseqsOpts), C.POINTER(Labels), vp, C.POINTER(Labels), C.POINTER(GetseqsOut)]
+    lib.vsx_getseqs_out_free.argtypes = [C.POINTER(GetseqsOut)]
+    lib.vsx_getseqs_out_free.restype = None
+    lib.vsx_getseqs_last_stats.argtypes = [C.POINTER(GetseqsStats)]
+    lib.vsx_getseqs_last_stats.restype = None
     _lib = lib
     return lib
 
