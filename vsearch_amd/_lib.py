@@ -68,6 +68,10 @@ HITOUT_ROWS, HITOUT_SYMBOLS_ROW, HITOUT_SAM, HITOUT_NONE = 1, 2, 4, 0xFFFFFFFFFF
 MASK_SYMBOLS = ["vsx_fastx_mask_opts_default", "vsx_fastx_mask", "vsx_fastx_mask_out_free", "vsx_fastx_mask_last_stats"]
 # include/vsx_getseqs.h
 GETSEQS_SYMBOLS = ["vsx_getseqs_opts_default", "vsx_getseqs", "vsx_getseqs_out_free", "vsx_getseqs_last_stats"]
+# include/vsx_cut.h
+CUT_SYMBOLS = ["vsx_cut_opts_default", "vsx_cut_pattern_check", "vsx_cut", "vsx_cut_out_free", "vsx_cut_last_stats"]
+CUT_WANT_FWD, CUT_WANT_REV, CUT_WANT_REV_TEXT, CUT_WANT_DISCARDED_REV_TEXT = 1, 2, 4, 8
+CUT_DEVICE_MAX_PATTERN = 64
 MASK_WANT_TEXT, MASK_WANT_BITS = 1, 2                                                    # VSX_MASK_WANT_TEXT / _BITS
 ORIENT_MAX_QLEN, ORIENT_CLASSES, ORIENT_CLASS_QLEN = 16384, 3, (512, 4096, 16384)      # VSX_ORIENT_MAX_QLEN, the count kernel's length classes
 
@@ -363,6 +367,26 @@ class GetseqsStats(C.Structure):
                [(n, C.c_uint64) for n in ("headers_device", "headers_host", "host_no_context", "host_environment", "host_count", "host_memory",
                                           "host_needle_length", "host_header_length", "host_lengths", "labels_in_table", "distinct_lengths",
                                           "table_slots", "probes", "verifications")]
+
+
+class CutOpts(C.Structure):
+    """vsx_cut_opts (include/vsx_cut.h)"""
+    _fields_ = [("pattern", C.c_char_p), ("pattern_len", C.c_uint64), ("want", C.c_uint32), ("threads", C.c_int32), ("window", C.c_int64)]
+
+
+class CutOut(C.Structure):
+    """vsx_cut_out (include/vsx_cut.h); fwd / rev: records of (uint64 seq, uint32 start, uint32 length)"""
+    _fields_ = [("n", C.c_uint64), ("matches", C.c_void_p), ("n_fwd", C.c_uint64), ("fwd", C.c_void_p), ("n_rev", C.c_uint64), ("rev", C.c_void_p),
+                ("n_uncut", C.c_uint64), ("uncut", C.c_void_p), ("text", C.c_void_p), ("text_bytes", C.c_uint64), ("rev_off", C.c_void_p),
+                ("discarded_off", C.c_void_p), ("cut", C.c_uint64), ("uncut_total", C.c_uint64), ("total_matches", C.c_uint64)]
+
+
+class CutStats(C.Structure):
+    """vsx_cut_stats (include/vsx_cut.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_match", "seconds_rank", "seconds_fragments", "seconds_emit",
+                                          "seconds_output", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("sequences", "symbols", "blocks", "items", "tile", "pattern_length", "host_no_context",
+                                          "host_environment", "host_count", "host_memory", "host_pattern_length")]
 
 
 class HitoutOpts(C.Structure):
@@ -747,6 +771,14 @@ def load():
     lib.vsx_getseqs_out_free.restype = None
     lib.vsx_getseqs_last_stats.argtypes = [C.POINTER(GetseqsStats)]
     lib.vsx_getseqs_last_stats.restype = None
+    lib.vsx_cut_opts_default.argtypes = [C.POINTER(CutOpts)]
+    lib.vsx_cut_opts_default.restype = None
+    lib.vsx_cut_pattern_check.argtypes = [C.c_char_p, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.vsx_cut.argtypes = [vp, C.POINTER(CutOpts), C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(CutOut)]
+    lib.vsx_cut_out_free.argtypes = [C.POINTER(CutOut)]
+    lib.vsx_cut_out_free.restype = None
+    lib.vsx_cut_last_stats.argtypes = [C.POINTER(CutStats)]
+    lib.vsx_cut_last_stats.restype = None
     _lib = lib
     return lib
 
