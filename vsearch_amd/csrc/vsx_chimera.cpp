@@ -999,8 +999,7 @@ int vsx_uchime_ref(vsx_searcher * S, const vsx_chimera_opts * O, uint64_t n, con
   if (O->mindiffs < 0 || !(O->xn > 0.0) || !(O->dn >= 0.0)) return fail(VSX_EINVAL, "vsx_uchime_ref: xn must be > 0, dn >= 0, mindiffs >= 0");
   for (uint64_t k = 0; k < n; ++k)
     if (qoff[k] + qlen[k] > qbytes) return fail(VSX_EINVAL, "vsx_uchime_ref: query exceeds the blob");
-  const char * env = std::getenv("VSX_CHIMERA");
-  const bool host_all = env && std::strcmp(env, "host") == 0;
+  const bool host_all = vsxp::env_is_host("VSX_CHIMERA");
   const uint64_t window = O->window > 0 ? (uint64_t) O->window : 16384;
   CallBufs bufs;
   for (uint64_t w0 = 0; w0 < n; w0 += window)
@@ -1054,8 +1053,7 @@ int vsx_uchime_denovo(vsx_searcher * S, const vsx_chimera_denovo_opts * O, vsx_c
   int rc = vsx_internal_denovo_create(S, &D);
   if (rc != VSX_OK) return rc;
   struct DGuard { VsxDenovo * d; ~DGuard() { vsx_internal_denovo_destroy(d); } } dg {D};
-  const char * env = std::getenv("VSX_CHIMERA");
-  const bool host_all = env && std::strcmp(env, "host") == 0;
+  const bool host_all = vsxp::env_is_host("VSX_CHIMERA");
   const uint64_t window = O->base.window > 0 ? (uint64_t) O->base.window : 4096;
   CallBufs bufs;
   UchimeMode mode {VsxChimParams {O->base.minh, O->base.mindiv, O->base.xn, O->base.dn, O->base.mindiffs, O->variant}, bufs, host_all};
@@ -1120,8 +1118,7 @@ int vsx_chimeras_denovo(vsx_searcher * S, const vsx_chimeras_long_opts * O, vsx_
   rc = vsx_internal_denovo_create(S, &D);
   if (rc != VSX_OK) return rc;
   struct DGuard { VsxDenovo * d; ~DGuard() { vsx_internal_denovo_destroy(d); } } dg {D};
-  const char * env = std::getenv("VSX_CHIMERA");
-  const bool host_all = env && std::strcmp(env, "host") == 0;
+  const bool host_all = vsxp::env_is_host("VSX_CHIMERA");
   const uint64_t window = O->window > 0 ? (uint64_t) O->window : 4096;
   CallBufs bufs;
   LongMode mode {VsxChimLongParams {O->parents_max, O->length_min, O->diff_pct, 0, 0}, O->parts, (uint32_t) so.maxaccepts, bufs, host_all};

@@ -23,8 +23,11 @@
 #include "vsx_cut_internal.h"
 #include "vsx_private.h"
 
+using vsxp::env_u64;
 using vsxp::fail;
+using vsxp::host_array;
 using vsxp::now_s;
+using vsxp::Scratch;
 
 static_assert(sizeof(VsxCutRec) == sizeof(vsx_cut_fragment) && sizeof(vsx_cut_fragment) == 16, "the device writes vsx_cut_fragment records");
 static_assert(VSX_CUT_MAX_P == VSX_CUT_DEVICE_MAX_PATTERN, "one pattern limit");
@@ -75,9 +78,6 @@ void release(vsx_cut_out * out)
   std::free(out->text); std::free(out->rev_off); std::free(out->discarded_off);
   std::memset(out, 0, sizeof *out);
 }
-
-template <typename T>
-T * host_array(uint64_t count) { return static_cast<T *>(std::malloc(std::max<uint64_t>(count, 1) * sizeof(T))); }
 
 // the arrays of the result, once the list lengths are known
 int allocate(const Plan & P, vsx_cut_out & out, uint64_t n_fwd, uint64_t n_rev, uint64_t n_uncut)
@@ -194,32 +194,6 @@ int host_route(const Plan & P, vsx_cut_out & out)
 }
 
 // ---- the device route -----------------------------------------------------------------------------------------------------------
-template <typename T>
-struct Scratch {
-  vsx_ctx * ctx = nullptr;
-  T * p = nullptr;
-  size_t got = 0;
-  Scratch() = default;
-  Scratch(const Scratch &) = delete;
-  Scratch & operator=(const Scratch &) = delete;
-  ~Scratch() { if (p) vsx_internal_scratch_put(ctx, p, got); }
-  hipError_t alloc(vsx_ctx * c, size_t count)
-  {
-    if (p) { vsx_internal_scratch_put(ctx, p, got); p = nullptr; }
-    ctx = c;
-    void * q = nullptr;
-    const hipError_t e = vsx_internal_scratch_get(c, std::max<size_t>(count, 1) * sizeof(T), &q, &got);
-    if (e == hipSuccess) p = static_cast<T *>(q);
-    return e;
-  }
-  hipError_t upload(vsx_ctx * c, const T * h, size_t count, hipStream_t st)
-  {
-    const hipError_t e = alloc(c, count);
-    if (e != hipSuccess || count == 0) return e;
-    return hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, st);
-  }
-};
-
 struct DeviceBufs {
   Scratch<uint8_t> text, otext;
   Scratch<uint64_t> off;
@@ -230,23 +204,16 @@ struct DeviceBufs {
   std::vector<std::unique_ptr<Scratch<uint8_t>>> temps;       // rocPRIM's temporary storage, kept until the call's last kernel is through
 };
 
-int scan32(vsx_ctx * ctx, DeviceBufs & B, const uint32_t * in, uint32_t * out, uint64_t count, hipStream_t st)
+// an exclusive scan by vsx_launch_cut_scan32 or vsx_launch_cut_scan64: the first call sizes the temporary storage, the second runs
+template <typename T>
+int scan(hipError_t (*launch)(void *, size_t *, const T *, T *, uint64_t, hipStream_t), vsx_ctx * ctx, DeviceBufs & B, const T * in, T * out,
+         uint64_t count, hipStream_t st)
 {
   size_t bytes = 0;
-  VSX_HIP_AS(WHO, vsx_launch_cut_scan32(nullptr, &bytes, in, out, count, st));
+  VSX_HIP_AS(WHO, launch(nullptr, &bytes, in, out, count, st));
   B.temps.emplace_back(new Scratch<uint8_t>());
   VSX_HIP_AS(WHO, B.temps.back()->alloc(ctx, bytes));
-  VSX_HIP_AS(WHO, vsx_launch_cut_scan32(B.temps.back()->p, &bytes, in, out, count, st));
-  return VSX_OK;
-}
-
-int scan64(vsx_ctx * ctx, DeviceBufs & B, const uint64_t * in, uint64_t * out, uint64_t count, hipStream_t st)
-{
-  size_t bytes = 0;
-  VSX_HIP_AS(WHO, vsx_launch_cut_scan64(nullptr, &bytes, in, out, count, st));
-  B.temps.emplace_back(new Scratch<uint8_t>());
-  VSX_HIP_AS(WHO, B.temps.back()->alloc(ctx, bytes));
-  VSX_HIP_AS(WHO, vsx_launch_cut_scan64(B.temps.back()->p, &bytes, in, out, count, st));
+  VSX_HIP_AS(WHO, launch(B.temps.back()->p, &bytes, in, out, count, st));
   return VSX_OK;
 }
 
@@ -270,6 +237,8 @@ uint64_t device_bytes_lists(uint64_t matches, uint64_t n_fwd, uint64_t n_rev, ui
   return 8 * matches + 16 * n_fwd + 32 * (n_rev + n_uncut + 1) + 4 * n_uncut + text + ((uint64_t) 16 << 20);
 }
 
+// the check between the stages (the device is set; no testing aid): a device that does not report its memory sends the call to the
+// host route here, where vsxp::device_fits at the start of the call fails it
 bool fits(uint64_t need)
 {
   size_t free_b = 0, total_b = 0;
@@ -338,7 +307,7 @@ int device_run(vsx_ctx * ctx, hipStream_t st, const Plan & P, uint64_t blocks, D
 
   // ---- ranks and positions
   t0 = now_s();
-  int rc = scan32(ctx, B, B.count.p, B.rank.p, (uint64_t) nb + 1, st);
+  int rc = scan(vsx_launch_cut_scan32, ctx, B, B.count.p, B.rank.p, (uint64_t) nb + 1, st);
   if (rc != VSX_OK) return rc;
   uint32_t n_matches = 0;
   VSX_HIP_AS(WHO, hipMemcpyAsync(&n_matches, B.rank.p + nb, sizeof n_matches, hipMemcpyDeviceToHost, st));
@@ -355,9 +324,9 @@ int device_run(vsx_ctx * ctx, hipStream_t st, const Plan & P, uint64_t blocks, D
   for (Scratch<uint32_t> * a : { &B.matches, &B.nfwd, &B.nrev, &B.uncut, &B.basef, &B.baser, &B.baseu }) VSX_HIP_AS(WHO, a->alloc(ctx, (size_t) n + 1));
   for (Scratch<uint32_t> * a : { &B.nfwd, &B.nrev, &B.uncut }) VSX_HIP_AS(WHO, hipMemsetAsync(a->p + n, 0, sizeof(uint32_t), st));
   VSX_HIP_AS(WHO, vsx_launch_cut_seqinfo(n, B.len.p, B.bstart.p, B.rank.p, B.pos.p, pat, B.matches.p, B.nfwd.p, B.nrev.p, B.uncut.p, st));
-  if ((rc = scan32(ctx, B, B.nfwd.p, B.basef.p, (uint64_t) n + 1, st)) != VSX_OK) return rc;
-  if ((rc = scan32(ctx, B, B.nrev.p, B.baser.p, (uint64_t) n + 1, st)) != VSX_OK) return rc;
-  if ((rc = scan32(ctx, B, B.uncut.p, B.baseu.p, (uint64_t) n + 1, st)) != VSX_OK) return rc;
+  if ((rc = scan(vsx_launch_cut_scan32, ctx, B, B.nfwd.p, B.basef.p, (uint64_t) n + 1, st)) != VSX_OK) return rc;
+  if ((rc = scan(vsx_launch_cut_scan32, ctx, B, B.nrev.p, B.baser.p, (uint64_t) n + 1, st)) != VSX_OK) return rc;
+  if ((rc = scan(vsx_launch_cut_scan32, ctx, B, B.uncut.p, B.baseu.p, (uint64_t) n + 1, st)) != VSX_OK) return rc;
   uint32_t totals[3] = { 0, 0, 0 };
   VSX_HIP_AS(WHO, hipMemcpyAsync(&totals[0], B.basef.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   VSX_HIP_AS(WHO, hipMemcpyAsync(&totals[1], B.baser.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -389,7 +358,7 @@ int device_run(vsx_ctx * ctx, hipStream_t st, const Plan & P, uint64_t blocks, D
   if (text)
     {
       VSX_HIP_AS(WHO, hipMemsetAsync(B.plen.p + n_pieces, 0, sizeof(uint64_t), st));
-      if ((rc = scan64(ctx, B, reinterpret_cast<const uint64_t *>(B.plen.p), reinterpret_cast<uint64_t *>(B.poffs.p), n_pieces + 1, st)) != VSX_OK) return rc;
+      if ((rc = scan(vsx_launch_cut_scan64, ctx, B, reinterpret_cast<const uint64_t *>(B.plen.p), reinterpret_cast<uint64_t *>(B.poffs.p), n_pieces + 1, st)) != VSX_OK) return rc;
       poffs.resize(n_pieces + 1);
       VSX_HIP_AS(WHO, hipMemcpyAsync(poffs.data(), B.poffs.p, (n_pieces + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
       VSX_HIP_AS(WHO, hipStreamSynchronize(st));
@@ -434,12 +403,6 @@ int device_route(vsx_ctx * ctx, const Plan & P, uint64_t blocks, vsx_cut_out & o
   return rc;
 }
 
-uint64_t env_u64(const char * name, uint64_t otherwise)
-{
-  const char * e = std::getenv(name);
-  return (e && *e) ? std::strtoull(e, nullptr, 10) : otherwise;
-}
-
 int run(vsx_ctx * ctx, const vsx_cut_opts * o, uint64_t n, const char * blob, uint64_t blob_bytes, const uint64_t * offsets, const uint32_t * lengths,
         vsx_cut_out * out)
 {
@@ -482,19 +445,20 @@ int run(vsx_ctx * ctx, const vsx_cut_opts * o, uint64_t n, const char * blob, ui
 
   // ---- the route
   bool host = true;
-  const char * env = std::getenv("VSX_CUT");
   const uint64_t count_limit = std::min<uint64_t>(COUNT_LIMIT, env_u64("VSX_CUT_DEVICE_COUNT", COUNT_LIMIT));
   if (!ctx) g_stats.host_no_context = 1;
-  else if (env && std::strcmp(env, "host") == 0) g_stats.host_environment = 1;
+  else if (vsxp::env_is_host("VSX_CUT")) g_stats.host_environment = 1;
   else if (n > count_limit || symbols + n > count_limit) g_stats.host_count = 1;      // every list holds at most matches + sequences records
   else if (plen > VSX_CUT_DEVICE_MAX_PATTERN) g_stats.host_pattern_length = 1;
   else host = false;
   int rc = VSX_OK;
   if (!host && n)
     {
-      if (hipSetDevice(vsx_internal_device(ctx)) != hipSuccess) { release(out); return fail(VSX_EHIP, "%s: the device does not answer", WHO); }
+      // (the testing aid is read here, not by device_fits: in this command an empty value counts as unset)
       const uint64_t need = env_u64("VSX_CUT_PRETEND_BYTES", device_bytes(P, blocks));
-      if (!fits(need)) { host = true; g_stats.host_memory = 1; }
+      bool fit = false;
+      if ((rc = vsxp::device_fits(ctx, WHO, need, nullptr, &fit)) != VSX_OK) { release(out); return rc; }
+      if (!fit) { host = true; g_stats.host_memory = 1; }
     }
   if (!host && n)
     {

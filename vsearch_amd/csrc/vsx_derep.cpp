@@ -28,8 +28,10 @@
 
 #pragma clang fp contract(off)
 
+using vsxp::array_of;
 using vsxp::fail;
 using vsxp::now_s;
+using vsxp::upload;
 using vsxp::DevBuf;
 using vsxp::PinnedBuf;
 using vsxp::ensure_pinned;
@@ -206,14 +208,6 @@ uint64_t device_bytes(uint64_t K, uint64_t W, uint64_t T, uint64_t qual_bytes)
   return W * 8 + K * 160 + T * 4 + 3 * qual_bytes + ((uint64_t) 64 << 20);
 }
 
-template <typename T>
-int upload(DevBuf<T> & d, const T * h, uint64_t count, hipStream_t st)
-{
-  VSX_HIP_AS(WHO, d.alloc(count));
-  if (count) VSX_HIP_AS(WHO, hipMemcpyAsync(d.p, h, count * sizeof(T), hipMemcpyHostToDevice, st));
-  return VSX_OK;
-}
-
 int device_groups(vsx_ctx * ctx, const Input & in, uint64_t W, Groups & G)
 {
   const vsx_derep_opts & o = *in.o;
@@ -294,12 +288,11 @@ int device_groups(vsx_ctx * ctx, const Input & in, uint64_t W, Groups & G)
   DevBuf<uint64_t> d_woff_p, d_woff_m, d_ab, d_khash, d_kwoff, d_size, d_keys_a, d_keys_b;
   DevBuf<uint8_t> d_flag, d_temp;
   DevBuf<VsxDerepCounters> d_counters;
-  int rc;
-  if ((rc = upload(d_len, len.data(), K, st)) != VSX_OK) return rc;
-  if ((rc = upload(d_woff_p, woff_p.data(), K, st)) != VSX_OK) return rc;
-  if (both && (rc = upload(d_woff_m, woff_m.data(), K, st)) != VSX_OK) return rc;
-  if (!ab.empty() && (rc = upload(d_ab, ab.data(), K, st)) != VSX_OK) return rc;
-  if (o.by_label && (rc = upload(d_label, label.data(), K, st)) != VSX_OK) return rc;
+  VSX_HIP_AS(WHO, upload(d_len, len.data(), K, st));
+  VSX_HIP_AS(WHO, upload(d_woff_p, woff_p.data(), K, st));
+  if (both) VSX_HIP_AS(WHO, upload(d_woff_m, woff_m.data(), K, st));
+  if (!ab.empty()) VSX_HIP_AS(WHO, upload(d_ab, ab.data(), K, st));
+  if (o.by_label) VSX_HIP_AS(WHO, upload(d_label, label.data(), K, st));
   const uint64_t table_size = vsxe::table_size_for(K);
   VSX_HIP_AS(WHO, d_table.alloc(table_size));
   VSX_HIP_AS(WHO, d_root.alloc(K)); VSX_HIP_AS(WHO, d_rep.alloc(K)); VSX_HIP_AS(WHO, d_count.alloc(K)); VSX_HIP_AS(WHO, d_size.alloc(K));
@@ -395,11 +388,11 @@ int device_groups(vsx_ctx * ctx, const Input & in, uint64_t W, Groups & G)
       DevBuf<uint8_t> d_qual, d_out;
       DevBuf<uint64_t> d_qoff;
       DevBuf<VsxDerepQTask> d_tasks;
-      if ((rc = upload(d_prob, prob, 128, st)) != VSX_OK) return rc;
-      if ((rc = upload(d_thr, thr, VSX_DEREP_THRESHOLDS, st)) != VSX_OK) return rc;
-      if ((rc = upload(d_qual, reinterpret_cast<const uint8_t *>(in.reads->qual), in.reads->bytes, st)) != VSX_OK) return rc;
-      if ((rc = upload(d_qoff, qoff.data(), K, st)) != VSX_OK) return rc;
-      if ((rc = upload(d_tasks, tasks.data(), tasks.size(), st)) != VSX_OK) return rc;
+      VSX_HIP_AS(WHO, upload(d_prob, prob, 128, st));
+      VSX_HIP_AS(WHO, upload(d_thr, thr, VSX_DEREP_THRESHOLDS, st));
+      VSX_HIP_AS(WHO, upload(d_qual, reinterpret_cast<const uint8_t *>(in.reads->qual), in.reads->bytes, st));
+      VSX_HIP_AS(WHO, upload(d_qoff, qoff.data(), K, st));
+      VSX_HIP_AS(WHO, upload(d_tasks, tasks.data(), tasks.size(), st));
       VSX_HIP_AS(WHO, d_out.alloc(merged_bytes));
       VsxDerepQParams QP {};
       QP.prob = d_prob.p; QP.threshold = reinterpret_cast<const uint64_t *>(d_thr.p);
@@ -430,8 +423,6 @@ void release(vsx_derep_out * out)
   std::memset(out, 0, sizeof *out);
 }
 
-template <typename T>
-T * array_of(uint64_t n) { return static_cast<T *>(std::calloc(std::max<uint64_t>(n, 1), sizeof(T))); }
 
 int finish(const Input & in, const Groups & G, vsx_derep_out & out)
 {
@@ -557,18 +548,16 @@ int vsx_derep(vsx_ctx * ctx, const vsx_derep_opts * opts, uint64_t n, const vsx_
   if (o.strand_both) W *= 2;
 
   // ---- the route
-  const char * env = std::getenv("VSX_DEREP");
-  bool host_all = (env && std::strcmp(env, "host") == 0) || !ctx || K > (uint64_t) UINT32_MAX - 1;
-  if (!host_all && K)
-    {
-      size_t free_b = 0, total_b = 0;
-      if (hipSetDevice(vsx_internal_device(ctx)) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess)
-        return fail(VSX_EHIP, "%s: the device does not answer", WHO);
-      const uint64_t need = device_bytes(K, W, vsxe::table_size_for(K), o.want_quality ? reads->bytes : 0);
-      if (need + VSX_DEVICE_RESERVE_BYTES > free_b) host_all = true;       // buffers that do not fit: the host, as a whole
-    }
+  bool host_all = vsxp::env_is_host("VSX_DEREP") || !ctx || K > (uint64_t) UINT32_MAX - 1;
   Groups G;
   int rc = VSX_OK;
+  if (!host_all && K)
+    {
+      bool fits = false;
+      rc = vsxp::device_fits(ctx, WHO, device_bytes(K, W, vsxe::table_size_for(K), o.want_quality ? reads->bytes : 0), nullptr, &fits);
+      if (rc != VSX_OK) return rc;
+      if (!fits) host_all = true;       // buffers that do not fit: the host, as a whole
+    }
   if (host_all || K == 0) host_groups(in, G);
   else rc = device_groups(ctx, in, W, G);
   if (rc == VSX_OK)

@@ -27,8 +27,10 @@
 #include "vsx_derep_prefix_internal.h"
 #include "vsx_private.h"
 
+using vsxp::array_of;
 using vsxp::fail;
 using vsxp::now_s;
+using vsxp::upload;
 using vsxp::DevBuf;
 using vsxp::PinnedBuf;
 using vsxp::ensure_pinned;
@@ -251,14 +253,6 @@ uint64_t device_bytes(uint64_t K, uint64_t W, uint64_t T, uint64_t D)
   return W * 16 + K * 128 + T * 4 + D * 4 + ((uint64_t) 64 << 20);
 }
 
-template <typename T>
-int upload(DevBuf<T> & d, const T * h, uint64_t count, hipStream_t st)
-{
-  VSX_HIP_AS(WHO, d.alloc(count));
-  if (count) VSX_HIP_AS(WHO, hipMemcpyAsync(d.p, h, count * sizeof(T), hipMemcpyHostToDevice, st));
-  return VSX_OK;
-}
-
 int device_groups(vsx_ctx * ctx, const Input & in, uint64_t W, Groups & G)
 {
   const vsx_derep_prefix_opts & o = *in.o;
@@ -335,11 +329,11 @@ int device_groups(vsx_ctx * ctx, const Input & in, uint64_t W, Groups & G)
   DevBuf<VsxDerepCounters> d_gcounters;
   DevBuf<VsxDerepPrefixCounters> d_counters;
   int rc;
-  if ((rc = upload(d_len, len.data(), K, st)) != VSX_OK) return rc;
-  if ((rc = upload(d_lidx, length_index.data(), K, st)) != VSX_OK) return rc;
-  if ((rc = upload(d_lengths, in.lengths.data(), D, st)) != VSX_OK) return rc;
-  if ((rc = upload(d_woff, woff.data(), K, st)) != VSX_OK) return rc;
-  if (!ab.empty() && (rc = upload(d_ab, ab.data(), K, st)) != VSX_OK) return rc;
+  VSX_HIP_AS(WHO, upload(d_len, len.data(), K, st));
+  VSX_HIP_AS(WHO, upload(d_lidx, length_index.data(), K, st));
+  VSX_HIP_AS(WHO, upload(d_lengths, in.lengths.data(), D, st));
+  VSX_HIP_AS(WHO, upload(d_woff, woff.data(), K, st));
+  if (!ab.empty()) VSX_HIP_AS(WHO, upload(d_ab, ab.data(), K, st));
   const uint64_t table_size = vsxe::table_size_for(K);
   VSX_HIP_AS(WHO, d_table.alloc(table_size));
   VSX_HIP_AS(WHO, d_root.alloc(K)); VSX_HIP_AS(WHO, d_rep.alloc(K)); VSX_HIP_AS(WHO, d_count.alloc(K)); VSX_HIP_AS(WHO, d_size.alloc(K));
@@ -445,8 +439,6 @@ void release(vsx_derep_prefix_out * out)
   std::memset(out, 0, sizeof *out);
 }
 
-template <typename T>
-T * array_of(uint64_t n) { return static_cast<T *>(std::calloc(std::max<uint64_t>(n, 1), sizeof(T))); }
 
 int finish(const Input & in, const Groups & G, vsx_derep_prefix_out & out)
 {
@@ -549,27 +541,22 @@ int vsx_derep_prefix(vsx_ctx * ctx, const vsx_derep_prefix_opts * opts, uint64_t
   g_stats.distinct_lengths = in.lengths.size();
 
   // ---- the route
-  const char * env = std::getenv("VSX_DEREP_PREFIX");
-  const char * limit = std::getenv("VSX_DEREP_PREFIX_DEVICE_READS");                      // testing aid: a lower limit of the device route
-  uint64_t device_reads = (uint64_t) UINT32_MAX - 1;
-  if (limit) device_reads = std::min<uint64_t>(device_reads, std::strtoull(limit, nullptr, 10));
+  const uint64_t most_reads = (uint64_t) UINT32_MAX - 1;                                  // testing aid: a lower limit of the device route
+  const uint64_t device_reads = std::min(most_reads, vsxp::env_u64("VSX_DEREP_PREFIX_DEVICE_READS", most_reads, true));
   bool host_all = true;
   if (!ctx) g_stats.host_no_context = 1;
-  else if (env && std::strcmp(env, "host") == 0) g_stats.host_environment = 1;
+  else if (vsxp::env_is_host("VSX_DEREP_PREFIX")) g_stats.host_environment = 1;
   else if (K > device_reads) g_stats.host_read_count = 1;
   else host_all = false;
-  if (!host_all && K)
-    {
-      size_t free_b = 0, total_b = 0;
-      if (hipSetDevice(vsx_internal_device(ctx)) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess)
-        return fail(VSX_EHIP, "%s: the device does not answer", WHO);
-      uint64_t need = device_bytes(K, W, vsxe::table_size_for(K), in.lengths.size());
-      const char * pretend = std::getenv("VSX_DEREP_PREFIX_PRETEND_BYTES");                // testing aid: what the words are taken to need
-      if (pretend) need = std::strtoull(pretend, nullptr, 10);
-      if (need + VSX_DEVICE_RESERVE_BYTES > free_b) { host_all = true; g_stats.host_memory = 1; }      // the host, as a whole
-    }
   Groups G;
   int rc = VSX_OK;
+  if (!host_all && K)
+    {
+      bool fits = false;                                                                  // (the testing aid: what the words are taken to need)
+      rc = vsxp::device_fits(ctx, WHO, device_bytes(K, W, vsxe::table_size_for(K), in.lengths.size()), "VSX_DEREP_PREFIX_PRETEND_BYTES", &fits);
+      if (rc != VSX_OK) return rc;
+      if (!fits) { host_all = true; g_stats.host_memory = 1; }      // the host, as a whole
+    }
   if (host_all || K == 0) host_groups(in, G);
   else rc = device_groups(ctx, in, W, G);
   if (rc == VSX_OK)

@@ -8,8 +8,8 @@
 //   windows  a window is a run of consecutive reads whose quality bytes span at most the staging capacity, copied into pinned
 //            memory with one memcpy; the kernels follow the caller's offsets, rebased to the span.  Two slots, one stream each:
 //            window k + 1 is staged and walked while window k's ordered sum runs.  The sum of window k + 1 waits for the sum of
-//            window k through an event, so every chain sees the reads in input order.  (The filter's planner is written around
-//            its two sides and its sequence blob, so this file has its own, for one quality blob.)
+//            window k through an event, so every chain sees the reads in input order.  Planner, slot base and driver are
+//            those of vsx_window.h; the slot, submit_window and collect_window below are this command's.
 //   host     accumulate_host below is written from the specification, not from the kernels: the fallback (VSX_EESTATS=host, a
 //            histogram beyond the budget, more than UINT32_MAX reads) and what the tests without a device call.
 #include <hip/hip_runtime.h>
@@ -22,12 +22,14 @@
 #include <vector>
 
 #include "vsx_eestats_internal.h"
-#include "vsx_private.h"
+#include "vsx_window.h"
 
 #pragma clang fp contract(off)
 
+using vsxp::align64;
 using vsxp::fail;
 using vsxp::now_s;
+using vsxp::zeroed;
 using vsxp::DevBuf;
 using vsxp::PinnedBuf;
 
@@ -158,42 +160,17 @@ int accumulate_host(const vsx_fastq_eestats_opts & o, const Input & in, const Le
   return VSX_OK;
 }
 
-// ---- the window pipeline ----------------------------------------------------------------------------------------------------
-uint64_t align64(uint64_t v) { return (v + 63) & ~(uint64_t) 63; }
+// ---- the window pipeline (vsx_window.h) ---------------------------------------------------------------------------------------
+enum { EV_IN, EV_RUN, EV_WALKED, EV_SUM, EV_DONE, EVENTS };
 
-struct Slot {
-  hipStream_t st = nullptr;
-  hipEvent_t ev_in = nullptr, ev_run = nullptr, ev_walked = nullptr, ev_sum = nullptr, ev_done = nullptr;
+struct Slot : vsxp::Slot<EVENTS> {
   PinnedBuf<uint8_t> h_in;              // items + quality span
   PinnedBuf<uint32_t> h_err;
   DevBuf<uint8_t> d_in;
   DevBuf<uint32_t> d_err;
   DevBuf<double> d_matrix;
-  uint64_t w0 = 0, n = 0;               // the window in flight
-  bool busy = false, summed = false;
-  ~Slot()
-  {
-    if (st) (void) hipStreamSynchronize(st);
-    for (hipEvent_t e : { ev_in, ev_run, ev_walked, ev_sum, ev_done }) if (e) (void) hipEventDestroy(e);
-    if (st) (void) hipStreamDestroy(st);
-  }
+  bool summed = false;
 };
-
-struct Span { uint64_t lo = 0, hi = 0; };
-
-// extend the window at w0 greedily: up to `window` reads whose quality bytes span at most the capacity; a single read always fits
-uint64_t plan_window(const Input & in, uint64_t w0, uint64_t window, Span & span)
-{
-  uint64_t n = 0;
-  for (uint64_t k = w0; k < in.n && n < window; ++k, ++n)
-    {
-      const uint64_t lo = in.off[k], hi = lo + in.len[k];
-      const Span next { n ? std::min(span.lo, lo) : lo, n ? std::max(span.hi, hi) : hi };
-      if (n && next.hi - next.lo > SPAN_CAPACITY) break;
-      span = next;
-    }
-  return n;
-}
 
 struct Device {
   VsxEestatsParams P {};
@@ -204,18 +181,16 @@ struct Device {
 
 // stage window [w0, w0 + n) into the slot and enqueue copy-in, the walk, the ordered sum (behind the previous window's) and the
 // copy-out of the per-read error positions on its stream
-int submit_window(Slot & s, const Slot & previous, const Input & in, const Device & D, uint64_t w0, uint64_t n, const Span & span,
+int submit_window(Slot & s, const Slot & previous, const Input & in, const Device & D, uint64_t w0, const vsxp::Window & W,
                   uint64_t reserve_in)
 {
   const double t0 = now_s();
+  const uint64_t n = W.n;
+  const vsxp::Span span = W.span[0];
   const uint64_t items_bytes = align64(n * sizeof(VsxEestatsItem));
   const uint64_t in_bytes = items_bytes + align64(span.hi - span.lo + 64);
-  if (!s.d_in.p || in_bytes > s.d_in.n)
-    {
-      s.h_in.release(); s.d_in.release();
-      VSX_HIP_AS(WHO, s.h_in.alloc(std::max(in_bytes, reserve_in)));
-      VSX_HIP_AS(WHO, s.d_in.alloc(std::max(in_bytes, reserve_in)));
-    }
+  const int rc = vsxp::grow_pair(WHO, s.h_in, s.d_in, in_bytes, std::max(in_bytes, reserve_in));
+  if (rc != VSX_OK) return rc;
   VsxEestatsItem * items = reinterpret_cast<VsxEestatsItem *>(s.h_in.p);
   for (uint64_t j = 0; j < n; ++j) items[j] = VsxEestatsItem { (uint32_t) (in.off[w0 + j] - span.lo), in.len[w0 + j] };
   std::memcpy(s.h_in.p + items_bytes, in.qual + span.lo, span.hi - span.lo);
@@ -223,19 +198,19 @@ int submit_window(Slot & s, const Slot & previous, const Input & in, const Devic
   const VsxEestatsItem * d_items = reinterpret_cast<const VsxEestatsItem *>(s.d_in.p);
   VsxEestatsParams P = D.P;
   P.matrix = s.d_matrix.p;
-  VSX_HIP_AS(WHO, hipEventRecord(s.ev_in, s.st));
+  VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_IN], s.st));
   VSX_HIP_AS(WHO, hipMemcpyAsync(s.d_in.p, s.h_in.p, in_bytes, hipMemcpyHostToDevice, s.st));
-  VSX_HIP_AS(WHO, hipEventRecord(s.ev_run, s.st));
+  VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_RUN], s.st));
   VSX_HIP_AS(WHO, vsx_launch_eestats_walk(d_items, (uint32_t) n, s.d_in.p + items_bytes, P, s.d_err.p, s.st));
-  VSX_HIP_AS(WHO, hipEventRecord(s.ev_walked, s.st));
+  VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_WALKED], s.st));
   VSX_HIP_AS(WHO, hipMemcpyAsync(s.h_err.p, s.d_err.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s.st));
   if (D.tables)
     {
       // the chains continue where the previous window's sums ended
-      if (previous.summed) VSX_HIP_AS(WHO, hipStreamWaitEvent(s.st, previous.ev_done, 0));
-      VSX_HIP_AS(WHO, hipEventRecord(s.ev_sum, s.st));
+      if (previous.summed) VSX_HIP_AS(WHO, hipStreamWaitEvent(s.st, previous.ev[EV_DONE], 0));
+      VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_SUM], s.st));
       VSX_HIP_AS(WHO, vsx_launch_eestats_sum(s.d_matrix.p, P.stride, d_items, (uint32_t) n, D.len_max, D.d_sum.p, s.st));
-      VSX_HIP_AS(WHO, hipEventRecord(s.ev_done, s.st));
+      VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_DONE], s.st));
       s.summed = true;
     }
   s.busy = true;
@@ -249,16 +224,9 @@ int collect_window(Slot & s, const vsx_fastq_eestats_opts & o, const Input & in,
   const double t0 = now_s();
   VSX_HIP_AS(WHO, hipStreamSynchronize(s.st));
   s.busy = false;
-  float ms = 0.f;
-  VSX_HIP_AS(WHO, hipEventElapsedTime(&ms, s.ev_in, s.ev_run));
-  g_stats.seconds_h2d += ms * 1e-3;
-  VSX_HIP_AS(WHO, hipEventElapsedTime(&ms, s.ev_run, s.ev_walked));
-  g_stats.seconds_walk += ms * 1e-3;
-  if (tables)
-    {
-      VSX_HIP_AS(WHO, hipEventElapsedTime(&ms, s.ev_sum, s.ev_done));
-      g_stats.seconds_sum += ms * 1e-3;
-    }
+  VSX_HIP_AS(WHO, s.add_elapsed(EV_IN, EV_RUN, g_stats.seconds_h2d));
+  VSX_HIP_AS(WHO, s.add_elapsed(EV_RUN, EV_WALKED, g_stats.seconds_walk));
+  if (tables) VSX_HIP_AS(WHO, s.add_elapsed(EV_SUM, EV_DONE, g_stats.seconds_sum));
   for (uint64_t j = 0; j < s.n; ++j)
     if (s.h_err.p[j] != VSX_EESTATS_NO_ERROR)
       {
@@ -266,14 +234,6 @@ int collect_window(Slot & s, const vsx_fastq_eestats_opts & o, const Input & in,
         return vsxp::quality_failure(WHO, v < o.qmin ? 1 : 2, v, (long long) o.qmin, (long long) o.qmax);
       }
   g_stats.seconds_d2h_output += now_s() - t0;
-  return VSX_OK;
-}
-
-template <typename T>
-int zeroed(DevBuf<T> & b, size_t count)
-{
-  VSX_HIP_AS(WHO, b.alloc(count));
-  VSX_HIP_AS(WHO, hipMemset(b.p, 0, std::max<size_t>(count, 1) * sizeof(T)));
   return VSX_OK;
 }
 
@@ -297,13 +257,13 @@ int accumulate_device(vsx_ctx * ctx, const vsx_fastq_eestats_opts & o, const Inp
   VSX_HIP_AS(WHO, hipMemcpy(d_q2e.p, q2e, 128 * sizeof(double), hipMemcpyHostToDevice));
   VSX_HIP_AS(WHO, d_cutoffs.alloc(cutoffs ? o.n_ee_cutoffs : 0));
   if (cutoffs) VSX_HIP_AS(WHO, hipMemcpy(d_cutoffs.p, o.ee_cutoffs, o.n_ee_cutoffs * sizeof(double), hipMemcpyHostToDevice));
-  int rc = zeroed(d_cut, cutoffs ? L.len_steps * o.n_ee_cutoffs : 0);
+  int rc = zeroed(WHO, d_cut, cutoffs ? L.len_steps * o.n_ee_cutoffs : 0);
   if (rc != VSX_OK) return rc;
   if (tables)
     {
-      if ((rc = zeroed(d_qc, L.len_max * out.qual_cols)) != VSX_OK) return rc;
-      if ((rc = zeroed(d_hist, ee_start(L.len_max))) != VSX_OK) return rc;
-      if ((rc = zeroed(D.d_sum, L.len_max)) != VSX_OK) return rc;
+      if ((rc = zeroed(WHO, d_qc, L.len_max * out.qual_cols)) != VSX_OK) return rc;
+      if ((rc = zeroed(WHO, d_hist, ee_start(L.len_max))) != VSX_OK) return rc;
+      if ((rc = zeroed(WHO, D.d_sum, L.len_max)) != VSX_OK) return rc;
       fill_reads_at(in, L.len_max, out.reads_at);
       VSX_HIP_AS(WHO, d_reads_at.alloc(L.len_max));
       VSX_HIP_AS(WHO, hipMemcpy(d_reads_at.p, out.reads_at, L.len_max * sizeof(uint64_t), hipMemcpyHostToDevice));
@@ -322,8 +282,7 @@ int accumulate_device(vsx_ctx * ctx, const vsx_fastq_eestats_opts & o, const Inp
   Slot slot[2];
   for (Slot & s : slot)
     {
-      VSX_HIP_AS(WHO, hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-      for (hipEvent_t * e : { &s.ev_in, &s.ev_run, &s.ev_walked, &s.ev_sum, &s.ev_done }) VSX_HIP_AS(WHO, hipEventCreate(e));
+      if ((rc = s.create(WHO)) != VSX_OK) return rc;
       VSX_HIP_AS(WHO, s.h_err.alloc(window));
       VSX_HIP_AS(WHO, s.d_err.alloc(window));
       if (tables) VSX_HIP_AS(WHO, s.d_matrix.alloc(window * L.len_max));
@@ -332,35 +291,24 @@ int accumulate_device(vsx_ctx * ctx, const vsx_fastq_eestats_opts & o, const Inp
   uint64_t bytes = 0;
   for (uint64_t k = 0; k < in.n; ++k) bytes = std::max(bytes, in.off[k] + in.len[k]);
   const uint64_t reserve_in = align64(window * sizeof(VsxEestatsItem)) + align64(std::min(SPAN_CAPACITY, bytes) + 64);
-  uint64_t w = 0;
-  for (uint64_t w0 = 0; w0 < in.n; ++w)
-    {
-      Slot & s = slot[w & 1];
-      if (s.busy && (rc = collect_window(s, o, in, tables)) != VSX_OK) return rc;
-      const double t0 = now_s();
-      Span span;
-      const uint64_t wn = plan_window(in, w0, window, span);
-      g_stats.seconds_stage += now_s() - t0;
-      if ((rc = submit_window(s, slot[(w + 1) & 1], in, D, w0, wn, span, reserve_in)) != VSX_OK) return rc;
-      ++g_stats.windows;
-      w0 += wn;
-    }
-  for (uint64_t d = 0; d < 2; ++d)
-    {
-      Slot & s = slot[(w + d) & 1];          // the older window first
-      if (s.busy && (rc = collect_window(s, o, in, tables)) != VSX_OK) return rc;
-    }
+  const vsxp::Side side { in.off, in.len };
+  rc = vsxp::run_windows(slot, in.n,
+    [&](uint64_t w0) { vsxp::Stopwatch t(g_stats.seconds_stage); return vsxp::plan_window(&side, 1, w0, in.n, window, SPAN_CAPACITY); },
+    [&](Slot & s, Slot & previous, uint64_t w0, const vsxp::Window & W) { return submit_window(s, previous, in, D, w0, W, reserve_in); },
+    [&](Slot & s) { return collect_window(s, o, in, tables); },
+    g_stats.windows);
+  if (rc != VSX_OK) return rc;
 
   const double t0 = now_s();
   if (tables)
     {
       Slot & s = slot[0];
-      VSX_HIP_AS(WHO, hipEventRecord(s.ev_in, s.st));
+      VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_IN], s.st));
       VSX_HIP_AS(WHO, vsx_launch_eestats_quantile(d_hist.p, d_reads_at.p, D.len_max, d_bins.p, s.st));
-      VSX_HIP_AS(WHO, hipEventRecord(s.ev_done, s.st));
+      VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_DONE], s.st));
       VSX_HIP_AS(WHO, hipStreamSynchronize(s.st));
       float ms = 0.f;
-      VSX_HIP_AS(WHO, hipEventElapsedTime(&ms, s.ev_in, s.ev_done));
+      VSX_HIP_AS(WHO, hipEventElapsedTime(&ms, s.ev[EV_IN], s.ev[EV_DONE]));
       g_stats.seconds_quantile = ms * 1e-3;
       std::vector<uint32_t> qc(L.len_max * out.qual_cols);
       VSX_HIP_AS(WHO, hipMemcpy(qc.data(), d_qc.p, qc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -457,8 +405,7 @@ int vsx_fastq_eestats(vsx_ctx * ctx, const vsx_fastq_eestats_opts * opts, uint64
   if (!opts || !out || !reads) return fail(VSX_EINVAL, "%s: null argument", WHO);
   std::memset(out, 0, sizeof *out);
   if (n && (!reads->qual || !reads->off || !reads->len)) return fail(VSX_EINVAL, "%s: null argument", WHO);
-  const char * env = std::getenv("VSX_EESTATS");
-  const bool host_all = env && std::strcmp(env, "host") == 0;
+  const bool host_all = vsxp::env_is_host("VSX_EESTATS");
   if (!ctx && !host_all) return fail(VSX_EINVAL, "%s: no context (only VSX_EESTATS=host runs without one)", WHO);
   const int rc_opts = check_options(*opts);
   if (rc_opts != VSX_OK) return rc_opts;

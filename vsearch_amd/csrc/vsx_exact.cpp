@@ -379,8 +379,7 @@ int vsx_search_exact(vsx_searcher * S, uint64_t nq, const char * qblob, uint64_t
   if (!S) return fail(VSX_EINVAL, "%s: null argument", WHO);
   const int rc_q = check_queries(nq, qblob, qbytes, qoff, qlen, out);
   if (rc_q != VSX_OK) return rc_q;
-  const char * env = std::getenv("VSX_EXACT");
-  const bool host_all = (env && std::strcmp(env, "host") == 0) || !S->ctx;
+  const bool host_all = vsxp::env_is_host("VSX_EXACT") || !S->ctx;
   const int rc = run(S, host_all, nq, qblob, qoff, qlen, qmeta, out);
   if (rc != VSX_OK) { vsx_hits_free(out); return rc; }
   out->seconds_total = g_stats.seconds_total = now_s() - t_begin;

@@ -4,9 +4,10 @@
 //   table    10^(-score/10) by quality SYMBOL, score = symbol - ascii and 0 below ascii (std::pow on the host)
 //   tables   the counters live on the device for the whole call; length_counts follows from the lengths on the host; ee_counts and
 //            q_counts are the suffix sums of the downloaded histogram of prefix lengths
-//   windows  the staging plan of vsx_eestats.cpp: consecutive reads spanning at most the staging capacity, one memcpy per blob into
-//            pinned memory, two slots with a stream each.  In vsx_fastq_stats the ordered sum (vsx_launch_eestats_sum, unchanged) of
-//            window k + 1 waits for the sum of window k through an event, so every chain of sum_ee sees the reads in input order.
+//   windows  the pipeline of vsx_window.h with the staging of vsx_eestats.cpp: consecutive reads spanning at most the staging
+//            capacity, one memcpy per blob into pinned memory, two slots with a stream each.  In vsx_fastq_stats the ordered sum
+//            (vsx_launch_eestats_sum, unchanged) of window k + 1 waits for the sum of window k through an event, so every chain of
+//            sum_ee sees the reads in input order.
 //   checks   the kernels report per read (lowest and highest quality character; a byte outside 33 ... 126); the host walks those
 //            in input order, so the first offending read is the one the host restatement names
 //   host     stats_host and chars_host are written from the specification, not from the kernels: the fallback (VSX_FASTQ_STATS=host,
@@ -21,12 +22,14 @@
 #include <vector>
 
 #include "vsx_fastq_stats_internal.h"
-#include "vsx_private.h"
+#include "vsx_window.h"
 
 #pragma clang fp contract(off)
 
+using vsxp::align64;
 using vsxp::fail;
 using vsxp::now_s;
+using vsxp::zeroed;
 using vsxp::DevBuf;
 using vsxp::PinnedBuf;
 
@@ -132,42 +135,17 @@ int chars_host(const vsx_fastq_chars_opts & o, const Input & in, vsx_fastq_chars
   return VSX_OK;
 }
 
-// ---- the window pipeline -------------------------------------------------------------------------------------------------------
-uint64_t align64(uint64_t v) { return (v + 63) & ~(uint64_t) 63; }
+// ---- the window pipeline (vsx_window.h) ------------------------------------------------------------------------------------------
+enum { EV_IN, EV_RUN, EV_WALKED, EV_SUM, EV_DONE, EVENTS };
 
-struct Slot {
-  hipStream_t st = nullptr;
-  hipEvent_t ev_in = nullptr, ev_run = nullptr, ev_walked = nullptr, ev_sum = nullptr, ev_done = nullptr;
+struct Slot : vsxp::Slot<EVENTS> {
   PinnedBuf<uint8_t> h_in;              // items + the span of each blob
   PinnedBuf<uint32_t> h_flag;
   DevBuf<uint8_t> d_in;
   DevBuf<uint32_t> d_flag;              // per read: minmax (stats) or the bad-byte flag (chars)
   DevBuf<double> d_matrix;
-  uint64_t w0 = 0, n = 0;               // the window in flight
-  bool busy = false, summed = false;
-  ~Slot()
-  {
-    if (st) (void) hipStreamSynchronize(st);
-    for (hipEvent_t e : { ev_in, ev_run, ev_walked, ev_sum, ev_done }) if (e) (void) hipEventDestroy(e);
-    if (st) (void) hipStreamDestroy(st);
-  }
+  bool summed = false;
 };
-
-struct Span { uint64_t lo = 0, hi = 0; };
-
-// extend the window at w0 greedily: up to `window` reads whose bytes span at most the capacity; a single read always fits
-uint64_t plan_window(const Input & in, uint64_t w0, uint64_t window, Span & span)
-{
-  uint64_t n = 0;
-  for (uint64_t k = w0; k < in.n && n < window; ++k, ++n)
-    {
-      const uint64_t lo = in.off[k], hi = lo + in.len[k];
-      const Span next { n ? std::min(span.lo, lo) : lo, n ? std::max(span.hi, hi) : hi };
-      if (n && next.hi - next.lo > SPAN_CAPACITY) break;
-      span = next;
-    }
-  return n;
-}
 
 // what differs between the two calls
 struct Device {
@@ -184,8 +162,8 @@ int create_slots(Slot (&slot)[2], const Device & D, uint64_t window, uint64_t ma
 {
   for (Slot & s : slot)
     {
-      VSX_HIP_AS(D.who, hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-      for (hipEvent_t * e : { &s.ev_in, &s.ev_run, &s.ev_walked, &s.ev_sum, &s.ev_done }) VSX_HIP_AS(D.who, hipEventCreate(e));
+      const int rc = s.create(D.who);
+      if (rc != VSX_OK) return rc;
       VSX_HIP_AS(D.who, s.h_flag.alloc(window));
       VSX_HIP_AS(D.who, s.d_flag.alloc(window));
       if (matrix_elems) VSX_HIP_AS(D.who, s.d_matrix.alloc(matrix_elems));
@@ -194,20 +172,18 @@ int create_slots(Slot (&slot)[2], const Device & D, uint64_t window, uint64_t ma
 }
 
 // stage window [w0, w0 + n) into the slot and enqueue copy-in, the kernel(s) and the copy-out of the per-read flags on its stream
-int submit_window(Slot & s, const Slot & previous, const Input & in, const Device & D, uint64_t w0, uint64_t n, const Span & span,
+int submit_window(Slot & s, const Slot & previous, const Input & in, const Device & D, uint64_t w0, const vsxp::Window & W,
                   uint64_t reserve_in)
 {
   const double t0 = now_s();
+  const uint64_t n = W.n;
+  const vsxp::Span span = W.span[0];
   const uint64_t blobs = D.chars ? 2 : 1;
   const uint64_t items_bytes = align64(n * sizeof(VsxEestatsItem));
   const uint64_t span_bytes = align64(span.hi - span.lo + 64);
   const uint64_t in_bytes = items_bytes + blobs * span_bytes;
-  if (!s.d_in.p || in_bytes > s.d_in.n)
-    {
-      s.h_in.release(); s.d_in.release();
-      VSX_HIP_AS(D.who, s.h_in.alloc(std::max(in_bytes, reserve_in)));
-      VSX_HIP_AS(D.who, s.d_in.alloc(std::max(in_bytes, reserve_in)));
-    }
+  const int rc = vsxp::grow_pair(D.who, s.h_in, s.d_in, in_bytes, std::max(in_bytes, reserve_in));
+  if (rc != VSX_OK) return rc;
   VsxEestatsItem * items = reinterpret_cast<VsxEestatsItem *>(s.h_in.p);
   for (uint64_t j = 0; j < n; ++j) items[j] = VsxEestatsItem { (uint32_t) (in.off[w0 + j] - span.lo), in.len[w0 + j] };
   std::memcpy(s.h_in.p + items_bytes, in.qual + span.lo, span.hi - span.lo);
@@ -215,9 +191,9 @@ int submit_window(Slot & s, const Slot & previous, const Input & in, const Devic
   s.w0 = w0; s.n = n;
   const VsxEestatsItem * d_items = reinterpret_cast<const VsxEestatsItem *>(s.d_in.p);
   const uint8_t * d_qual = s.d_in.p + items_bytes;
-  VSX_HIP_AS(D.who, hipEventRecord(s.ev_in, s.st));
+  VSX_HIP_AS(D.who, hipEventRecord(s.ev[EV_IN], s.st));
   VSX_HIP_AS(D.who, hipMemcpyAsync(s.d_in.p, s.h_in.p, in_bytes, hipMemcpyHostToDevice, s.st));
-  VSX_HIP_AS(D.who, hipEventRecord(s.ev_run, s.st));
+  VSX_HIP_AS(D.who, hipEventRecord(s.ev[EV_RUN], s.st));
   if (D.chars)
     VSX_HIP_AS(D.who, vsx_launch_fastq_chars(d_items, (uint32_t) n, d_qual + span_bytes, d_qual, D.tail, D.d_acc.p, s.d_flag.p, s.st));
   else
@@ -226,15 +202,15 @@ int submit_window(Slot & s, const Slot & previous, const Input & in, const Devic
       P.matrix = s.d_matrix.p;
       VSX_HIP_AS(D.who, vsx_launch_fastq_stats_walk(d_items, (uint32_t) n, d_qual, P, s.d_flag.p, s.st));
     }
-  VSX_HIP_AS(D.who, hipEventRecord(s.ev_walked, s.st));
+  VSX_HIP_AS(D.who, hipEventRecord(s.ev[EV_WALKED], s.st));
   VSX_HIP_AS(D.who, hipMemcpyAsync(s.h_flag.p, s.d_flag.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s.st));
   if (!D.chars)
     {
       // the chains continue where the previous window's sums ended
-      if (previous.summed) VSX_HIP_AS(D.who, hipStreamWaitEvent(s.st, previous.ev_done, 0));
-      VSX_HIP_AS(D.who, hipEventRecord(s.ev_sum, s.st));
+      if (previous.summed) VSX_HIP_AS(D.who, hipStreamWaitEvent(s.st, previous.ev[EV_DONE], 0));
+      VSX_HIP_AS(D.who, hipEventRecord(s.ev[EV_SUM], s.st));
       VSX_HIP_AS(D.who, vsx_launch_eestats_sum(s.d_matrix.p, D.P.stride, d_items, (uint32_t) n, D.P.len_max, D.d_sum.p, s.st));
-      VSX_HIP_AS(D.who, hipEventRecord(s.ev_done, s.st));
+      VSX_HIP_AS(D.who, hipEventRecord(s.ev[EV_DONE], s.st));
       s.summed = true;
     }
   s.busy = true;
@@ -247,12 +223,9 @@ int wait_window(Slot & s, const Device & D)
 {
   VSX_HIP_AS(D.who, hipStreamSynchronize(s.st));
   s.busy = false;
-  float ms_in = 0.f, ms_run = 0.f, ms_sum = 0.f;
-  VSX_HIP_AS(D.who, hipEventElapsedTime(&ms_in, s.ev_in, s.ev_run));
-  VSX_HIP_AS(D.who, hipEventElapsedTime(&ms_run, s.ev_run, s.ev_walked));
-  if (!D.chars) VSX_HIP_AS(D.who, hipEventElapsedTime(&ms_sum, s.ev_sum, s.ev_done));
-  if (D.chars) { g_chars.seconds_h2d += ms_in * 1e-3; g_chars.seconds_kernel += ms_run * 1e-3; }
-  else { g_stats.seconds_h2d += ms_in * 1e-3; g_stats.seconds_walk += ms_run * 1e-3; g_stats.seconds_sum += ms_sum * 1e-3; }
+  VSX_HIP_AS(D.who, s.add_elapsed(EV_IN, EV_RUN, D.chars ? g_chars.seconds_h2d : g_stats.seconds_h2d));
+  VSX_HIP_AS(D.who, s.add_elapsed(EV_RUN, EV_WALKED, D.chars ? g_chars.seconds_kernel : g_stats.seconds_walk));
+  if (!D.chars) VSX_HIP_AS(D.who, s.add_elapsed(EV_SUM, EV_DONE, g_stats.seconds_sum));
   return VSX_OK;
 }
 
@@ -289,34 +262,11 @@ int run_windows(Slot (&slot)[2], const Input & in, const Device & D, uint64_t wi
   uint64_t bytes = 0;
   for (uint64_t k = 0; k < in.n; ++k) bytes = std::max(bytes, in.off[k] + in.len[k]);
   const uint64_t reserve_in = align64(window * sizeof(VsxEestatsItem)) + (D.chars ? 2 : 1) * align64(std::min(SPAN_CAPACITY, bytes) + 64);
-  int rc = VSX_OK;
-  uint64_t w = 0;
-  for (uint64_t w0 = 0; w0 < in.n; ++w)
-    {
-      Slot & s = slot[w & 1];
-      if (s.busy && (rc = collect(s)) != VSX_OK) return rc;
-      const double t0 = now_s();
-      Span span;
-      const uint64_t wn = plan_window(in, w0, window, span);
-      *D.seconds_stage += now_s() - t0;
-      if ((rc = submit_window(s, slot[(w + 1) & 1], in, D, w0, wn, span, reserve_in)) != VSX_OK) return rc;
-      ++windows;
-      w0 += wn;
-    }
-  for (uint64_t d = 0; d < 2; ++d)
-    {
-      Slot & s = slot[(w + d) & 1];          // the older window first
-      if (s.busy && (rc = collect(s)) != VSX_OK) return rc;
-    }
-  return VSX_OK;
-}
-
-template <typename T>
-int zeroed(const char * who, DevBuf<T> & b, size_t count)
-{
-  VSX_HIP_AS(who, b.alloc(count));
-  VSX_HIP_AS(who, hipMemset(b.p, 0, std::max<size_t>(count, 1) * sizeof(T)));
-  return VSX_OK;
+  const vsxp::Side side { in.off, in.len };
+  return vsxp::run_windows(slot, in.n,
+    [&](uint64_t w0) { vsxp::Stopwatch t(*D.seconds_stage); return vsxp::plan_window(&side, 1, w0, in.n, window, SPAN_CAPACITY); },
+    [&](Slot & s, Slot & previous, uint64_t w0, const vsxp::Window & W) { return submit_window(s, previous, in, D, w0, W, reserve_in); },
+    collect, windows);
 }
 
 uint64_t stats_window(const vsx_fastq_stats_opts & o, uint64_t n, uint64_t len_max)
@@ -421,11 +371,7 @@ int scan_lengths(const char * who, uint64_t n, const vsx_fastx_reads & reads, Le
   return VSX_OK;
 }
 
-bool host_mode()
-{
-  const char * env = std::getenv("VSX_FASTQ_STATS");
-  return env && std::strcmp(env, "host") == 0;
-}
+bool host_mode() { return vsxp::env_is_host("VSX_FASTQ_STATS"); }
 
 // what the reference's check_parameters refuses
 int check_stats_options(const vsx_fastq_stats_opts & o)

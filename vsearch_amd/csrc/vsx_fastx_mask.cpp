@@ -28,6 +28,8 @@
 
 #pragma clang fp contract(off)
 
+using vsxp::align64;
+using vsxp::env_u64;
 using vsxp::fail;
 using vsxp::now_s;
 using vsxp::DevBuf;
@@ -47,14 +49,6 @@ constexpr uint64_t BUILTIN_LONG_MIN = 65536;
 constexpr uint64_t BUILTIN_SEGMENT = 4096;
 
 thread_local vsx_fastx_mask_stats g_stats {};
-
-uint64_t align64(uint64_t v) { return (v + 63) & ~(uint64_t) 63; }
-
-uint64_t env_u64(const char * name, uint64_t otherwise)
-{
-  const char * e = std::getenv(name);
-  return (e && *e) ? std::strtoull(e, nullptr, 10) : otherwise;
-}
 
 struct Input {
   uint64_t n;
@@ -390,8 +384,7 @@ int vsx_fastx_mask(vsx_ctx * ctx, const vsx_fastx_mask_opts * opts, uint64_t n, 
   if (!opts || !out) return fail(VSX_EINVAL, "%s: null argument", WHO);
   std::memset(out, 0, sizeof *out);
   if (n && (!offsets || !lengths || (!blob && blob_bytes))) return fail(VSX_EINVAL, "%s: null argument", WHO);
-  const char * env = std::getenv("VSX_MASK");
-  const bool host_all = env && std::strcmp(env, "host") == 0;
+  const bool host_all = vsxp::env_is_host("VSX_MASK");
   if (!ctx && !host_all) return fail(VSX_EINVAL, "%s: no context (only VSX_MASK=host runs without one)", WHO);
   const vsx_fastx_mask_opts & o = *opts;
   if (o.qmask < VSX_MASK_NONE || o.qmask > VSX_MASK_DUST) return fail(VSX_EINVAL, "%s: qmask must be 0 (none), 1 (soft) or 2 (dust)", WHO);

@@ -5,7 +5,8 @@
 //   windows  a window is a run of consecutive reads whose bytes span at most the staging capacity: [min offset, max offset + length).
 //            The span is copied into pinned memory with one memcpy per blob and the kernel follows the caller's offsets, rebased to
 //            the span -- no per-read packing.  Scattered or overlapping offsets merely give small windows; a single read always fits.
-//            Two slots (pinned + device buffers, one stream each): window k + 1 is staged while window k's kernel runs.
+//            Two slots (pinned + device buffers, one stream each): window k + 1 is staged while window k's kernel runs.  Planner,
+//            slot base and driver are those of vsx_window.h.
 //   host     analyse_host below is written from the specification, not from the kernel; VSX_FILTER=host sends every read through it.
 #include <hip/hip_runtime.h>
 
@@ -17,10 +18,11 @@
 #include <cstring>
 
 #include "vsx_filter_internal.h"
-#include "vsx_private.h"
+#include "vsx_window.h"
 
 #pragma clang fp contract(off)
 
+using vsxp::align64;
 using vsxp::fail;
 using vsxp::now_s;
 using vsxp::DevBuf;
@@ -108,69 +110,20 @@ int put_read(const vsx_fastx_filter_opts & o, const Sides & in, vsx_fastx_filter
   return VSX_OK;
 }
 
-// ---- the window pipeline ----------------------------------------------------------------------------------------------------
-uint64_t align64(uint64_t v) { return (v + 63) & ~(uint64_t) 63; }
+// ---- the window pipeline (vsx_window.h) ---------------------------------------------------------------------------------------
+enum { EV_IN, EV_RUN, EV_DONE, EVENTS };
 
-struct Slot {
-  hipStream_t st = nullptr;
-  hipEvent_t ev_in = nullptr, ev_run = nullptr, ev_done = nullptr;
+struct Slot : vsxp::Slot<EVENTS> {
   PinnedBuf<uint8_t> h_in, h_out;       // in: per side items + sequence span + quality span; out: per side records
   DevBuf<uint8_t> d_in, d_out;
-  uint64_t w0 = 0, n = 0;               // the window in flight
-  bool busy = false;
-  ~Slot()
-  {
-    if (st) (void) hipStreamSynchronize(st);
-    for (hipEvent_t e : { ev_in, ev_run, ev_done }) if (e) (void) hipEventDestroy(e);
-    if (st) (void) hipStreamDestroy(st);
-  }
 };
 
-// the bytes [lo, hi) of one side's blobs that reads [w0, w0 + n) touch
-struct Span { uint64_t lo = 0, hi = 0; };
-
-// extend the window at w0 greedily: up to `window` reads, every side's span within the capacity; a single read always fits
-uint64_t plan_window(const Sides & in, uint64_t w0, uint64_t n_total, uint64_t window, Span span[2])
-{
-  uint64_t n = 0;
-  for (uint64_t k = w0; k < n_total && n < window; ++k, ++n)
-    {
-      Span next[2];
-      bool fits = true;
-      for (int s = 0; s < in.n_sides; ++s)
-        {
-          const uint64_t lo = in.side[s]->off[k], hi = lo + in.side[s]->len[k];
-          next[s].lo = n ? std::min(span[s].lo, lo) : lo;
-          next[s].hi = n ? std::max(span[s].hi, hi) : hi;
-          fits = fits && next[s].hi - next[s].lo <= SPAN_CAPACITY;
-        }
-      if (n && !fits) break;
-      span[0] = next[0]; span[1] = next[1];
-    }
-  return n;
-}
-
-int reserve_slot(Slot & s, uint64_t in_bytes, uint64_t out_bytes)
-{
-  if (!s.d_in.p || in_bytes > s.d_in.n)
-    {
-      s.h_in.release(); s.d_in.release();
-      VSX_HIP_AS(WHO, s.h_in.alloc(in_bytes));
-      VSX_HIP_AS(WHO, s.d_in.alloc(in_bytes));
-    }
-  if (!s.d_out.p || out_bytes > s.d_out.n)
-    {
-      s.h_out.release(); s.d_out.release();
-      VSX_HIP_AS(WHO, s.h_out.alloc(out_bytes));
-      VSX_HIP_AS(WHO, s.d_out.alloc(out_bytes));
-    }
-  return VSX_OK;
-}
-
 // stage window [w0, w0 + n) into the slot and enqueue copy-in, one kernel per side, copy-out on its stream
-int submit_window(Slot & s, const Sides & in, const VsxFilterParams & P, uint64_t w0, uint64_t n, const Span span[2], uint64_t reserve_in, uint64_t reserve_out)
+int submit_window(Slot & s, const Sides & in, const VsxFilterParams & P, uint64_t w0, const vsxp::Window & W, uint64_t reserve_in, uint64_t reserve_out)
 {
   const double t0 = now_s();
+  const uint64_t n = W.n;
+  const vsxp::Span * const span = W.span;
   const uint64_t items_bytes = align64(n * sizeof(VsxFilterItem)), recs_bytes = align64(n * sizeof(VsxFilterDevRec));
   uint64_t side_off[2] = { 0, 0 }, seq_off[2], qual_off[2], in_bytes = 0;
   for (int k = 0; k < in.n_sides; ++k)
@@ -180,7 +133,9 @@ int submit_window(Slot & s, const Sides & in, const VsxFilterParams & P, uint64_
       qual_off[k] = seq_off[k] + bytes;
       in_bytes = qual_off[k] + (P.has_qual ? bytes : 0);
     }
-  const int rc = reserve_slot(s, std::max(in_bytes, reserve_in), std::max(recs_bytes * in.n_sides, reserve_out));
+  const uint64_t out_bytes = recs_bytes * in.n_sides;
+  int rc = vsxp::grow_pair(WHO, s.h_in, s.d_in, in_bytes, std::max(in_bytes, reserve_in));
+  if (rc == VSX_OK) rc = vsxp::grow_pair(WHO, s.h_out, s.d_out, out_bytes, std::max(out_bytes, reserve_out));
   if (rc != VSX_OK) return rc;
   for (int k = 0; k < in.n_sides; ++k)
     {
@@ -192,13 +147,13 @@ int submit_window(Slot & s, const Sides & in, const VsxFilterParams & P, uint64_
       if (P.has_qual) std::memcpy(s.h_in.p + qual_off[k], r.qual + span[k].lo, bytes);
     }
   s.w0 = w0; s.n = n;
-  VSX_HIP_AS(WHO, hipEventRecord(s.ev_in, s.st));
+  VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_IN], s.st));
   VSX_HIP_AS(WHO, hipMemcpyAsync(s.d_in.p, s.h_in.p, in_bytes, hipMemcpyHostToDevice, s.st));
-  VSX_HIP_AS(WHO, hipEventRecord(s.ev_run, s.st));
+  VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_RUN], s.st));
   for (int k = 0; k < in.n_sides; ++k)
     VSX_HIP_AS(WHO, vsx_launch_filter(reinterpret_cast<const VsxFilterItem *>(s.d_in.p + side_off[k]), (uint32_t) n, s.d_in.p + seq_off[k],
                                       s.d_in.p + qual_off[k], P, reinterpret_cast<VsxFilterDevRec *>(s.d_out.p + k * recs_bytes), s.st));
-  VSX_HIP_AS(WHO, hipEventRecord(s.ev_done, s.st));
+  VSX_HIP_AS(WHO, hipEventRecord(s.ev[EV_DONE], s.st));
   VSX_HIP_AS(WHO, hipMemcpyAsync(s.h_out.p, s.d_out.p, recs_bytes * in.n_sides, hipMemcpyDeviceToHost, s.st));
   s.busy = true;
   g_stats.seconds_stage += now_s() - t0;
@@ -211,11 +166,8 @@ int collect_window(Slot & s, const vsx_fastx_filter_opts & o, const Sides & in, 
   const double t0 = now_s();
   VSX_HIP_AS(WHO, hipStreamSynchronize(s.st));
   s.busy = false;
-  float ms = 0.f;
-  VSX_HIP_AS(WHO, hipEventElapsedTime(&ms, s.ev_in, s.ev_run));
-  g_stats.seconds_h2d += ms * 1e-3;
-  VSX_HIP_AS(WHO, hipEventElapsedTime(&ms, s.ev_run, s.ev_done));
-  g_stats.seconds_kernel += ms * 1e-3;
+  VSX_HIP_AS(WHO, s.add_elapsed(EV_IN, EV_RUN, g_stats.seconds_h2d));
+  VSX_HIP_AS(WHO, s.add_elapsed(EV_RUN, EV_DONE, g_stats.seconds_kernel));
   const uint64_t recs_bytes = align64(s.n * sizeof(VsxFilterDevRec));
   const VsxFilterDevRec * recs[2] = { reinterpret_cast<const VsxFilterDevRec *>(s.h_out.p), reinterpret_cast<const VsxFilterDevRec *>(s.h_out.p + recs_bytes) };
   for (uint64_t j = 0; j < s.n; ++j)
@@ -306,37 +258,20 @@ int run(vsx_ctx * ctx, const vsx_fastx_filter_opts & o, uint64_t n, const Sides 
 
   const uint64_t window = o.window > 0 ? (uint64_t) o.window : WINDOW_READS;
   Slot slot[2];
-  for (Slot & s : slot)
-    {
-      VSX_HIP_AS(WHO, hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-      for (hipEvent_t * e : { &s.ev_in, &s.ev_run, &s.ev_done }) VSX_HIP_AS(WHO, hipEventCreate(e));
-    }
+  for (Slot & s : slot) { const int rc = s.create(WHO); if (rc != VSX_OK) return rc; }
   // the first window of a slot sizes its buffers for every later one (a single read above the capacity grows them when it comes)
   uint64_t reserve_in = 0;
   for (int s = 0; s < in.n_sides; ++s)
     reserve_in += align64(std::min(window, n) * sizeof(VsxFilterItem))
                   + (has_qual ? 2 : 1) * align64(std::min(SPAN_CAPACITY, in.side[s]->bytes) + VSX_FILTER_PAD);
   const uint64_t reserve_out = in.n_sides * align64(std::min(window, n) * sizeof(VsxFilterDevRec));
-  uint64_t w = 0;
-  for (uint64_t w0 = 0; w0 < n; ++w)
-    {
-      Slot & s = slot[w & 1];
-      if (s.busy) { const int rc = collect_window(s, o, in, out); if (rc != VSX_OK) return rc; }
-      const double t0 = now_s();
-      Span span[2];
-      const uint64_t wn = plan_window(in, w0, n, window, span);
-      g_stats.seconds_stage += now_s() - t0;
-      const int rc = submit_window(s, in, P, w0, wn, span, reserve_in, reserve_out);
-      if (rc != VSX_OK) return rc;
-      ++g_stats.windows;
-      w0 += wn;
-    }
-  for (uint64_t d = 0; d < 2; ++d)
-    {
-      Slot & s = slot[(w + d) & 1];          // the older window first
-      if (s.busy) { const int rc = collect_window(s, o, in, out); if (rc != VSX_OK) return rc; }
-    }
-  return VSX_OK;
+  vsxp::Side side[2] = { { in.side[0]->off, in.side[0]->len }, { nullptr, nullptr } };
+  if (in.n_sides > 1) side[1] = { in.side[1]->off, in.side[1]->len };
+  return vsxp::run_windows(slot, n,
+    [&](uint64_t w0) { vsxp::Stopwatch t(g_stats.seconds_stage); return vsxp::plan_window(side, in.n_sides, w0, n, window, SPAN_CAPACITY); },
+    [&](Slot & s, Slot &, uint64_t w0, const vsxp::Window & W) { return submit_window(s, in, P, w0, W, reserve_in, reserve_out); },
+    [&](Slot & s) { return collect_window(s, o, in, out); },
+    g_stats.windows);
 }
 
 }  // namespace
@@ -375,8 +310,7 @@ int vsx_fastx_filter(vsx_ctx * ctx, const vsx_fastx_filter_opts * opts, uint64_t
     if (n && (!in.side[s]->seq || !in.side[s]->off || !in.side[s]->len)) return fail(VSX_EINVAL, "%s: null argument", WHO);
   if (rev && n && (fwd->qual == nullptr) != (rev->qual == nullptr))
     return fail(VSX_EINVAL, "%s: the forward and the reverse reads must both have qualities or both have none", WHO);
-  const char * env = std::getenv("VSX_FILTER");
-  const bool host_all = env && std::strcmp(env, "host") == 0;
+  const bool host_all = vsxp::env_is_host("VSX_FILTER");
   if (!ctx && !host_all) return fail(VSX_EINVAL, "%s: no context (only VSX_FILTER=host runs without one)", WHO);
   const int rc_opts = check_options(*opts);
   if (rc_opts != VSX_OK) return rc_opts;

@@ -21,6 +21,7 @@
 
 using vsxp::fail;
 using vsxp::now_s;
+using vsxp::Scratch;
 
 namespace {
 
@@ -191,32 +192,6 @@ int host_route(const Plan & P, vsx_getseqs_out & out)
 }
 
 // ---- the device route ------------------------------------------------------------------------------------------------------------
-template <typename T>
-struct Scratch {
-  vsx_ctx * ctx = nullptr;
-  T * p = nullptr;
-  size_t got = 0;
-  Scratch() = default;
-  Scratch(const Scratch &) = delete;
-  Scratch & operator=(const Scratch &) = delete;
-  ~Scratch() { if (p) vsx_internal_scratch_put(ctx, p, got); }
-  hipError_t alloc(vsx_ctx * c, size_t count)
-  {
-    if (p) { vsx_internal_scratch_put(ctx, p, got); p = nullptr; }
-    ctx = c;
-    void * q = nullptr;
-    const hipError_t e = vsx_internal_scratch_get(c, std::max<size_t>(count, 1) * sizeof(T), &q, &got);
-    if (e == hipSuccess) p = static_cast<T *>(q);
-    return e;
-  }
-  hipError_t upload(vsx_ctx * c, const T * h, size_t count, hipStream_t st)
-  {
-    const hipError_t e = alloc(c, count);
-    if (e != hipSuccess || count == 0) return e;
-    return hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, st);
-  }
-};
-
 struct DeviceBufs {
   Scratch<uint8_t> hblob, nblob, temp;
   Scratch<uint64_t> hoff, noff;
@@ -396,7 +371,7 @@ int make_plan(const vsx_getseqs_opts * o, const vsx_labels * H, const uint32_t *
   while (slots < 2 * (uint64_t) P.nn) slots <<= 1;
   P.slots = (uint32_t) slots;
   P.hash_mask = ~0ull;
-  if (const char * env = std::getenv("VSX_GETSEQS_HASH_BITS"))
+  if (const char * env = std::getenv("VSX_GETSEQS_HASH_BITS"))      // (not vsxp::env_u64: a signed value, used only within 1 .. 63)
     {
       const long b = std::strtol(env, nullptr, 10);
       if (b >= 1 && b < 64) P.hash_mask = (1ull << b) - 1;
@@ -428,12 +403,10 @@ int run(vsx_ctx * ctx, const vsx_getseqs_opts * opts, const vsx_labels * H, cons
   g_stats.seconds_stage += now_s() - t_begin;
 
   bool host_all = true;
-  const char * env = std::getenv("VSX_GETSEQS");
-  uint64_t device_headers = COUNT_LIMIT, max_lengths = UINT64_MAX;
-  if (const char * limit = std::getenv("VSX_GETSEQS_DEVICE_HEADERS")) device_headers = std::min<uint64_t>(device_headers, std::strtoull(limit, nullptr, 10));
-  if (const char * limit = std::getenv("VSX_GETSEQS_MAX_LENGTHS")) max_lengths = std::strtoull(limit, nullptr, 10);
+  const uint64_t device_headers = std::min<uint64_t>(COUNT_LIMIT, vsxp::env_u64("VSX_GETSEQS_DEVICE_HEADERS", COUNT_LIMIT, true));
+  const uint64_t max_lengths = vsxp::env_u64("VSX_GETSEQS_MAX_LENGTHS", UINT64_MAX, true);
   if (!ctx) g_stats.host_no_context = 1;
-  else if (env && std::strcmp(env, "host") == 0) g_stats.host_environment = 1;
+  else if (vsxp::env_is_host("VSX_GETSEQS")) g_stats.host_environment = 1;
   else if (H->n > device_headers) g_stats.host_count = 1;
   else if (P.max_needle > VSX_GETSEQS_DEVICE_MAX_BYTES) g_stats.host_needle_length = 1;
   else if (!P.exact && P.max_header > VSX_GETSEQS_DEVICE_MAX_BYTES) g_stats.host_header_length = 1;
@@ -441,12 +414,9 @@ int run(vsx_ctx * ctx, const vsx_getseqs_opts * opts, const vsx_labels * H, cons
   else host_all = false;
   if (!host_all)
     {
-      size_t free_b = 0, total_b = 0;
-      if (hipSetDevice(vsx_internal_device(ctx)) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess)
-        { release(out); return fail(VSX_EHIP, "%s: the device does not answer", WHO); }
-      uint64_t need = device_bytes(P);
-      if (const char * pretend = std::getenv("VSX_GETSEQS_PRETEND_BYTES")) need = std::strtoull(pretend, nullptr, 10);
-      if (need + VSX_DEVICE_RESERVE_BYTES > free_b) { host_all = true; g_stats.host_memory = 1; }
+      bool fits = false;
+      if ((rc = vsxp::device_fits(ctx, WHO, device_bytes(P), "VSX_GETSEQS_PRETEND_BYTES", &fits)) != VSX_OK) { release(out); return rc; }
+      if (!fits) { host_all = true; g_stats.host_memory = 1; }
     }
   rc = host_all ? host_route(P, *out) : device_route(ctx, P, *out);
   if (rc != VSX_OK) { release(out); return rc; }

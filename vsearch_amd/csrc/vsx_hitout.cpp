@@ -20,6 +20,7 @@
 #include "vsx_private.h"
 #include "vsx_search_internal.h"
 
+using vsxp::array_of;
 using vsxp::fail;
 using vsxp::now_s;
 
@@ -278,9 +279,6 @@ void host_md(const Input & in, const Staged & S, uint64_t h, std::string & md)
 }
 
 template <typename T>
-T * array_of(uint64_t n) { return static_cast<T *>(std::calloc(std::max<uint64_t>(n, 1), sizeof(T))); }
-
-template <typename T>
 bool copy_out(T *& dst, const std::vector<T> & v)
 {
   dst = array_of<T>(v.size());
@@ -520,17 +518,12 @@ int run(vsx_searcher * SR, Input & in, const vsx_hitout_opts * o, vsx_hit_text *
   if (!SR || !SR->ctx) g_stats.host_no_context = 1;
   else
     {
-      const char * env = std::getenv("VSX_HITOUT");
-      uint64_t device_hits = HIT_LIMIT;
-      if (const char * limit = std::getenv("VSX_HITOUT_DEVICE_HITS")) device_hits = std::min<uint64_t>(device_hits, std::strtoull(limit, nullptr, 10));
-      if (env && std::strcmp(env, "host") == 0) g_stats.host_environment = 1;
+      const uint64_t device_hits = std::min<uint64_t>(HIT_LIMIT, vsxp::env_u64("VSX_HITOUT_DEVICE_HITS", HIT_LIMIT, true));
+      if (vsxp::env_is_host("VSX_HITOUT")) g_stats.host_environment = 1;
       else if (nh > device_hits) g_stats.host_hit_count = 1;
       else host_all = false;
       if (!host_all && nh)
         {
-          size_t free_b = 0, total_b = 0;
-          if (hipSetDevice(vsx_internal_device(SR->ctx)) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess)
-            { release(out); return fail(VSX_EHIP, "%s: the device does not answer", WHO); }
           uint64_t need = 0;
           for (uint64_t h0 = 0; h0 < nh; h0 += in.window)
             {
@@ -539,8 +532,9 @@ int run(vsx_searcher * SR, Input & in, const vsx_hitout_opts * o, vsx_hit_text *
             }
           need += S.qtext.size() + ((uint64_t) 64 << 20);
           if (!SR->hidx || !SR->hidx->db_uploaded) need += in.db_bytes;
-          if (const char * pretend = std::getenv("VSX_HITOUT_PRETEND_BYTES")) need = std::strtoull(pretend, nullptr, 10);
-          if (need + VSX_DEVICE_RESERVE_BYTES > free_b) { host_all = true; g_stats.host_memory = 1; }
+          bool fits = false;
+          if ((rc = vsxp::device_fits(SR->ctx, WHO, need, "VSX_HITOUT_PRETEND_BYTES", &fits)) != VSX_OK) { release(out); return rc; }
+          if (!fits) { host_all = true; g_stats.host_memory = 1; }
         }
     }
   rc = host_all ? host_route(in, S, *out) : device_route(SR, in, S, *out);

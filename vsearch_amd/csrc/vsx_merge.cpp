@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "vsx_merge_internal.h"
-#include "vsx_private.h"
+#include "vsx_window.h"
 
 #pragma clang fp contract(off)
 
@@ -250,21 +250,13 @@ int quality_failure(const vsx_merge_opts & o, const QualError & e)
   return vsxp::quality_failure("vsx_merge_pairs", e.kind, e.value, (long long) o.fastq_qmin, (long long) o.fastq_qmax);
 }
 
-// ---- the window pipeline ----------------------------------------------------------------------------------------------------
-struct Slot {
-  hipStream_t st = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+// ---- the window pipeline (vsx_window.h) ---------------------------------------------------------------------------------------
+enum { EV_RUN, EV_DONE, EVENTS };
+
+struct Slot : vsxp::Slot<EVENTS> {
   PinnedBuf<uint8_t> h_in, h_out;                            // in: items + blob; out: recs + seq + qual
   DevBuf<uint8_t> d_in, d_out;                               // (each as large as its pinned twin)
-  uint64_t w0 = 0, n = 0, blob_off = 0, out_bytes = 0;       // the window in flight
-  bool busy = false;
-  ~Slot()
-  {
-    if (st) (void) hipStreamSynchronize(st);
-    if (ev0) (void) hipEventDestroy(ev0);
-    if (ev1) (void) hipEventDestroy(ev1);
-    if (st) (void) hipStreamDestroy(st);
-  }
+  uint64_t blob_off = 0, out_bytes = 0;                      // of the window in flight
 };
 
 uint64_t align16(uint64_t v) { return (v + 15) & ~(uint64_t) 15; }
@@ -274,25 +266,6 @@ struct Inputs {
   const uint64_t * foff, * roff;
   const uint32_t * flen, * rlen;
 };
-
-int reserve_slot(Slot & s, uint64_t in_bytes, uint64_t out_bytes)
-{
-  if (!s.d_in.p || in_bytes > s.d_in.n)
-    {
-      s.h_in.release(); s.d_in.release();
-      const uint64_t want = in_bytes + (in_bytes >> 3);
-      VSX_HIP_AS("vsx_merge_pairs", s.h_in.alloc(want));
-      VSX_HIP_AS("vsx_merge_pairs", s.d_in.alloc(want));
-    }
-  if (!s.d_out.p || out_bytes > s.d_out.n)
-    {
-      s.h_out.release(); s.d_out.release();
-      const uint64_t want = out_bytes + (out_bytes >> 3);
-      VSX_HIP_AS("vsx_merge_pairs", s.h_out.alloc(want));
-      VSX_HIP_AS("vsx_merge_pairs", s.d_out.alloc(want));
-    }
-  return VSX_OK;
-}
 
 // pack window [w0, w0 + n) into the slot and enqueue copy-in, kernel, copy-out on its stream
 int submit_window(Slot & s, const Inputs & in, const VsxMergeParams & P, uint64_t w0, uint64_t n)
@@ -305,7 +278,10 @@ int submit_window(Slot & s, const Inputs & in, const VsxMergeParams & P, uint64_
       { blob += 2 * ((uint64_t) in.flen[k] + in.rlen[k]); outb += (uint64_t) in.flen[k] + in.rlen[k]; }
   const uint64_t recs_bytes = align16(n * sizeof(VsxMergeDevRec));
   outb = align16(outb);
-  const int rc = reserve_slot(s, items_bytes + blob + 16, recs_bytes + 2 * outb + 16);
+  // a window that outgrows the slot's buffers replaces them with an eighth of headroom
+  const uint64_t in_bytes = items_bytes + blob + 16, out_bytes = recs_bytes + 2 * outb + 16;
+  int rc = vsxp::grow_pair("vsx_merge_pairs", s.h_in, s.d_in, in_bytes, in_bytes + (in_bytes >> 3));
+  if (rc == VSX_OK) rc = vsxp::grow_pair("vsx_merge_pairs", s.h_out, s.d_out, out_bytes, out_bytes + (out_bytes >> 3));
   if (rc != VSX_OK) return rc;
   VsxMergeItem * items = reinterpret_cast<VsxMergeItem *>(s.h_in.p);
   uint8_t * hb = s.h_in.p + items_bytes;
@@ -324,10 +300,10 @@ int submit_window(Slot & s, const Inputs & in, const VsxMergeParams & P, uint64_
     }
   s.w0 = w0; s.n = n; s.blob_off = items_bytes; s.out_bytes = recs_bytes + 2 * outb;
   VSX_HIP_AS("vsx_merge_pairs", hipMemcpyAsync(s.d_in.p, s.h_in.p, items_bytes + blob, hipMemcpyHostToDevice, s.st));
-  VSX_HIP_AS("vsx_merge_pairs", hipEventRecord(s.ev0, s.st));
+  VSX_HIP_AS("vsx_merge_pairs", hipEventRecord(s.ev[EV_RUN], s.st));
   VSX_HIP_AS("vsx_merge_pairs", vsx_launch_merge(reinterpret_cast<const VsxMergeItem *>(s.d_in.p), (uint32_t) n, s.d_in.p + items_bytes, P,
                         reinterpret_cast<VsxMergeDevRec *>(s.d_out.p), s.d_out.p + recs_bytes, s.d_out.p + recs_bytes + outb, s.st));
-  VSX_HIP_AS("vsx_merge_pairs", hipEventRecord(s.ev1, s.st));
+  VSX_HIP_AS("vsx_merge_pairs", hipEventRecord(s.ev[EV_DONE], s.st));
   VSX_HIP_AS("vsx_merge_pairs", hipMemcpyAsync(s.h_out.p, s.d_out.p, s.out_bytes, hipMemcpyDeviceToHost, s.st));
   s.busy = true;
   g_stats.seconds_stage += now_s() - t0;
@@ -340,9 +316,7 @@ int collect_window(Slot & s, const Inputs & in, const HostParams & H, const Tabl
   const double t0 = now_s();
   VSX_HIP_AS("vsx_merge_pairs", hipStreamSynchronize(s.st));
   s.busy = false;
-  float ms = 0.f;
-  VSX_HIP_AS("vsx_merge_pairs", hipEventElapsedTime(&ms, s.ev0, s.ev1));
-  g_stats.seconds_kernel += ms * 1e-3;
+  VSX_HIP_AS("vsx_merge_pairs", s.add_elapsed(EV_RUN, EV_DONE, g_stats.seconds_kernel));
   const VsxMergeItem * items = reinterpret_cast<const VsxMergeItem *>(s.h_in.p);
   const VsxMergeDevRec * recs = reinterpret_cast<const VsxMergeDevRec *>(s.h_out.p);
   const uint64_t recs_bytes = align16(s.n * sizeof(VsxMergeDevRec));
@@ -415,8 +389,7 @@ int vsx_merge_pairs(vsx_ctx * ctx, const vsx_merge_opts * opts, uint64_t n,
   if (!opts || !out || (n && (!fwd_seq || !fwd_qual || !fwd_off || !fwd_len || !rev_seq || !rev_qual || !rev_off || !rev_len)))
     return fail(VSX_EINVAL, "vsx_merge_pairs: null argument");
   std::memset(out, 0, sizeof *out);
-  const char * env = std::getenv("VSX_MERGE");
-  const bool host_all = env && std::strcmp(env, "host") == 0;
+  const bool host_all = vsxp::env_is_host("VSX_MERGE");
   if (!ctx && !host_all) return fail(VSX_EINVAL, "vsx_merge_pairs: no context (only VSX_MERGE=host runs without one)");
 
   HostParams H;
@@ -489,26 +462,14 @@ int vsx_merge_pairs(vsx_ctx * ctx, const vsx_merge_opts * opts, uint64_t n,
 
       const uint64_t window = o.window > 0 ? (uint64_t) o.window : 32768;
       Slot slot[2];
-      for (Slot & s : slot)
-        {
-          VSX_HIP_AS("vsx_merge_pairs", hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-          VSX_HIP_AS("vsx_merge_pairs", hipEventCreate(&s.ev0));
-          VSX_HIP_AS("vsx_merge_pairs", hipEventCreate(&s.ev1));
-        }
-      uint64_t w = 0;
-      for (uint64_t w0 = 0; w0 < n; w0 += window, ++w)
-        {
-          Slot & s = slot[w & 1];
-          if (s.busy) { const int rc = collect_window(s, in, H, T, ob); if (rc != VSX_OK) return rc; }
-          const int rc = submit_window(s, in, P, w0, std::min(window, n - w0));
-          if (rc != VSX_OK) return rc;
-          ++g_stats.windows;
-        }
-      for (uint64_t d = 0; d < 2; ++d)
-        {
-          Slot & s = slot[(w + d) & 1];          // the older window first
-          if (s.busy) { const int rc = collect_window(s, in, H, T, ob); if (rc != VSX_OK) return rc; }
-        }
+      for (Slot & s : slot) { const int rc = s.create("vsx_merge_pairs"); if (rc != VSX_OK) return rc; }
+      // (fixed windows of `window` pairs: the pairs are packed, so no span limits a window)
+      const int rc = vsxp::run_windows(slot, n,
+        [&](uint64_t w0) { vsxp::Window W; W.n = std::min(window, n - w0); return W; },
+        [&](Slot & s, Slot &, uint64_t w0, const vsxp::Window & W) { return submit_window(s, in, P, w0, W.n); },
+        [&](Slot & s) { return collect_window(s, in, H, T, ob); },
+        g_stats.windows);
+      if (rc != VSX_OK) return rc;
     }
 
   out->n = n; out->rec = ob.rec; out->seq_blob = ob.seq; out->qual_blob = ob.qual; out->blob_bytes = ob.used;

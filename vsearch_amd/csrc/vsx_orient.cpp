@@ -44,13 +44,6 @@ thread_local vsx_orient_stats g_stats;
 
 struct Queries { uint64_t n; const char * blob; uint64_t bytes; const uint64_t * off; const uint32_t * len; const char * qual; };
 
-uint64_t env_u64(const char * name, uint64_t fallback)
-{
-  const char * e = std::getenv(name);
-  const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
-  return v > 0 ? v : fallback;
-}
-
 // ---- the host table ----------------------------------------------------------------------------------------------------------
 void build_host(const vsx_searcher & S, VsxOrientIndex & X)
 {
@@ -197,7 +190,8 @@ int build_device(vsx_searcher * S, VsxOrientIndex & X)
   VSX_HIP_AS(WHO, hipMemsetAsync(X.d_mc.p, 0, nwords * sizeof(uint32_t), st));
 
   // chunks of consecutive sequences within the key budget; a sequence longer than the budget is a chunk of its own
-  const uint64_t budget = env_u64("VSX_ORIENT_BUILD_KEYS", (uint64_t) 1 << 25);       // (tests lower it to cut small databases)
+  const uint64_t budget_env = vsxp::env_u64("VSX_ORIENT_BUILD_KEYS", 0);             // (tests lower it to cut small databases)
+  const uint64_t budget = budget_env ? budget_env : (uint64_t) 1 << 25;               // (here a 0 counts as unset)
   const uint64_t max_seqs = (uint64_t) 1 << 20;
   std::vector<uint64_t> slot_of(n + 1, 0);
   for (uint64_t i = 0; i < n; ++i) slot_of[i + 1] = slot_of[i] + S->len[i];
@@ -257,7 +251,7 @@ int run_device(vsx_searcher * S, VsxOrientIndex & X, const vsx_orient_opts & o, 
   VSX_HIP_AS(WHO, hipSetDevice(vsx_internal_device(S->ctx)));
   hipStream_t st = vsx_internal_stream(S->ctx);
   const uint64_t window = o.window > 0 ? (uint64_t) o.window : 65536;
-  const int hash_bits = (int) env_u64("VSX_ORIENT_HASH_BITS", 0);                 // tests: long probe chains
+  const int hash_bits = (int) vsxp::env_u64("VSX_ORIENT_HASH_BITS", 0);                // tests: long probe chains
   const bool text = out->text != nullptr, qual = out->qual != nullptr;
   const int nth = std::max(1, S->threads);
 
@@ -404,8 +398,7 @@ int run(vsx_searcher * S, const vsx_orient_opts & o, const Queries & Q, vsx_orie
   if (!out->rec || (o.want_text && !out->text) || (o.want_text && Q.qual && !out->qual)) return fail(VSX_ENOMEM, "%s: out of memory", WHO);
 
   // the route of each query
-  const char * env = std::getenv("VSX_ORIENT");
-  if (S->w > VSX_ORIENT_MAX_DEVICE_WORDLENGTH || !device_serves(S) || (env && std::strcmp(env, "host") == 0))
+  if (S->w > VSX_ORIENT_MAX_DEVICE_WORDLENGTH || !device_serves(S) || vsxp::env_is_host("VSX_ORIENT"))
     {
       (S->w > VSX_ORIENT_MAX_DEVICE_WORDLENGTH ? g_stats.queries_host_wordlength : g_stats.queries_host_forced) += Q.n;
       run_host(*S, X, o, Q, nullptr, Q.n, out);

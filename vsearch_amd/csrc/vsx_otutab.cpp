@@ -26,7 +26,10 @@
 #include "vsx_private.h"
 
 using vsxp::fail;
+using vsxp::array_of;
+using vsxp::download;
 using vsxp::now_s;
+using vsxp::Scratch;
 
 namespace {
 
@@ -219,40 +222,6 @@ int host_mid(const Input & in, Mid & M)
 }
 
 // ---- the device route ------------------------------------------------------------------------------------------------------------
-// a block of the context's scratch pool
-template <typename T>
-struct Scratch {
-  vsx_ctx * ctx = nullptr;
-  T * p = nullptr;
-  size_t got = 0;
-  Scratch() = default;
-  Scratch(const Scratch &) = delete;
-  Scratch & operator=(const Scratch &) = delete;
-  ~Scratch() { if (p) vsx_internal_scratch_put(ctx, p, got); }
-  hipError_t alloc(vsx_ctx * c, size_t count)
-  {
-    if (p) { vsx_internal_scratch_put(ctx, p, got); p = nullptr; }
-    ctx = c;
-    void * q = nullptr;
-    const hipError_t e = vsx_internal_scratch_get(c, std::max<size_t>(count, 1) * sizeof(T), &q, &got);
-    if (e == hipSuccess) p = static_cast<T *>(q);
-    return e;
-  }
-  hipError_t upload(vsx_ctx * c, const T * h, size_t count, hipStream_t st)
-  {
-    const hipError_t e = alloc(c, count);
-    if (e != hipSuccess || count == 0) return e;
-    return hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, st);
-  }
-};
-
-template <typename T>
-hipError_t download(std::vector<T> & h, const T * d, size_t count, hipStream_t st)
-{
-  h.resize(count);
-  return count ? hipMemcpyAsync(h.data(), d, count * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess;
-}
-
 uint64_t device_bytes(const Input & in) { return in.Q->bytes + in.T->bytes + 200 * (in.nq() + in.nt()) + ((uint64_t) 64 << 20); }
 
 // the buffers of one grouping, sized for the larger side and used by both in turn
@@ -333,7 +302,7 @@ int device_mid_run(vsx_ctx * ctx, hipStream_t st, const Input & in, DeviceBufs &
   const uint32_t nq = (uint32_t) Q.n, nt = (uint32_t) T.n;
   uint64_t hash_mask = ~0ull;
   uint32_t hash_bits = 64;
-  if (const char * env = std::getenv("VSX_OTUTAB_HASH_BITS"))
+  if (const char * env = std::getenv("VSX_OTUTAB_HASH_BITS"))      // (not vsxp::env_u64: a signed value, used only within 1 .. 63)
     {
       const long b = std::strtol(env, nullptr, 10);
       if (b >= 1 && b < 64) { hash_bits = (uint32_t) b; hash_mask = (1ull << b) - 1; }
@@ -483,8 +452,6 @@ void release(vsx_otutab_result * out)
   std::memset(out, 0, sizeof *out);
 }
 
-template <typename T>
-T * array_of(uint64_t n) { return static_cast<T *>(std::calloc(std::max<uint64_t>(n, 1), sizeof(T))); }
 
 // the spans' bytes one after the other; a span of length NONE takes none
 bool pack(const char * blob, const std::vector<Span> & spans, char *& out_blob, uint64_t & out_bytes, uint64_t *& out_off, uint32_t *& out_len)
@@ -560,23 +527,17 @@ int run(vsx_ctx * ctx, Route route, const vsx_otutab_opts * opts, const vsx_labe
   if (route == ROUTE_HOST_ONLY) {}
   else
     {
-      const char * env = std::getenv("VSX_OTUTAB");
-      const char * limit = std::getenv("VSX_OTUTAB_DEVICE_LABELS");                          // testing aid: a lower limit of the device route
-      uint64_t device_labels = LABEL_LIMIT;
-      if (limit) device_labels = std::min<uint64_t>(device_labels, std::strtoull(limit, nullptr, 10));
+      // testing aid: a lower limit of the device route
+      const uint64_t device_labels = std::min<uint64_t>(LABEL_LIMIT, vsxp::env_u64("VSX_OTUTAB_DEVICE_LABELS", LABEL_LIMIT, true));
       if (!ctx) g_stats.host_no_context = 1;
-      else if (env && std::strcmp(env, "host") == 0) g_stats.host_environment = 1;
+      else if (vsxp::env_is_host("VSX_OTUTAB")) g_stats.host_environment = 1;
       else if (Q->n > device_labels || T->n > device_labels || Q->n + T->n > device_labels) g_stats.host_label_count = 1;
       else host_all = false;
       if (!host_all)
         {
-          size_t free_b = 0, total_b = 0;
-          if (hipSetDevice(vsx_internal_device(ctx)) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess)
-            return fail(VSX_EHIP, "%s: the device does not answer", WHO);
-          uint64_t need = device_bytes(in);
-          const char * pretend = std::getenv("VSX_OTUTAB_PRETEND_BYTES");                      // testing aid: what the call is taken to need
-          if (pretend) need = std::strtoull(pretend, nullptr, 10);
-          if (need + VSX_DEVICE_RESERVE_BYTES > free_b) { host_all = true; g_stats.host_memory = 1; }
+          bool fits = false;                                                                   // (the testing aid: what the call is taken to need)
+          if ((rc = vsxp::device_fits(ctx, WHO, device_bytes(in), "VSX_OTUTAB_PRETEND_BYTES", &fits)) != VSX_OK) return rc;
+          if (!fits) { host_all = true; g_stats.host_memory = 1; }
         }
     }
   Mid M;

@@ -12,6 +12,8 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -232,6 +234,96 @@ struct PinnedBuf {
 template <typename T>
 hipError_t ensure_pinned(PinnedBuf<T> & b, size_t count) { return (b.p && count <= b.n) ? hipSuccess : b.alloc(count + count / 4); }
 
+// a fresh DevBuf of `count` elements filled from the host, and a device array into a host vector; both on `st`, neither waits
+template <typename T>
+hipError_t upload(DevBuf<T> & d, const T * h, size_t count, hipStream_t st)
+{
+  const hipError_t e = d.alloc(count);
+  if (e != hipSuccess || count == 0) return e;
+  return hipMemcpyAsync(d.p, h, count * sizeof(T), hipMemcpyHostToDevice, st);
+}
+
+template <typename T>
+hipError_t download(std::vector<T> & h, const T * d, size_t count, hipStream_t st)
+{
+  h.resize(count);
+  return count ? hipMemcpyAsync(h.data(), d, count * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+// a fresh DevBuf of `count` zeroes (null stream)
+template <typename T>
+int zeroed(const char * who, DevBuf<T> & b, size_t count)
+{
+  VSX_HIP_AS(who, b.alloc(count));
+  VSX_HIP_AS(who, hipMemset(b.p, 0, std::max<size_t>(count, 1) * sizeof(T)));
+  return VSX_OK;
+}
+
+// a lease on a block of the context's scratch pool (vsx_internal_scratch_get): it goes back when the lease ends or is renewed
+template <typename T>
+struct Scratch {
+  vsx_ctx * ctx = nullptr;
+  T * p = nullptr;
+  size_t got = 0;
+  Scratch() = default;
+  Scratch(const Scratch &) = delete;
+  Scratch & operator=(const Scratch &) = delete;
+  ~Scratch() { if (p) vsx_internal_scratch_put(ctx, p, got); }
+  hipError_t alloc(vsx_ctx * c, size_t count)
+  {
+    if (p) { vsx_internal_scratch_put(ctx, p, got); p = nullptr; }
+    ctx = c;
+    void * q = nullptr;
+    const hipError_t e = vsx_internal_scratch_get(c, std::max<size_t>(count, 1) * sizeof(T), &q, &got);
+    if (e == hipSuccess) p = static_cast<T *>(q);
+    return e;
+  }
+  hipError_t upload(vsx_ctx * c, const T * h, size_t count, hipStream_t st)
+  {
+    const hipError_t e = alloc(c, count);
+    if (e != hipSuccess || count == 0) return e;
+    return hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, st);
+  }
+};
+
+// the arrays of a result the caller frees with free(): n elements (one for none), null when the host is out of memory.
+// array_of zeroes them; host_array leaves them as malloc gives them, for results of which every element is written
+// (tests/test_gpu_poison.py would show one that is not: keep each caller on the kind it has).
+template <typename T>
+T * array_of(uint64_t n) { return static_cast<T *>(std::calloc(std::max<uint64_t>(n, 1), sizeof(T))); }
+template <typename T>
+T * host_array(uint64_t n) { return static_cast<T *>(std::malloc(std::max<uint64_t>(n, 1) * sizeof(T))); }
+
+inline uint64_t align64(uint64_t v) { return (v + 63) & ~(uint64_t) 63; }
+
+// a decimal number from the environment; `otherwise` when the variable is unset.  An empty value counts as unset -- except under
+// empty_is_zero, for the variables that were always read with a bare strtoull (which makes 0 of it).
+inline uint64_t env_u64(const char * name, uint64_t otherwise, bool empty_is_zero = false)
+{
+  const char * e = std::getenv(name);
+  return (e && (*e || empty_is_zero)) ? std::strtoull(e, nullptr, 10) : otherwise;
+}
+
+// VSX_<COMMAND>=host: the call takes the command's host route
+inline bool env_is_host(const char * name)
+{
+  const char * env = std::getenv(name);
+  return env && std::strcmp(env, "host") == 0;
+}
+
+// Does a call that needs `need` bytes of device memory fit beside the reserve?  Sets the context's device and reads its free
+// memory (hipMemGetInfo answers for the current device, so the two belong together).  pretend_env, where not null, names the
+// testing aid that replaces `need`.  The answer goes to *fits; the return value is VSX_OK unless either call fails.
+inline int device_fits(const vsx_ctx * ctx, const char * who, uint64_t need, const char * pretend_env, bool * fits)
+{
+  size_t free_b = 0, total_b = 0;
+  if (hipSetDevice(vsx_internal_device(ctx)) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess)
+    return fail(VSX_EHIP, "%s: the device does not answer", who);
+  if (pretend_env) need = env_u64(pretend_env, need, true);
+  *fits = need + VSX_DEVICE_RESERVE_BYTES <= free_b;
+  return VSX_OK;
+}
+
 // the error probability of a Phred quality value, as the reference tabulates it (the device never evaluates it: tables are host-built)
 inline double phred_error_probability(int value) { return std::pow(10.0, -value / 10.0); }
 
@@ -243,6 +335,14 @@ inline int quality_failure(const char * who, int kind, int value, long long qmin
 }
 
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// adds the host time of its scope to a field of a command's stats
+struct Stopwatch {
+  double & seconds;
+  const double t0 = now_s();
+  explicit Stopwatch(double & field) : seconds(field) {}
+  ~Stopwatch() { seconds += now_s() - t0; }
+};
 
 inline int usable_cpus() { return vsx_internal_usable_cpus(); }
 

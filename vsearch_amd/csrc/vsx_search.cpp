@@ -424,7 +424,7 @@ void build_index(vsx_searcher * S)
 // bucket per word, 9..15 with tagged postings (vsx_kmer.hip); at least one sequence.  VSX_KMER=host forces the host threads.
 bool device_kmer_ok(const vsx_searcher & S)
 {
-  static const bool forced_host = std::getenv("VSX_KMER") && std::strcmp(std::getenv("VSX_KMER"), "host") == 0;
+  static const bool forced_host = vsxp::env_is_host("VSX_KMER");
   return !forced_host && S.w >= 3 && S.w <= 15 && !S.len.empty();
 }
 // clustering rebuilds SUBSET indexes (centroids, round members) every round: those exist for the one-bucket-per-word form only

@@ -416,8 +416,7 @@ int check_call(const vsx_sintax_opts * o, uint64_t nq, const char * qblob, uint6
 
 uint32_t max_dblen()
 {
-  const char * e = std::getenv("VSX_SINTAX_MAX_DBLEN");                // tests lower the limit to force the route
-  const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
+  const uint64_t v = vsxp::env_u64("VSX_SINTAX_MAX_DBLEN", 0);         // tests lower the limit to force the route
   return (v > 0 && v < VSX_SINTAX_MAX_DBLEN) ? (uint32_t) v : VSX_SINTAX_MAX_DBLEN;
 }
 
@@ -444,12 +443,11 @@ int run(vsx_searcher * S, const vsx_sintax_opts & o, const Queries & Q, vsx_sint
   if (!out->rec || (o.want_candidates && !out->candidates)) return fail(VSX_ENOMEM, "%s: out of memory", WHO);
 
   // the route of the call
-  const char * env = std::getenv("VSX_SINTAX");
   uint64_t * route = &g_stats.queries_device;
   if (o.sintax_random) route = &g_stats.queries_host_random;
   else if (S->w > 8) route = &g_stats.queries_host_wordlength;
   else if (n && *std::max_element(S->len.begin(), S->len.end()) >= max_dblen()) route = &g_stats.queries_host_dblen;
-  else if (!S->ctx || n == 0 || (env && std::strcmp(env, "host") == 0)) route = &g_stats.queries_host_forced;
+  else if (!S->ctx || n == 0 || vsxp::env_is_host("VSX_SINTAX")) route = &g_stats.queries_host_forced;
   *route += Q.n;
   if (route == &g_stats.queries_device) { const int rc = run_device(S, X, o, Q, out); if (rc != VSX_OK) return rc; }
   else run_host(S, X, o, Q, out);
