@@ -1,5 +1,5 @@
 """Inputs that put the result marshalling (the dense run buffer, vsx_cigar_text_kernel in vsearch_amd/csrc/vsx_tbtext.hip, settle() /
-fetch_core() / fetch_ranked_lists() and the exports in vsx_host.cpp) on its edges, and what the scalar oracle says they must give.
+fetch_core() / fetch_ranked_lists() and the exports in vsx_fetch.cpp) on its edges, and what the scalar oracle says they must give.
 
 A case is a dictionary: "name", "P" (scoring in search16_init order), "queries", "targets", "qidx", "tidx" (pairs by index: no
 sequence is replicated), "host" (the pairs the library answers without the device: empty query, empty target, size guard) and
@@ -7,7 +7,7 @@ sequence is replicated), "host" (the pairs the library answers without the devic
 oracle, without a device, that every case reaches the edge it is named after, and tests/test_gpu_marshal.py compares the device
 with the same oracle rows.
 
-Facts used here (vsx_tbtext.hip, vsx_host.cpp): a pair's text is its CIGAR + NUL, padded with zero bytes to a multiple of 4 -- for
+Facts used here (vsx_tbtext.hip, vsx_fetch.cpp): a pair's text is its CIGAR + NUL, padded with zero bytes to a multiple of 4 -- for
 the pairs the DEVICE formats; the strings of host-answered pairs follow the device text in pair order, CIGAR + NUL back to back
 without padding, so their offsets are not dword-aligned by design (fetch_core() writes them byte-wise on the host); one
 lane formats one pair, a wave of 64 lanes allocates its strings with one atomic, a block is 256 lanes; a run length has 1 .. 5
@@ -140,7 +140,7 @@ PIPE_PAIRS, PIPE_SLICE, PIPE_RUNS_CAP, PIPE_TEXT_CAP = 4200, 700, 60000, 90000
 
 
 def pipeline_cuts(n, slice_pairs):
-    """the slice boundaries vsx_align_pairs takes for n >= 3 slices' worth of pairs whose neighbours never share a query (vsx_host.cpp
+    """the slice boundaries vsx_align_pairs takes for n >= 3 slices' worth of pairs whose neighbours never share a query (vsx_align_pairs.cpp
     align_pairs_impl): a quarter and a half slice, the middle in equal parts of at most a slice, a half and a quarter"""
     assert n >= 3 * slice_pairs
     head = [slice_pairs // 4, slice_pairs // 2]

@@ -120,7 +120,7 @@ def result_rows(res):
 # ---- the aligner (vsx_device.hip, vsx_tbtext.hip, vsx_rank.hip) -------------------------------------------------------------------
 
 def tilt_reach(P, Q, D):
-    """the planner's bound (vsx_host.cpp tilt_possible()), as tests/test_gpu_parity.py states it"""
+    """the planner's bound (vsx_plan.cpp tilt_possible()), as tests/test_gpu_parity.py states it"""
     B = max(abs(P[0]), abs(P[1]), *P[8:14])
     G = max(P[2:8])
     return 4 * G + 2 * (Q + ((D + 3) & ~3) + 64) * B

@@ -1,5 +1,5 @@
 """-m gpu: the stage between the traceback and the caller -- the dense run buffer, vsx_cigar_text_kernel (vsx_tbtext.hip), settle() /
-fetch_core() / fetch_ranked_lists() and the device-to-device exports (vsx_host.cpp) -- on the inputs of tests/marshal_data.py.
+fetch_core() / fetch_ranked_lists() and the device-to-device exports (vsx_fetch.cpp) -- on the inputs of tests/marshal_data.py.
 
 Expected values are the scalar oracle's rows, field for field and CIGAR included (a pair the filter rejects keeps its numbers and loses
 its CIGAR; tests/test_marshal_host.py asserts without a device that the inputs reach their edges).  The overflow recovery is reached

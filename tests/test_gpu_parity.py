@@ -362,7 +362,7 @@ def test_pipelined_slices_equal_one_plan(gpu_required):
 
 
 def _tilt_reach(P, Q, D):
-    """the planner's bound (vsx_host.cpp tilt_possible()): |any value the tilted kernel forms| stays below this"""
+    """the planner's bound (vsx_plan.cpp tilt_possible()): |any value the tilted kernel forms| stays below this"""
     B = max(abs(P[0]), abs(P[1]), *P[8:14])
     G = max(P[2:8])
     return 4 * G + 2 * (Q + ((D + 3) & ~3) + 64) * B
@@ -550,7 +550,7 @@ def test_sparse_class_threshold(gpu_required):
 @pytest.mark.gpu
 def test_memory_pressure_releases_idle_blocks(gpu_required, oracle):
     """r05: a context keeps its checkpoint blocks, its slab and a pool of idle scratch between plans; whoever runs out of device memory
-    calls vsx_internal_memory_pressure(device) and every context of the device gives back what no plan holds (vsx_host.cpp).  Here: two
+    calls vsx_internal_memory_pressure(device) and every context of the device gives back what no plan holds (vsx_context.cpp).  Here: two
     contexts with warm blocks, the hook called by hand -- the blocks are gone, bytes were released, and both contexts plan and align again
     (a context with a LIVE plan keeps that plan's block until the plan dies)."""
     import ctypes as C

@@ -61,7 +61,7 @@ def test_history_is_strictly_larger(case):
 
 
 def _pick_rows(Q):
-    """vsx_host.cpp pick_rows() over vsx_supported_rows(): the first row count R with 16 R >= Q, never more rows than the query has"""
+    """vsx_plan.cpp pick_rows() over vsx_supported_rows(): the first row count R with 16 R >= Q, never more rows than the query has"""
     from vsearch_amd import _lib
     lib = _lib.load()
     lib.vsx_supported_rows.restype = C.POINTER(C.c_int)

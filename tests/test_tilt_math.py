@@ -97,7 +97,7 @@ def test_last_row_left_implies_ext_left_with_positive_open(seed):
     """What the MAX3 class's interior steps rely on (vsx_forward_kernel LASTFAST): along the LAST query row the
     traceback's "the I run continues through column j" is left(j) or ext-left(j); with a positive gap open of the query's right end
     left implies ext-left, so ext-left alone decides -- in plain and in tilted coordinates.  With a zero open the implication fails
-    (the planner keeps such scorings out of the class, vsx_host.cpp tilt_possible()): the test shows a counter-example exists."""
+    (the planner keeps such scorings out of the class, vsx_plan.cpp tilt_possible()): the test shows a counter-example exists."""
     rng = random.Random(1000 + seed)
     counter_examples = 0
     for _ in range(60):

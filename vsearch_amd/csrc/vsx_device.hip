@@ -74,7 +74,7 @@ DEV u32 dpp_rol1(u32 src) { return (u32) __builtin_amdgcn_update_dpp((int) src, 
 // profile in LDS (any IUPAC / unknown symbol on either side).
 // ---------------------------------------------------------------------------------------------
 // TRACK = false drops the running H min/max (the overflow rule): the planner selects it only for tasks
-// whose score range provably stays inside (SHRT_MIN + max(go+ge), SHRT_MAX) -- see vsx_host.cpp no_overflow_possible().
+// whose score range provably stays inside (SHRT_MIN + max(go+ge), SHRT_MAX) -- see vsx_plan.cpp no_overflow_possible().
 // No direction bits are stored, only CHECKPOINTS: every step each lane stores the (H, F) pair it hands to the next
 // pipeline position (row checkpoints, 8 B) and every 16 steps its whole column state hprev[R], E[R] (column
 // checkpoints); the traceback kernel recomputes the direction bits only for the <= R x 16 tiles the path crosses.
@@ -105,7 +105,7 @@ DEV u32 dpp_rol1(u32 src) { return (u32) __builtin_amdgcn_update_dpp((int) src, 
 // in which the recurrence is the same max-plus recurrence with score' = score + 2g, every QR' = QR - g, every R' = R - g:
 //   H*(i,j) = max(H*(i-1,j-1) + S + 2g, F*(i,j), E*(i,j)),  F*(i+1,j) = max(F*(i,j) - (Rt_j - g), H*(i,j) - (QRt_j - g)),  E* alike.
 // Both sides of every comparison sit on the same cell, so every maximum picks the same operand and every direction bit is
-// unchanged; the planner proves the shifted range (vsx_host.cpp tilt_possible()).  The host hands over the primed constants
+// unchanged; the planner proves the shifted range (vsx_plan.cpp tilt_possible()).  The host hands over the primed constants
 // and tables (VsxDevParams with tilt = g); what this kernel adds is that in the interior R' = 0, so F - R and E - R are not
 // computed at all: 7 instead of 9 packed instructions per lane-row.  Borders: Htop*(j) = Htop(j) + (j-1)g, Hleft* alike,
 // H*(-1,-1) = -2g; the score is un-tilted in the epilogue; checkpoints hold tilted values (the traceback recomputes with the
@@ -145,7 +145,7 @@ DEV u32 pk_max3_bits(u32 a, u32 b, u32 c)            // IEEE maximum of three: t
 // reference refills its 8 SIMD lanes with new targets as old ones finish (align_simd.cpp:1823-1946); here a task was one wave whatever
 // the number of its targets (a query with 1 candidate paid for 8: VERDICT r04 missing 3).  A task keeps its VsxTask and its VsxSlotOut
 // entries; the NQ tasks of a wave share ONE checkpoint block and ONE step range (VsxTask::steps = the longest of them, ::dir_off the
-// same: the planner's job, vsx_host.cpp), in which lane group gw of the wave owns the slots l * 4 + gw exactly as in a whole-wave
+// same: the planner's job, vsx_plan.cpp), in which lane group gw of the wave owns the slots l * 4 + gw exactly as in a whole-wave
 // task -- every store instruction still writes 768 B of full lines (the first build gave each task a block of its own: 12-byte pieces
 // 48 bytes apart, 4 x the lines, each partially written: cands = 1 ran 1.5 x SLOWER than as whole waves,
 // profiles/r05/r05b_sparse_ab_first_build.txt).  The traceback finds a pair's lane group as VsxTask::group0 + slot / 2.  Each
@@ -161,7 +161,7 @@ DEV u32 pk_max3_bits(u32 a, u32 b, u32 c)            // IEEE maximum of three: t
 // of 16 codes at a dword instead of a byte per row), which one wave cannot afford (two waves per SIMD: measured +18 %);
 // four waves sharing it can, when a query has >= 32 targets (--allpairs_global).  No look-ahead register set: the R dwords of a step are
 // read at its top, row r's compute waits for its own quarter only.  Everything a task owns -- VsxTask, checkpoint block, VsxSlotOut -- is
-// as in the whole-wave class, so the traceback is unchanged.  The planner forms the groups of four (vsx_host.cpp).
+// as in the whole-wave class, so the traceback is unchanged.  The planner forms the groups of four (vsx_plan.cpp).
 // ONE (r06): every task of the launch is a SINGLE-STRIP query (Q <= 16 R -- which pick_rows() gives every query of at most 512 symbols;
 // the planner knows per launch, Launch::multi).  The strip loop, its hand-over buffer and the per-strip address set then fold away at
 // compile time.  What that is worth was measured before it was built (a forced build, profiles/r06/r06l_onestrip_ab.txt): the whole-wave
@@ -193,7 +193,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
   // -ge (query-left extension) and a diagonal seeded with -go, so the first real row sees exactly Htop(j-1), Htop(j) and
   // F = Htop(j) - QR_t(j) -- and every position hands (H, F) over from its compile-time row R-1: no per-row capture.
   // Needs the LDS profile (a per-row constant score), no min/max tracking (the dummies would pollute it) and
-  // QR_q(interior) >= ge (the planner checks both, vsx_host.cpp no_overflow_possible()).  The traceback of this class
+  // QR_q(interior) >= ge (the planner checks both, vsx_plan.cpp no_overflow_possible()).  The traceback of this class
   // (vsx_traceback_ck_kernel<R, true>) uses the same slot layout.
   constexpr bool TOPPAD = !TRACK;
   static_assert(!TILT || TOPPAD, "tilted coordinates exist for the TOPPAD class only");
@@ -670,7 +670,7 @@ vsx_forward_kernel(const VsxDevParams P, const VsxTask * __restrict__ tasks,
               // LASTFAST (r04): in the last query row "left" implies "ext-left" when its gap-open penalty is positive -- E > max(h0, F)
               // makes H = E, and then (E - R) - (H - QR) = QR - R = go > 0 -- so `cont` of the leave-column tracking is the sign of
               // he - e alone: no h1 of its own (the row takes the three-way maximum like the others), no h1 - E, no OR.  The planner
-              // admits a pair to the MAX3 class only with go_q(right end) > 0 (vsx_host.cpp tilt_possible()); phase B needs
+              // admits a pair to the MAX3 class only with go_q(right end) > 0 (vsx_plan.cpp tilt_possible()); phase B needs
               // left(D - 1) by itself and keeps the long form.
               constexpr bool LASTFAST = MAX3 && SHARED;
 #pragma unroll
@@ -1049,7 +1049,7 @@ DEV int wave_max_i32(int v)
 
 // Arithmetic of the tile recompute.  PACKED = the DP kernel's saturating v_pk_*_i16 (this pair in the LOW int16 half,
 // sign bits funnelled to the right); FAST16 = for tasks whose scores provably never saturate (the planner's TRACK = 0
-// class, vsx_host.cpp no_overflow_possible()): values biased by 0x8000 into unsigned 16 bits, so the half-rate-free VOP2
+// class, vsx_plan.cpp no_overflow_possible()): values biased by 0x8000 into unsigned 16 bits, so the half-rate-free VOP2
 // forms v_add_u16 / v_sub_u16 / v_max_u16 (2 cycles per wave, measured: profiles/r01_ubench_valu.txt) give the same
 // numbers as the clamped packed ops (4 cycles), the comparison a > b is the sign of an exact 32-bit v_sub_u32, and one
 // v_alignbit_b32 shifts that sign into the direction word.
@@ -1909,7 +1909,7 @@ vsx_traceback_tilt_kernel(const VsxDevParams P, const VsxFilterDev FL, const Vsx
             const long p0 = gstart >> 1;                                     // floor, also for gstart = -1
             in.par = (int) (gstart - 2 * p0);
             // pairs p0 .. p0 + 8, unclamped: one base address and immediate offsets.  Pairs outside the region (p0 = -1, or past the
-            // last pair) feed entries nobody reads; the chunk's block has VSX_CK_SLACK_DW readable dwords at both ends (vsx_host.cpp)
+            // last pair) feed entries nobody reads; the chunk's block has VSX_CK_SLACK_DW readable dwords at both ends (vsx_plan.cpp)
             const u32 * bp = base + p0 * (long) VSX_ROWCK_PAIR_DW(true);
             if (LSTAGE)
               {

@@ -88,7 +88,7 @@ struct VsxFilterDev {
   int64_t maxsubs, maxgaps, mincols, maxdiffs;
   // r06, ranked plans (vsx_align_pairs_ranked): the traceback's epilogue appends every accepted / weak pair (plan-local pair index + the
   // identity the filter compared) and every pair the 16-bit DP refused at run time to two lists -- the hand-written compaction that
-  // the host then orders (vsx_host.cpp fetch_ranked_lists).  rank_counts == nullptr: off.
+  // the host then orders (vsx_fetch.cpp fetch_ranked_lists).  rank_counts == nullptr: off.
   uint32_t * rank_counts;      // [0] kept, [1] refused
   uint32_t * kept_pair;
   double   * kept_id;

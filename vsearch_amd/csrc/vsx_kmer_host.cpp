@@ -352,7 +352,7 @@ namespace {
 std::unique_ptr<KmerScratch> new_scratch()
 {
   std::unique_ptr<KmerScratch> p(new KmerScratch);
-  int prio_low = 0, prio_high = 0;               // counting runs BEHIND the aligner's plans (vsx_host.cpp vsx_create)
+  int prio_low = 0, prio_high = 0;               // counting runs BEHIND the aligner's plans (vsx_context.cpp vsx_create)
   (void) hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
   if (hipStreamCreateWithPriority(&p->st, hipStreamNonBlocking, prio_low) != hipSuccess || hipEventCreate(&p->e0) != hipSuccess ||
       hipEventCreate(&p->e1) != hipSuccess || hipEventCreateWithFlags(&p->e_turn, hipEventDisableTiming) != hipSuccess ||

@@ -20,7 +20,7 @@
 
 extern "C" {
 
-// ---- vsx_host.cpp ------------------------------------------------------------------------------------------------------------
+// ---- vsx_context.cpp, vsx_seqset.cpp -----------------------------------------------------------------------------------------
 // one thread-local error slot for the whole library (vsx_last_error)
 void vsx_internal_set_error(const char * msg);
 const vsx_scoring * vsx_internal_scoring(const vsx_ctx * ctx);

@@ -9,7 +9,7 @@
 //
 // The traceback's epilogue lists the kept pairs with their identities (vsx_device.hip rank_note); the kernel below gathers
 // their statistics / verdict / id / text offset into compact arrays that cross PCIe, and the host puts the few entries in
-// report order (vsx_host.cpp fetch_ranked_lists).
+// report order (vsx_fetch.cpp fetch_ranked_lists).
 #include <hip/hip_runtime.h>
 #include "vsx_internal.h"
 
@@ -31,7 +31,7 @@ vsx_rank_gather_kernel(const u32 * __restrict__ ranked, const double * __restric
 }
 
 // r06: the kept pairs of a ranked plan as the traceback's epilogue listed them (arrival order; VsxFilterDev::kept_pair / kept_id) ->
-// the compact arrays; the host orders the few entries (fetch_ranked_lists, vsx_host.cpp)
+// the compact arrays; the host orders the few entries (fetch_ranked_lists, vsx_fetch.cpp)
 extern "C" hipError_t vsx_rank_gather_list(const uint32_t * d_kept_pair, const double * d_kept_id, uint32_t kept, const VsxPairOut * d_out,
                                            const uint64_t * d_text_off, VsxRankedOut r, hipStream_t st)
 {
