@@ -313,7 +313,8 @@ int vsx_msa_device_batch(vsx_ctx * ctx, uint32_t n_clusters, const uint64_t * cl
    traceback left them; queries above VSX_CHIMERA_MAX_QLEN, and queries with a candidate the 16-bit aligner refused (realigned with
    vsx_lma_align), are answered by a host restatement of the same two functions.  Plus strand only (the reference refuses
    --strand both here).  The de novo forms (--uchime_denovo / uchime2 / uchime3) are vsx_uchime_denovo below, the long-read
-   detector --chimeras_denovo is vsx_chimeras_denovo.  Not covered: --uchimealns / --alnout text. */
+   detector --chimeras_denovo is vsx_chimeras_denovo.  The --uchimealns text of the records of vsx_uchime_ref / vsx_uchime_denovo is
+   a call of its own, declared in vsx_chimalns.h.  Not covered: the --alnout text of --chimeras_denovo. */
 typedef struct vsx_chimera_opts {
   vsx_search_opts search;   /* the searcher's options: masking, hardmask, wordlength, threads, window (of the part search) and the
                                detection parameters id = weak_id = 0.55, maxaccepts 4, maxrejects 16.  As in the reference, the

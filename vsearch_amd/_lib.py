@@ -70,6 +70,10 @@ MASK_SYMBOLS = ["vsx_fastx_mask_opts_default", "vsx_fastx_mask", "vsx_fastx_mask
 GETSEQS_SYMBOLS = ["vsx_getseqs_opts_default", "vsx_getseqs", "vsx_getseqs_out_free", "vsx_getseqs_last_stats"]
 # include/vsx_cut.h
 CUT_SYMBOLS = ["vsx_cut_opts_default", "vsx_cut_pattern_check", "vsx_cut", "vsx_cut_out_free", "vsx_cut_last_stats"]
+# include/vsx_chimalns.h
+CHIMALNS_SYMBOLS = ["vsx_chimalns_opts_default", "vsx_chimera_alns", "vsx_chimalns_out_free", "vsx_chimalns_last_stats",
+                    "vsx_internal_chimalns_host", "vsx_internal_chimalns_device"]
+CHIMALNS_Y, CHIMALNS_BORDERLINE, CHIMALNS_N, CHIMALNS_MAX_COLS = 1, 2, 4, 8192      # VSX_CHIMALNS_*
 CUT_WANT_FWD, CUT_WANT_REV, CUT_WANT_REV_TEXT, CUT_WANT_DISCARDED_REV_TEXT = 1, 2, 4, 8
 CUT_DEVICE_MAX_PATTERN = 64
 MASK_WANT_TEXT, MASK_WANT_BITS = 1, 2                                                    # VSX_MASK_WANT_TEXT / _BITS
@@ -153,6 +157,28 @@ class ChimerasLongResult(C.Structure):
                 ("parent", C.c_uint32 * CHIMERAS_LONG_MAX_PARENTS), ("start", C.c_int32 * CHIMERAS_LONG_MAX_PARENTS),
                 ("len", C.c_int32 * CHIMERAS_LONG_MAX_PARENTS), ("id_query_parent", C.c_double * CHIMERAS_LONG_MAX_PARENTS),
                 ("id_query_top", C.c_double), ("divergence", C.c_double)]
+
+
+class ChimalnsOpts(C.Structure):
+    """vsx_chimalns_opts (include/vsx_chimalns.h)"""
+    _fields_ = [("xn", C.c_double), ("dn", C.c_double), ("alignwidth", C.c_int32), ("select", C.c_uint32), ("window", C.c_int64),
+                ("threads", C.c_int32), ("pad", C.c_int32)]
+
+
+class ChimalnsOut(C.Structure):
+    """vsx_chimalns_out (include/vsx_chimalns.h)"""
+    _fields_ = [("n", C.c_uint64), ("text_bytes", C.c_uint64), ("n_lines", C.c_uint64), ("record", C.POINTER(C.c_uint64)),
+                ("alnlen", C.POINTER(C.c_uint32)), ("text_off", C.POINTER(C.c_uint64)), ("text", C.POINTER(C.c_char)),
+                ("line_first", C.POINTER(C.c_uint64)), ("line_end", C.POINTER(C.c_uint32)), ("best_i", C.POINTER(C.c_int32)),
+                ("h", C.POINTER(C.c_double)), ("counts", C.POINTER(C.c_int32))]
+
+
+class ChimalnsStats(C.Structure):
+    """vsx_chimalns_stats (include/vsx_chimalns.h)"""
+    _fields_ = [("seconds_align", C.c_double), ("seconds_kernel", C.c_double), ("seconds_download", C.c_double),
+                ("seconds_host", C.c_double), ("seconds_total", C.c_double), ("windows", C.c_uint64), ("records_selected", C.c_uint64),
+                ("records_kernel", C.c_uint64), ("records_host", C.c_uint64), ("sentinel_pairs", C.c_uint64),
+                ("host_long_query", C.c_uint64), ("host_long_alignment", C.c_uint64), ("host_forced", C.c_uint64)]
 
 
 class MergeOpts(C.Structure):
@@ -779,6 +805,17 @@ def load():
     lib.vsx_cut_out_free.restype = None
     lib.vsx_cut_last_stats.argtypes = [C.POINTER(CutStats)]
     lib.vsx_cut_last_stats.restype = None
+    lib.vsx_chimalns_opts_default.argtypes = [C.POINTER(ChimalnsOpts)]
+    lib.vsx_chimalns_opts_default.restype = None
+    lib.vsx_chimera_alns.argtypes = [vp, C.POINTER(ChimalnsOpts), C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.POINTER(ChimalnsOut)]
+    lib.vsx_chimalns_out_free.argtypes = [C.POINTER(ChimalnsOut)]
+    lib.vsx_chimalns_out_free.restype = None
+    lib.vsx_chimalns_last_stats.argtypes = [C.POINTER(ChimalnsStats)]
+    lib.vsx_chimalns_last_stats.restype = None
+    lib.vsx_internal_chimalns_host.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p,
+                                               C.POINTER(ChimalnsOpts), C.POINTER(ChimalnsOut)]
+    lib.vsx_internal_chimalns_device.argtypes = [vp, C.c_uint64] + [C.POINTER(C.c_char_p), vp] * 3 + [C.POINTER(C.c_char_p)] * 2 + \
+        [C.POINTER(ChimalnsOpts), C.POINTER(ChimalnsOut)]
     _lib = lib
     return lib
 

@@ -966,6 +966,29 @@ int denovo_window(vsx_searcher * S, VsxDenovo * D, Mode & M, vsx_chimera_denovo_
 
 }  // namespace
 
+// align_pairs for vsx_chimalns.cpp (vsx_private.h): the same call, with buffers the handle owns
+struct VsxRealigned {
+  CallBufs bufs;
+  Aligned aligned;
+};
+
+int vsx_internal_chimera_realign(vsx_searcher * S, const vsx_seqset * qset, const std::vector<uint32_t> & qidx, const std::vector<uint32_t> & tidx,
+                                 const char * who, VsxRealigned ** out)
+{
+  VsxRealigned * R = new VsxRealigned;
+  *out = R;
+  return align_pairs(S, R->bufs, qset, qidx, tidx, who, R->aligned);
+}
+
+void vsx_internal_chimera_realigned_view(const VsxRealigned * R, const VsxPairOut ** hits, const uint32_t ** d_runs, uint64_t * nruns)
+{
+  *hits = R->aligned.hits.data();
+  *d_runs = R->bufs.runs.p;
+  *nruns = R->aligned.nruns;
+}
+
+void vsx_internal_chimera_realigned_free(VsxRealigned * R) { delete R; }
+
 extern "C" {
 
 void vsx_chimera_opts_default(vsx_chimera_opts * o)

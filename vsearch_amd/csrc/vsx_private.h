@@ -96,6 +96,17 @@ int vsx_internal_denovo_search(VsxDenovo * D, const std::vector<uint32_t> & part
                                uint64_t * pairs, uint64_t * sentinels);
 void vsx_internal_denovo_commit(VsxDenovo * D, const std::vector<uint32_t> & seqnos);
 
+// ---- vsx_chimera.cpp ---------------------------------------------------------------------------------------------------------
+// what vsx_chimalns.cpp needs of the detection: (qidx[p] in qset, tidx[p] in the searcher's database) pairs through the detection's
+// own align_pairs, with device buffers that live as long as the handle.  The view: the hit records on the host, the exported run
+// words on the device (stored last column first) and their number.
+struct VsxRealigned;
+struct VsxPairOut;
+int vsx_internal_chimera_realign(vsx_searcher * S, const vsx_seqset * qset, const std::vector<uint32_t> & qidx, const std::vector<uint32_t> & tidx,
+                                 const char * who, VsxRealigned ** out);
+void vsx_internal_chimera_realigned_view(const VsxRealigned * R, const VsxPairOut ** hits, const uint32_t ** d_runs, uint64_t * nruns);
+void vsx_internal_chimera_realigned_free(VsxRealigned * R);
+
 // ---- vsx_exact.cpp -----------------------------------------------------------------------------------------------------------
 // the exact-match index of a searcher (device table + code words, host map), built by the first vsx_search_exact
 struct VsxExactIndex;
