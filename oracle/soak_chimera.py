@@ -20,6 +20,17 @@ probability 0.15, 0.1 (the host restatement answers: the stats must say so).  Co
 --nonchimeras; then the device's records against the host restatement's (VSX_CHIMERA=host).  Coverage: the length class, "parts",
 "diff_pct_host".
 
+--outputs alns (default: off, so a seed's rounds stay byte for byte what they were): every round of the four commands also hands the
+CLI --uchimealns, --chimeras, --nonchimeras and --borderline.  Their options come from a second generator seeded from (seed, round
+number), so the first stream is untouched: --alignwidth 0 / 1 / 60 / 80 / 133 (the reference takes all five), --fasta_score,
+--sizeout / --xsize / --relabel, --fasta_width 0 / 60 / 80; --xn / --dn are the round's.  Compared byte for byte: the four files with
+ChimeraSession / DenovoChimeraSession.uchimealns, chimeras_fasta, nonchimeras_fasta, borderline_fasta; then alns_raw of every scored
+record on the device with VSX_CHIMALNS=host field for field, and vsx_chimalns_last_stats: host_long_query is non-zero exactly when a
+scored query has more than 4 096 symbols (the 3 900-4 200 class), every other record is the kernel's unless one of its pairs is a
+sentinel pair.  Coverage: alns, alignwidth0, alignwidth_other (1 or 133), fasta_score, borderline (that file is not empty),
+alns_host_long (judged from the reference's --uchimeout).  An exception of a library call ends the script with exit status 3:
+nothing more is started on the device.
+
     python oracle/soak_chimera.py --seconds 120 --seed 1 --out soak_chimera.json
 """
 import argparse
@@ -111,6 +122,74 @@ def draw(rng, commands=COMMANDS):
     return cmd, length, o, cli
 
 
+ALIGNWIDTHS = [0, 1, 60, 80, 133]          # (the reference CLI takes each of them: checked with --reference-only)
+ALNS_FILES = ("uchimealns", "chimeras", "nonchimeras", "borderline")
+ALNS_ARRAYS = ("record", "alnlen", "text_off", "text", "line_first", "line_end", "best_i", "h", "counts")
+MAX_QLEN = 4096                            # VSX_CHIMERA_MAX_QLEN: a longer query's block is rendered on the host
+
+
+def draw_alns(r):
+    """--outputs alns -> the options of the four extra files, from the round's own generator; every number is drawn"""
+    w = dict(alignwidth=r.choice(ALIGNWIDTHS), fasta_score=r.random() < 0.5, fasta_width=r.choice([0, 60, 80]))
+    sizeout, xsize, relabel = r.random() < 0.3, r.random() < 0.3, r.random() < 0.3
+    w.update(sizeout=sizeout, xsize=xsize and not sizeout, relabel="C" if relabel else None)      # (the reference refuses the two together)
+    return w
+
+
+def alns_cli(w, tmp):
+    files = {k: os.path.join(tmp, k) for k in ALNS_FILES}
+    cli = ["--alignwidth", str(w["alignwidth"]), "--fasta_width", str(w["fasta_width"])]
+    for k in ALNS_FILES:
+        cli += ["--" + k, files[k]]
+    cli += ["--" + k for k in ("fasta_score", "sizeout", "xsize") if w[k]]
+    return files, cli + (["--relabel", w["relabel"]] if w["relabel"] else [])
+
+
+def alns_diff(ses, src, recs, qlens, w, exp):
+    """the four files against the session's texts, then alns_raw of every scored record on the device against VSX_CHIMALNS=host
+    field for field, and the route counters -> a mismatch record or None"""
+    kw = {k: w[k] for k in ("sizeout", "xsize", "relabel", "fasta_width")}
+    got = dict(uchimealns=ses.uchimealns(*src, records=recs, alignwidth=w["alignwidth"], xsize=w["xsize"]).splitlines(True))
+    for k in ALNS_FILES[1:]:
+        got[k] = [l + "\n" for l in getattr(ses, k + "_fasta")(*src, records=recs, fasta_score=w["fasta_score"], **kw)]
+    for k in ALNS_FILES:
+        if got[k] != exp[k]:
+            first = next((i for i, (x, y) in enumerate(zip(got[k], exp[k])) if x != y), min(len(got[k]), len(exp[k])))
+            return {"what": k, "lines": [len(got[k]), len(exp[k])], "first_diff": first, "got": got[k][first][:300] if first < len(got[k]) else None,
+                    "exp": exp[k][first][:300] if first < len(exp[k]) else None}
+    dev = ses.alns_raw(*src[:1], recs, alignwidth=w["alignwidth"], select="Y?N")
+    os.environ["VSX_CHIMALNS"] = "host"
+    try:
+        host = ses.alns_raw(*src[:1], recs, alignwidth=w["alignwidth"], select="Y?N")
+    finally:
+        del os.environ["VSX_CHIMALNS"]
+    for name, x, y in zip(ALNS_ARRAYS, dev.arrays(), host.arrays()):
+        if x != y:
+            return {"what": f"alns_raw: device and VSX_CHIMALNS=host differ in {name}"}
+    st, hs = dev.stats, host.stats
+    scored = [k for k, r in enumerate(recs) if r["status"] == "scored"]
+    long_queries = sum(qlens[k] > MAX_QLEN for k in scored)
+    if hs["records_host"] != len(scored) or hs["host_forced"] != len(scored) or hs["records_kernel"] != 0:
+        return {"what": "VSX_CHIMALNS=host: the host did not answer every record", "stats": hs}
+    if st["records_selected"] != len(scored) or st["records_kernel"] + st["records_host"] != len(scored) or st["host_forced"] != 0:
+        return {"what": "alns_raw: the counters do not add up to the scored records", "stats": st}
+    if (st["host_long_query"] > 0) != (long_queries > 0) or st["host_long_query"] > long_queries:
+        return {"what": f"alns_raw: {long_queries} scored queries above {MAX_QLEN} symbols, host_long_query says otherwise", "stats": st}
+    if st["records_host"] > st["host_long_query"] + st["host_long_alignment"] + st["sentinel_pairs"] or (long_queries == 0 and st["host_long_alignment"]):
+        return {"what": "alns_raw: records on the host that are neither long nor sentinel pairs", "stats": st}
+    return None
+
+
+def long_scored(uchimeout, seqs_by_label):
+    """does the reference's --uchimeout hold a scored record (it names two parents) of a query above the kernel's limit?"""
+    by_name = {l.split(";")[0]: s for l, s in seqs_by_label.items()}          # (the de novo commands print the label without its ;size=)
+    for line in uchimeout:
+        f = line.split("\t")
+        if f[2] != "*" and f[3] != "*" and len(by_name[f[1].split(";")[0]]) > MAX_QLEN:
+            return True
+    return False
+
+
 def _chimera(rng, parents):
     n = min(len(p) for p in parents)
     cuts = sorted(rng.sample(range(n // 6, n - n // 6), len(parents) - 1))
@@ -153,7 +232,10 @@ def main():
     ap.add_argument("--max-rounds", type=int, default=0, help="stop after this many rounds (0: run for --seconds): a deterministic set of rounds for a given seed")
     ap.add_argument("--reference-only", action="store_true", help="run the reference alone and count its lines (no device)")
     ap.add_argument("--commands", default=",".join(COMMANDS), help="the commands a round draws from, comma-separated (also: chimeras_denovo)")
+    ap.add_argument("--outputs", default="", choices=["", "alns"], help="alns: every round of the four commands also writes and compares "
+                    "--uchimealns, --chimeras, --nonchimeras and --borderline (default: off, so a seed's rounds stay what they were)")
     a = ap.parse_args()
+    alns = a.outputs == "alns"
     commands = a.commands.split(",")
     if not set(commands) <= set(COMMANDS + ["chimeras_denovo"]):
         raise SystemExit(f"--commands: {a.commands}")
@@ -169,6 +251,7 @@ def main():
     ref_seconds = 0.0
     failing = []
     coverage = {}
+    fatal = None
     with tempfile.TemporaryDirectory(prefix="vsxsoakc_") as tmp:
         qf, df, uo = os.path.join(tmp, "q.fa"), os.path.join(tmp, "db.fa"), os.path.join(tmp, "u.tsv")
         while time.time() < t_end and (a.max_rounds <= 0 or rounds < a.max_rounds):
@@ -227,13 +310,19 @@ def main():
                 qn, qs = denovo_data_set(rng, length, div)
                 args = [f"--{cmd}", qf]
             refcli.write_fasta(qf, qn, qs)
+            w, files, alns_args = None, {}, []
+            if alns:                                     # (its own generator per round: the first stream is what it was)
+                w = draw_alns(random.Random(a.seed * 1000003 + rounds))
+                files, alns_args = alns_cli(w, tmp)
             t0 = time.time()
-            p = subprocess.run([refcli.REF_BIN] + args + ["--uchimeout", uo, "--threads", "1", "--quiet"] + cli, capture_output=True, text=True)
+            p = subprocess.run([refcli.REF_BIN] + args + ["--uchimeout", uo, "--threads", "1", "--quiet"] + cli + alns_args, capture_output=True, text=True)
             ref_seconds += time.time() - t0
             rounds += 1
             for key in [f"{cmd}@{length[0]}-{length[1]}"] + [k for k in ("hardmask", "abskew") if k in o]:
                 coverage[key] = coverage.get(key, 0) + 1
             full = [cmd] + cli + [f"length={length}", f"n={len(qs)}"] + [f"{k}={o[k]}" for k in ("window", "search_window") if k in o]
+            if alns:
+                full += [f"{k}={v}" for k, v in w.items()]
             if p.returncode != 0:
                 bad += 1
                 if len(failing) < 10:
@@ -241,28 +330,58 @@ def main():
                 continue
             exp = open(uo).read().splitlines()
             lines += len(exp)
+            exp_alns = {k: open(f).read().splitlines(True) for k, f in files.items()}
+            if alns:
+                lines += sum(len(v) for v in exp_alns.values())
+                for key, hit in (("alns", True), ("alignwidth0", w["alignwidth"] == 0), ("alignwidth_other", w["alignwidth"] in (1, 133)),
+                                 ("fasta_score", w["fasta_score"]), ("borderline", bool(exp_alns["borderline"])),
+                                 ("alns_host_long", long_scored(exp, dict(zip(qn, qs))))):
+                    if hit:
+                        coverage[key] = coverage.get(key, 0) + 1
             if a.reference_only:
                 continue
-            if cmd == "uchime_ref":
-                got = ChimeraSession(al, db, labels=tn, **o).uchimeout(qs, qn)
-            else:
-                got = DenovoChimeraSession(al, qs, qn, variant=cmd.split("_")[0], **o).uchimeout()
-            if got != exp:
+            diff = None
+            try:                                         # any exception of a device call: nothing more is started on the GPU
+                if cmd == "uchime_ref":
+                    ses, src = ChimeraSession(al, db, labels=tn, **o), (qs, qn)
+                    recs = ses.uchime_ref(qs)
+                    got, qlens = ses.uchimeout(qs, qn, records=recs, xsize=bool(alns and w["xsize"])), [len(q) for q in qs]
+                else:
+                    ses, src = DenovoChimeraSession(al, qs, qn, variant=cmd.split("_")[0], **o), ()
+                    recs = ses.uchime_denovo()
+                    got, qlens = ses.uchimeout(recs, xsize=bool(alns and w["xsize"])), [len(q) for q in ses.seqs]
+                if got != exp:
+                    first = next((i for i, (x, y) in enumerate(zip(got, exp)) if x != y), min(len(got), len(exp)))
+                    diff = {"lines": [len(got), len(exp)], "first_diff": first, "got": got[first] if first < len(got) else None,
+                            "exp": exp[first] if first < len(exp) else None}
+                elif alns:
+                    diff = alns_diff(ses, src, recs, qlens, w, exp_alns)
+                ses.close()
+            except Exception as e:
+                fatal = f"{type(e).__name__}: {e}"
+                diff = {"error": fatal[-500:]}
+            if diff is not None:
                 bad += 1
                 if len(failing) < 10:
-                    first = next((i for i, (x, y) in enumerate(zip(got, exp)) if x != y), min(len(got), len(exp)))
-                    failing.append({"cli": full, "round": rounds - 1, "lines": [len(got), len(exp)], "first_diff": first,
-                                    "got": got[first] if first < len(got) else None, "exp": exp[first] if first < len(exp) else None})
-    if al is not None:
+                    failing.append({"cli": full, "round": rounds - 1, **diff})
+            if fatal is not None:
+                break
+    if al is not None and fatal is None:
         al.close()
     out = {"rounds": rounds, "lines": lines, "failing_rounds": bad, "failures": failing, "seed": a.seed, "seconds": a.seconds,
            "reference_seconds": round(ref_seconds, 3), "coverage": coverage,
            "what": "vsx_uchime_ref / vsx_uchime_denovo vs vsearch_ref --uchime_ref / --uchime*_denovo --uchimeout with the same randomly drawn options"
+                   + ("; --uchimealns, --chimeras, --nonchimeras, --borderline vs the sessions' texts, alns_raw on the device vs VSX_CHIMALNS=host" if alns else "")
                    + ("; vsx_chimeras_denovo vs --chimeras_denovo --tabbedout / --chimeras / --nonchimeras, device vs VSX_CHIMERA=host" if "chimeras_denovo" in commands else "")}
+    if fatal is not None:
+        out["fatal"] = fatal[-2000:]
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:
             json.dump(out, f)
+    if fatal is not None:                                # a library error that is no mismatch: exit status 3, and no destructor
+        sys.stdout.flush()                               # touches the device again
+        os._exit(3)
     sys.exit(1 if bad else 0)
 
 

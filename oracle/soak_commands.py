@@ -5,7 +5,8 @@ byte, and of the device route against the library's host restatement, field for 
     --command NAME      one leg of the registry LEGS: filter (--fastq_filter / --fastx_filter), eestats (--fastq_eestats /
                         --fastq_eestats2), fastq_stats (--fastq_stats / --fastq_chars), derep (--derep_fulllength / --fastx_uniques /
                         --derep_id), derep_prefix, search_exact, orient, sintax, otutab (--otutabout / --biomout /
-                        --mothur_shared_out), hitout (the seven hit writers of --usearch_global)
+                        --mothur_shared_out), hitout (the seven hit writers of --usearch_global), mask (--fastx_mask / --maskfasta),
+                        getseqs (--fastx_getseqs / --fastx_getseq / --fastx_getsubseq), cut (--cut)
     --route device|host device: the library on the device against the CLI, then the host restatement against the device result.
                         host: no context is created; the host restatement alone (the route of a call or searcher without a device, or
                         the leg's VSX_<COMMAND>=host) is compared with the CLI.  Needs no GPU.
@@ -16,6 +17,7 @@ number whether or not the option it belongs to is then set (each with probabilit
 does not depend on the choices.  A round the reference refuses counts as failing; a mismatch is recorded and the rounds go on; a
 library error that is no mismatch (VSX_EHIP, a sticky device error, any exception of the device call) ends the script at once with
 exit status 3: nothing is started on a GPU after a fault.  --reference-only counts the reference's lines without the library.
+A leg's `reference` may leave cfg["cover_after"]: coverage classes that only the reference's answer decides.
 
 The legs (data per round; what is drawn beyond the command's own options; the "coverage" classes the output counts):
     filter        100-300 reads of a length in 20 .. 320, in a third of the rounds 63 / 64 / 65 / 127 / 128 / 129 (the kernel walks
@@ -48,6 +50,31 @@ The legs (data per round; what is drawn beyond the command's own options; the "c
                   --rowlen 0 / 1 / 64 / 80, --maxhits, --top_hits_only, --output_no_hits, --id 0.7 / 0.9, --maxaccepts 1 .. 4, window
                   0 / 1 / 7; all seven files, --userout in both field orders, the SAM header.  The host route renders the hit list
                   the CLI itself prints.  hardmask, minus_strand, rowlen0, n_mismatch, window1
+    mask          100-300 sequences of 1 .. 600 symbols with low-complexity islands, lower case, N and IUPAC codes, in a third of the
+                  rounds every length from fastx_mask_data.LENGTHS / SEGMENT_LENGTHS (63 / 64 / 65, 95 / 96 / 97, 191 .. 257), FASTQ 0.3;
+                  the command (--maskfasta 0.3), --qmask, --hardmask, --min_unmasked_pct / --max_unmasked_pct drawn or, in half of the
+                  rounds, the percentages two of the round's own sequences have exactly (py_fastx_mask: the verdict sits on `<` against
+                  `<=`), --sizeout / --xsize / --relabel, --fasta_width 0 / 60 / 80, window 0 / 1 / 7 / 64, scattered blobs with gaps of
+                  A 0.3, the long DUST route forced 0.3 (VSX_MASK_LONG_MIN 1 / 64 / 200, VSX_MASK_SEGMENT 64 / 192 / 256: the counters
+                  must show long sequences).  dust, soft, hardmask, percent_exact, fastq, maskfasta, long_route, length_edge,
+                  discarded (the log counts sequences below AND above the bounds)
+    getseqs       200-600 headers in the style of test_gpu_getseqs.live_reads(), every seventh cut or padded to 63 / 64 / 65 / 127 /
+                  128 / 129 bytes, sequences of 1 .. 60 symbols, FASTQ 0.3 (a FASTA input has the two FASTA files only); 1-40 needles cut
+                  from the round's headers (whole labels, words, pieces across a ; or =, the case swapped in half), misses and one
+                  needle of 63 .. 65 bytes, for the list modes in a labels file with blank lines and no final newline half of the time;
+                  the mode, the command, --label_substr_match, --label_field (word modes), --subseq_start / --subseq_end (the end past
+                  every sequence 0.3), --relabel / --sizeout / --xsize / --sizein, --fasta_width; VSX_GETSEQS_HASH_BITS unset / 3 / 16,
+                  VSX_GETSEQS_MAX_LENGTHS below the distinct needle lengths 0.1 (the host answers: its counter is checked), window,
+                  scattered and shared spans.  The reference takes --fastx_getseq and --fastx_getsubseq with --label alone and the
+                  subsequence options only with the latter, so a round of another mode runs --fastx_getseqs.  one class per mode,
+                  substr, field, subseq, fastq, hash_cut, lengths_host, notmatched (both sides of the split are non-empty)
+    cut           100-300 sequences of 0 .. 600 symbols over ACGT, lower case, N, R, Y, U, one reading of the pattern planted at
+                  cut_data.seeded_set()'s rate, every tenth with it at 0 and at L - P, three of P - 1 / P / P + 1 symbols; a pattern of
+                  2 .. 12 IUPAC symbols with ^ and _ at any two places (one place in either order and both ends included), in a fifth
+                  of the rounds A^A_A or AC^A_CA over planted runs, 0.1 a pattern of 65 .. 70 symbols (the host answers:
+                  host_pattern_length is checked); VSX_CUT_TILE 64 / 128 / unset, the writer options, window, scattered blobs with gaps
+                  of A.  Every result is also held against cut_data.py_cut().  tile_small, iupac_pattern, self_overlap, site_at_end,
+                  short_sequence, pattern_host, discarded (cut and uncut lists both non-empty)
 
     python oracle/soak_commands.py --command filter --seconds 60 --seed 1 --out soak_filter.json
 """
@@ -921,6 +948,396 @@ def hitout_cover(cfg, s):
                              ("n_mismatch", o.get("n_mismatch")), ("window1", cfg["window"] == 1)) if hit]
 
 
+# ---- what mask, getseqs and cut share --------------------------------------------------------------------------------------------
+SMALL_WINDOWS = [0, 1, 7, 64]
+
+
+def writer_opts(rng, o, relabel):
+    """--sizeout / --xsize / --relabel and --fasta_width 0 / 60 / 80 of the FASTA writers"""
+    for flag in ("sizeout", "xsize"):
+        maybe(rng, o, flag, 1)
+    maybe(rng, o, "relabel", relabel)
+    o["fasta_width"] = int(rng.choice([0, 60, 80]))
+    if o.get("sizeout"):
+        o.pop("xsize", None)                             # (the reference refuses the two together)
+
+
+def asserted(fn, *a):
+    """an assert_* helper of tests/*_data.py as a mismatch record, or None"""
+    try:
+        fn(*a)
+    except AssertionError as e:
+        return {"what": f"{fn.__name__}: {str(e)[:400]}"}
+    return None
+
+
+def scattered_labels(labels, seed):
+    """a LabelBlob of the labels in another order with gaps between them; equal labels share one span half of the time"""
+    from vsearch_amd.otutab import LabelBlob
+    rng = random.Random(seed)
+    order = list(range(len(labels)))
+    rng.shuffle(order)
+    off, parts, at, seen = np.zeros(len(labels), np.uint64), [], 0, {}
+    for k in order:
+        if labels[k] in seen and rng.random() < 0.5:
+            off[k] = seen[labels[k]]
+            continue
+        gap = rng.randint(0, 5)
+        parts.append(b"S" * gap + labels[k])
+        off[k] = seen[labels[k]] = at + gap
+        at += gap + len(labels[k])
+    return LabelBlob.of(b"".join(parts) + b";S1", off, [len(l) for l in labels])
+
+
+# ---- mask: --fastx_mask / --maskfasta ------------------------------------------------------------------------------------------------
+MASK_HOST_ROUTES = ("sequences_host_forced", "sequences_host_memory", "sequences_host_long")
+
+
+def mask_draw(rng):
+    o = dict(qmask=MASKS[int(rng.integers(0, 3))])
+    maybe(rng, o, "hardmask", 1)
+    low, high = float(rng.integers(5, 60)), float(rng.integers(60, 100))
+    maybe(rng, o, "min_unmasked_pct", low)
+    maybe(rng, o, "max_unmasked_pct", high)
+    writer_opts(rng, o, "M")
+    cfg = dict(command="maskfasta" if rng.random() < 0.3 else "fastx_mask", n=int(rng.integers(100, 301)), fastq=bool(rng.random() < 0.3),
+               length_edge=bool(rng.random() < 1 / 3), percent_exact=bool(rng.random() < 0.5), window=int(rng.choice(SMALL_WINDOWS)),
+               scattered=bool(rng.random() < 0.3), data_seed=seed_of(rng), layout_seed=seed_of(rng), opts=o)
+    long_min, segment = int(rng.choice([1, 64, 200])), int(rng.choice([64, 192, 256]))
+    cfg["long"] = [long_min, segment] if rng.random() < 0.3 else None
+    cfg["cli"] = dict(o, **{k: cfg[k] for k in ("command", "n", "fastq", "length_edge", "percent_exact", "window", "scattered", "long", "data_seed")})
+    return cfg
+
+
+def mask_data(rng, cfg):
+    """sequences of 1 .. 600 symbols with low-complexity islands, lower-case stretches, N and IUPAC codes; in a third of the rounds
+    every length is one at which the window loop or the long route's segments change shape.  percent_exact: the two bounds ARE the
+    percentages of two of the round's sequences (py_fastx_mask), so that `<` and `<=` part on them"""
+    from tests import fastx_mask_data as md
+    r = random.Random(cfg["data_seed"])
+    kw = dict(alphabet="ACGTacgtNRYU", lower=0.2)
+    if cfg["length_edge"]:
+        seqs = [md.island_seq(r, r.choice(md.LENGTHS + md.SEGMENT_LENGTHS), **kw) for _ in range(cfg["n"])]
+    else:
+        seqs = md.seeded_sequences(cfg["data_seed"], cfg["n"], 1, 600, **kw)
+    labels = [f"s{k}" + (f";size={r.randint(1, 99)}" if r.random() < 0.6 else "") for k in range(len(seqs))]
+    quals = [md.quality(r, len(x)) for x in seqs] if cfg["fastq"] else None
+    o = dict(cfg["opts"])
+    if cfg["percent_exact"]:
+        exact = sorted(100.0 * md.py_fastx_mask([seqs[k]], o["qmask"], o.get("hardmask", 0))["unmasked"][0] / len(seqs[k])
+                       for k in r.sample(range(len(seqs)), 4))
+        o["min_unmasked_pct"], o["max_unmasked_pct"] = exact[1], exact[2]
+        cfg["cli"].update(min_unmasked_pct=exact[1], max_unmasked_pct=exact[2])
+    return md._set(f"soak_{cfg['data_seed']}", seqs, o, labels=labels, quals=quals)
+
+
+def mask_reference(s, cfg):
+    from tests import fastx_mask_data as md
+    ref, seconds = timed(md.run_reference, s, ("maskfasta",) if cfg["command"] == "maskfasta" else ("fasta", "fastq", "log"))
+    counts = {w: int(l.split()[0]) for l in ref.get("log", ()) for w in ("less", "more") if f"with {w} than" in l}
+    cfg["cover_after"] = ["discarded"] if counts.get("less", 0) > 0 and counts.get("more", 0) > 0 else []
+    return ref, seconds, sum(len(v) for v in ref.values() if v is not None)
+
+
+def mask_library(al, s, cfg):
+    from tests import fastx_mask_data as md
+    from vsearch_amd import mask as mk
+    if al is None:
+        return md.call(None, s, window=cfg["window"])
+    long_min, segment = cfg["long"] or (None, None)
+    with environment(VSX_MASK_LONG_MIN=long_min, VSX_MASK_SEGMENT=segment):
+        if cfg["scattered"]:
+            blob = scattered_blob(cfg["layout_seed"], b"A")          # (gaps of A: a window that leaves its sequence meets a run)
+            quals = None if s["quals"] is None else blob(s["quals"])[0]
+            res = mk.fastx_mask(al, blob(s["seqs"]), quals=quals, window=cfg["window"], **md.mask_kw(s))
+        else:
+            res = md.call(al, s, window=cfg["window"])
+    st = res.stats
+    if sum(st[r] for r in MASK_HOST_ROUTES) != 0 or st["sequences"] != len(s["seqs"]):
+        raise Fatal(f"mask: the device route did not answer: {st}")
+    if cfg["long"] and md.full_opts(s["opts"])["qmask"] == "dust" and max(len(x) for x in s["seqs"]) >= long_min:
+        if st["sequences_long"] == 0 or st["segment"] != segment:
+            raise Fatal(f"mask: VSX_MASK_LONG_MIN={long_min} VSX_MASK_SEGMENT={segment}, and no sequence took the long route: {st}")
+    return res
+
+
+def mask_compare(res, s, cfg, ref):
+    from tests import fastx_mask_data as md
+    from vsearch_amd import mask as mk
+    kw, o = md.writer_kw(s), md.full_opts(s["opts"])
+    if cfg["command"] == "maskfasta":
+        return diff_of([("maskfasta", mk.maskfasta_lines(res, s["labels"], **kw), ref["maskfasta"])])
+    pairs = [("fasta", mk.fasta_lines(res, s["labels"], **kw), ref["fasta"]),
+             ("log", mk.log_lines(res, o["min_unmasked_pct"], o["max_unmasked_pct"]), ref["log"])]
+    if s["quals"] is not None:
+        pairs.append(("fastq", mk.fastq_lines(res, s["labels"], **kw), ref["fastq"]))
+    return diff_of(pairs)
+
+
+def mask_same(a, b):
+    from tests import fastx_mask_data as md
+    return asserted(md.assert_same, a, b, "device and host") or first_diff("device and host: bytes", a.tobytes() == b.tobytes(), True)
+
+
+def mask_cover(cfg, s):
+    o, fastx = s["opts"], cfg["command"] == "fastx_mask"
+    return [k for k, hit in (("dust", o["qmask"] == "dust"), ("soft", o["qmask"] == "soft"), ("hardmask", o.get("hardmask")),
+                             ("percent_exact", cfg["percent_exact"] and fastx), ("fastq", cfg["fastq"] and fastx), ("maskfasta", not fastx),
+                             ("long_route", cfg["long"] and o["qmask"] == "dust"), ("length_edge", cfg["length_edge"])) if hit]
+
+
+# ---- getseqs: --fastx_getseqs / --fastx_getseq / --fastx_getsubseq ---------------------------------------------------------------------
+GETSEQS_COMMANDS = ["fastx_getseq", "fastx_getseqs", "fastx_getsubseq"]
+HEADER_EDGES = (63, 64, 65, 127, 128, 129)
+GETSEQS_FIELDS = [None, "sample", "size", "xsample"]
+
+
+def getseqs_draw(rng):
+    """the reference takes --label alone for --fastx_getseq and --fastx_getsubseq, the subsequence options only with the latter, and
+    any one of the four with --fastx_getseqs (checked with --reference-only): another mode than `label` makes the command
+    --fastx_getseqs, and only --fastx_getsubseq carries a subsequence.  --label_field goes with the word modes"""
+    from tests import getseqs_data as gd
+    mode, command = gd.MODES[int(rng.integers(0, 4))], GETSEQS_COMMANDS[int(rng.integers(0, 3))]
+    substr, field = bool(rng.random() < 0.5), GETSEQS_FIELDS[int(rng.integers(0, len(GETSEQS_FIELDS)))]
+    start, span, past = int(rng.integers(1, 40)), int(rng.integers(0, 40)), bool(rng.random() < 0.3)
+    w = {}
+    for flag in ("sizeout", "xsize", "sizein"):
+        maybe(rng, w, flag, True)
+    maybe(rng, w, "relabel", "kept")
+    w["fasta_width"] = int(rng.choice([0, 60, 80]))
+    if w.get("sizeout"):
+        w.pop("xsize", None)
+    if mode != "label":
+        command = "fastx_getseqs"
+    cfg = dict(mode=mode, command=command, substr=substr, field=field if mode.startswith("label_word") else None,
+               subseq=[start, 1000 if past else start + span] if command == "fastx_getsubseq" else None, past_end=past,
+               writer=dict(gd.WRITER_DEFAULTS, **w), n=int(rng.integers(200, 601)), n_needles=int(rng.integers(1, 41)), fastq=bool(rng.random() < 0.3),
+               hash_bits=hash_cut(rng), lengths_host=bool(rng.random() < 0.1), window=int(rng.choice(SMALL_WINDOWS)),
+               scattered=bool(rng.random() < 0.3), data_seed=seed_of(rng), layout_seed=seed_of(rng))
+    cfg["cli"] = dict(w, **{k: cfg[k] for k in ("mode", "command", "substr", "field", "subseq", "n", "n_needles", "fastq", "hash_bits", "lengths_host",
+                                                "window", "scattered", "data_seed")})
+    return cfg
+
+
+def getseqs_needles(r, heads, count):
+    """needles cut from the headers: whole labels, words, pieces across a ';' or '=', the case swapped in half of them; misses; one
+    needle of 63 .. 65 bytes"""
+    import re
+    out = []
+    for _ in range(count):
+        h, x = r.choice(heads), r.random()
+        nd = h
+        if 0.3 <= x < 0.6:
+            nd = r.choice([w for w in re.split(rb"[^0-9A-Za-z]+", h) if w])
+        elif 0.6 <= x < 0.85:
+            marks = [i for i, c in enumerate(h) if c in b";="]
+            if marks:
+                p = r.choice(marks)
+                nd = h[max(0, p - r.randint(1, 4)):p + 1 + r.randint(1, 4)]
+        elif x >= 0.85:
+            nd = b"miss%d" % r.randrange(1000)
+        out.append(nd.swapcase() if r.random() < 0.5 else nd)
+    L = r.choice((63, 64, 65))
+    long = [h for h in heads if len(h) >= L]
+    out.insert(r.randrange(len(out) + 1), r.choice(long)[:L] if long else b"Q" * L)
+    return out
+
+
+def getseqs_data(rng, cfg):
+    """headers in the style of tests/test_gpu_getseqs.live_reads(), every seventh padded to 63 / 64 / 65 / 127 / 128 / 129 bytes;
+    sequences of 1 .. 60 symbols; for the list modes a labels file with blank lines and, half of the time, no final newline"""
+    from tests import getseqs_data as gd
+    r = random.Random(cfg["data_seed"])
+    heads, seqs, quals = [], [], []
+    for k in range(cfg["n"]):
+        name = r.choice((b"read%d" % k, b"OTU_%d" % r.randrange(300), b"otu_%d" % r.randrange(300)))
+        tail = r.choice((b"", b";sample=S%d" % r.randrange(30), b";xsample=S%d;tax=k:B,g:G_%d" % (r.randrange(30), r.randrange(9)),
+                         b";sample=S%dx;size=%d" % (r.randrange(30), r.randrange(1, 50)), b"_S%d;sample=s%d;" % (r.randrange(30), r.randrange(30))))
+        h = b"OTU_7" if k % 97 == 0 else name + tail
+        if k % 7 == 3:
+            L = r.choice(HEADER_EDGES)
+            h = (h + b";pad=" + gd.filler(L))[:L]
+        heads.append(h)
+        L = r.randrange(1, 61)
+        seqs.append("".join(r.choice("ACGT") for _ in range(L)))
+        quals.append("".join(chr(r.randrange(48, 74)) for _ in range(L)))
+    needles = getseqs_needles(r, heads, cfg["n_needles"])
+    raw = None
+    if cfg["mode"] in gd.SINGLE:
+        needles = needles[:1]
+    else:
+        parts = []
+        for nd in needles:
+            parts += [b"", nd] if r.random() < 0.15 else [nd]
+        raw = b"\n".join(parts) + (b"" if r.random() < 0.5 else b"\n")
+        needles = gd.py_read_labels(raw)[0]
+    s = dict(name=f"soak_{cfg['data_seed']}", headers=heads, seqs=seqs, quals=quals if cfg["fastq"] else None, mode=cfg["mode"], needles=needles,
+             raw=raw, substr=cfg["substr"], field=cfg["field"], subseq=tuple(cfg["subseq"]) if cfg["subseq"] else None, writer=cfg["writer"])
+    # the host answers a call with more distinct needle lengths than VSX_GETSEQS_MAX_LENGTHS, unless it compares whole headers
+    distinct = len({len(nd) for nd in needles})
+    exact = cfg["mode"] in ("label", "labels") and not cfg["substr"]
+    s["max_lengths"] = distinct - 1 if cfg["lengths_host"] and distinct >= 2 and not exact else None
+    return s
+
+
+def getseqs_reference(s, cfg):
+    from tests import getseqs_data as gd
+    ref, seconds = timed(gd.run_cli, s["headers"], s["seqs"], s["quals"], s["mode"], s["needles"], s["raw"], s["substr"], s["field"], s["subseq"],
+                         s["writer"], command=cfg["command"])
+    cfg["cover_after"] = ["notmatched"] if ref["fastaout"] and ref["notmatched"] else []
+    return ref, seconds, sum(ref[n].count(b"\n") for n in gd.FILES if ref[n] is not None)
+
+
+def getseqs_library(al, s, cfg):
+    from tests import getseqs_data as gd
+    gs = importlib.import_module("vsearch_amd.getseqs")         # (the package exports the function under the module's name)
+    if al is None:
+        return gd.call(None, s, window=cfg["window"])
+    heads, needles = s["headers"], gd.needles_arg(s)
+    if cfg["scattered"]:
+        heads = scattered_labels(s["headers"], cfg["layout_seed"])
+        if s["mode"] not in gd.SINGLE:
+            needles = scattered_labels(s["needles"], cfg["layout_seed"] + 1)
+    with environment(VSX_GETSEQS_HASH_BITS=cfg["hash_bits"], VSX_GETSEQS_MAX_LENGTHS=s["max_lengths"]):
+        res = gs.getseqs(al, heads, s["seqs"], s["mode"], needles, **dict(gd.call_kw(s), window=cfg["window"]))
+    st, n = res.stats, len(s["headers"])
+    routes = {k: v for k, v in st.items() if k.startswith("host_") and v}
+    if s["max_lengths"] is not None:
+        if routes != {"host_lengths": 1} or (st["headers_host"], st["headers_device"]) != (n, 0):
+            raise Fatal(f"getseqs: VSX_GETSEQS_MAX_LENGTHS={s['max_lengths']}, and the route counters do not say host_lengths: {st}")
+    elif routes or (st["headers_host"], st["headers_device"]) != (0, n):
+        raise Fatal(f"getseqs: the device route did not answer: {st}")
+    return res
+
+
+def getseqs_compare(res, s, cfg, ref):
+    from tests import getseqs_data as gd
+    got = gd.texts(res, s)
+    return diff_of([(n, got[n], gd.as_lines(ref[n])) for n in gd.FILES if ref[n] is not None] + [("log", got["log"], ref["log"])])
+
+
+def getseqs_same(a, b):
+    names = ("matched", "ordinal", "start", "length", "kept", "discarded")
+    return diff_of((f"device and host: {n}", x, y) for n, x, y in zip(names, a.arrays(), b.arrays()))
+
+
+def getseqs_cover(cfg, s):
+    return [cfg["mode"]] + [k for k, hit in (("substr", cfg["substr"] and cfg["mode"] in ("label", "labels")), ("field", cfg["field"] is not None),
+                                             ("subseq", cfg["subseq"]), ("fastq", cfg["fastq"]), ("hash_cut", cfg["hash_bits"]),
+                                             ("lengths_host", s["max_lengths"] is not None)) if hit]
+
+
+# ---- cut: --cut ----------------------------------------------------------------------------------------------------------------------
+CUT_OVERLAPS = ["A^A_A", "AC^A_CA"]
+CUT_BASES = dict(A="A", C="C", G="G", T="T", U="T", R="AG", Y="CT", S="CG", W="AT", K="GT", M="AC", B="CGT", D="AGT", H="ACT", V="ACG", N="ACGT")
+
+
+def marked(body, fwd, rev):
+    """the pattern's symbols with '^' in front of symbol fwd and '_' in front of symbol rev; at one place the order is drawn by the
+    caller (rev < 0: '_' first at -rev - 1)"""
+    first = rev < 0
+    rev = -rev - 1 if first else rev
+    out = []
+    for i in range(len(body) + 1):
+        if i == rev and first:
+            out.append("_")
+        if i == fwd:
+            out.append("^")
+        if i == rev and not first:
+            out.append("_")
+        if i < len(body):
+            out.append(body[i])
+    return "".join(out)
+
+
+def cut_draw(rng):
+    from tests import cut_data as cd
+    symbols = "".join(cd.IUPAC[int(i)] for i in rng.integers(0, len(cd.IUPAC), 70))
+    plen, long_len = int(rng.integers(2, 13)), int(rng.integers(65, 71))
+    at = [float(x) for x in rng.random(2)]
+    underscore_first, kind, overlap = bool(rng.random() < 0.5), float(rng.random()), CUT_OVERLAPS[int(rng.integers(0, 2))]
+    if kind < 0.2:
+        pattern = overlap
+    else:
+        body = symbols[:long_len if kind < 0.3 else plen]
+        fwd, rev = (int(x * (len(body) + 1)) for x in at)            # any two places, both ends and one place for both included
+        pattern = marked(body, fwd, -rev - 1 if underscore_first else rev)
+    o = {}
+    writer_opts(rng, o, "F")
+    tile = [64, 128, None][int(rng.integers(0, 3))]
+    cfg = dict(pattern=pattern, self_overlap=kind < 0.2, n=int(rng.integers(100, 301)), tile=tile, window=int(rng.choice(SMALL_WINDOWS)),
+               scattered=bool(rng.random() < 0.3), data_seed=seed_of(rng), layout_seed=seed_of(rng), opts=o)
+    cfg["cli"] = dict(o, **{k: cfg[k] for k in ("pattern", "n", "tile", "window", "scattered", "data_seed")})
+    return cfg
+
+
+def cut_data(rng, cfg):
+    """sequences of 0 .. 600 symbols over ACGT, lower case, N, R, Y and U with one concrete reading of the pattern planted at
+    cut_data.seeded_set()'s rate (for the self-overlapping patterns a run of A or of AC); every tenth carries it at 0 and at L - P;
+    three have P - 1, P and P + 1 symbols"""
+    from tests import cut_data as cd
+    r = random.Random(cfg["data_seed"])
+    body = cd.py_pattern(cfg["pattern"])[0]
+    P = len(body)
+    site = "".join(r.choice(CUT_BASES[c]) for c in body)
+    if cfg["self_overlap"]:
+        site = ("A" * 9 if body == "AAA" else "AC" * 5 + "A")[:r.randint(P, 11)]
+    seqs = cd.seeded_set(cfg["data_seed"], cfg["n"], 0, 600, "ACGTacgtNRYU", site_rate=0.01, site=site)
+    for k in range(5, len(seqs), 10):
+        if len(seqs[k]) >= len(site):
+            seqs[k] = site + seqs[k][len(site):len(seqs[k]) - len(site)] + site if len(seqs[k]) >= 2 * len(site) else site
+    for k, L in zip(r.sample(range(len(seqs)), 3), (P - 1, P, P + 1)):
+        seqs[k] = (site + "A")[:L] if L > P else site[:L]
+    labels = [f"s{k}" + (f";size={r.randint(1, 99)}" if r.random() < 0.6 else "") for k in range(len(seqs))]
+    return cd._set(f"soak_{cfg['data_seed']}", seqs, cfg["pattern"], cfg["opts"], labels=labels)
+
+
+def cut_reference(s, cfg):
+    from tests import cut_data as cd
+    ref, seconds = timed(cd.run_cli, s)
+    words = ref["log"].split()                           # "%d sequence(s) cut %d times, %d sequence(s) never cut."
+    cfg["cover_after"] = ["discarded"] if int(words[0]) > 0 and int(words[5]) > 0 else []
+    return ref, seconds, sum(ref[w].count("\n") for w in cd.WHICH)
+
+
+def cut_library(al, s, cfg):
+    from tests import cut_data as cd
+    from vsearch_amd.cut import cut
+    if al is None:
+        return cd.call(None, s, window=cfg["window"])
+    with environment(VSX_CUT_TILE=cfg["tile"]):
+        seqs = scattered_blob(cfg["layout_seed"], b"A")(s["seqs"]) if cfg["scattered"] else s["seqs"]     # (gaps any pattern of A matches)
+        res = cut(al, seqs, s["pattern"], window=cfg["window"])
+    st = res.stats
+    host = len(cd.py_pattern(s["pattern"])[0]) > 64
+    if [st[r] for r in cd.HOST_ROUTES] != [0, 0, 0, 0, int(host)] or (not host and st["tile"] != (cfg["tile"] or st["tile"])):
+        raise Fatal(f"cut: the route counters do not fit a pattern of {st['pattern_length']} symbols and VSX_CUT_TILE={cfg['tile']}: {st}")
+    return res
+
+
+def cut_compare(res, s, cfg, ref):
+    from tests import cut_data as cd
+    from vsearch_amd.cut import log_lines
+    return asserted(cd.assert_equals_py, res, s) or \
+        diff_of([(w, cd.lib_text(res, s, w).splitlines(), ref[w].splitlines()) for w in cd.WHICH] +
+                [("bytes", [cd.lib_text(res, s, w) for w in cd.WHICH], [ref[w] for w in cd.WHICH]), ("log", log_lines(res), [ref["log"]])])
+
+
+def cut_same(a, b):
+    from tests import cut_data as cd
+    return asserted(cd.assert_same, a, b, "device and host") or first_diff("device and host: bytes", a.tobytes() == b.tobytes(), True)
+
+
+def cut_cover(cfg, s):
+    from tests import cut_data as cd
+    body = cd.py_pattern(s["pattern"])[0]
+    P, coded = len(body), [cd.code4(c) for c in body]
+    at_end = any(len(x) >= P and all(coded[j] & cd.code4(x[len(x) - P + j]) for j in range(P)) for x in s["seqs"])
+    return [k for k, hit in (("tile_small", cfg["tile"] == 64), ("iupac_pattern", any(c.upper() not in "ACGT" for c in body)),
+                             ("self_overlap", cfg["self_overlap"]), ("site_at_end", at_end),
+                             ("short_sequence", any(P - 1 <= len(x) <= P + 1 for x in s["seqs"])), ("pattern_host", P > 64)) if hit]
+
+
 # ---- the registry -------------------------------------------------------------------------------------------------------------------
 def leg(name, host_env, what, **fn):
     g = globals()
@@ -945,6 +1362,11 @@ LEGS = {l.name: l for l in (
     leg("otutab", "VSX_OTUTAB", "vsx_otutab vs vsearch_ref --search_exact --otutabout --mothur_shared_out --biomout"),
     leg("hitout", "VSX_HITOUT", "vsx_hits_render vs vsearch_ref --usearch_global: alnout, samout (and its header), blast6out, fastapairs, "
         "qsegout, tsegout, userout in both field orders"),
+    leg("mask", "VSX_MASK", "vsx_fastx_mask vs vsearch_ref --fastx_mask (fastaout, fastqout, the closing log lines) / --maskfasta --output"),
+    leg("getseqs", "VSX_GETSEQS", "vsx_getseqs vs vsearch_ref --fastx_getseqs / --fastx_getseq / --fastx_getsubseq: fastaout, fastqout, "
+        "notmatched, notmatchedfq, the log line"),
+    leg("cut", "VSX_CUT", "vsx_cut vs vsearch_ref --cut: fastaout, fastaout_rev, fastaout_discarded, fastaout_discarded_rev, the log line; "
+        "and vs cut_data.py_cut()"),
 )}
 
 
@@ -1001,6 +1423,8 @@ def main():
             continue
         ref_seconds += seconds
         lines += n
+        for key in cfg.get("cover_after", ()):          # (classes only the reference's answer decides)
+            coverage[key] = coverage.get(key, 0) + 1
         if a.reference_only:
             continue
         if al is not None:

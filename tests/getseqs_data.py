@@ -421,11 +421,13 @@ def assert_equals_py(res, s):
 
 
 def sizes_of(s):
+    """the abundance --sizeout prints: the header's ;size= annotation, WITH OR WITHOUT --sizein (fastx_get_abundance reads the header
+    itself; found by oracle/soak_commands.py --command getseqs), 1 where there is none"""
     import re
     out = []
     for h in s["headers"]:
         m = re.search(rb"(?:^|;)size=(\d+)(?:;|$)", h)
-        out.append(int(m.group(1)) if (m and s["writer"]["sizein"]) else 1)
+        out.append(int(m.group(1)) if m else 1)
     return out
 
 
@@ -434,9 +436,10 @@ def texts(res, s):
     gs = importlib.import_module("vsearch_amd.getseqs")
     w = s["writer"]
     kw = dict(sizes=sizes_of(s), sizeout=w["sizeout"], xsize=w["xsize"], relabel=w["relabel"], fasta_width=w["fasta_width"])
+    fastq = s["quals"] is not None                                       # (a FASTA input has no FASTQ files: None)
     return dict(fastaout=gs.fasta_lines(res, s["headers"], s["seqs"], True, **kw), notmatched=gs.fasta_lines(res, s["headers"], s["seqs"], False, **kw),
-                fastqout=gs.fastq_lines(res, s["headers"], s["seqs"], s["quals"], True, **kw),
-                notmatchedfq=gs.fastq_lines(res, s["headers"], s["seqs"], s["quals"], False, **kw), log=gs.log_lines(res))
+                fastqout=gs.fastq_lines(res, s["headers"], s["seqs"], s["quals"], True, **kw) if fastq else None,
+                notmatchedfq=gs.fastq_lines(res, s["headers"], s["seqs"], s["quals"], False, **kw) if fastq else None, log=gs.log_lines(res))
 
 
 def device_digest(aligner):
@@ -459,16 +462,24 @@ FILES = ("fastaout", "fastqout", "notmatched", "notmatchedfq")
 
 
 def run_cli(headers, seqs, quals, mode, needles, raw, substr, field, subseq, writer, command=None):
-    """the reference CLI on a FASTQ file of the reads -> dict(fastaout, fastqout, notmatched, notmatchedfq: bytes; log: the line)"""
+    """the reference CLI on a FASTQ file of the reads -> dict(fastaout, fastqout, notmatched, notmatchedfq: bytes; log: the line).
+    quals=None: a FASTA file, and only the two FASTA outputs (the two FASTQ files are None)"""
     with tempfile.TemporaryDirectory(prefix="vsx_getseqs_") as tmp:
         p = lambda n: os.path.join(tmp, n)  # noqa: E731
-        with open(p("in.fq"), "wb") as f:
-            for h, sq, q in zip(headers, seqs, quals):
-                f.write(b"@" + h + b"\n" + B(sq) + b"\n+\n" + B(q) + b"\n")
+        fastq = quals is not None
+        source = p("in.fq" if fastq else "in.fa")
+        with open(source, "wb") as f:
+            if fastq:
+                for h, sq, q in zip(headers, seqs, quals):
+                    f.write(b"@" + h + b"\n" + B(sq) + b"\n+\n" + B(q) + b"\n")
+            else:
+                for h, sq in zip(headers, seqs):
+                    f.write(b">" + h + b"\n" + B(sq) + b"\n")
+        files = FILES if fastq else ("fastaout", "notmatched")
         if command is None:
             command = "fastx_getsubseq" if subseq else "fastx_getseqs"
-        args = [ref_binary(), "--" + command, p("in.fq"), "--log", p("log.txt"), "--quiet"]
-        for n in FILES:
+        args = [ref_binary(), "--" + command, source, "--log", p("log.txt"), "--quiet"]
+        for n in files:
             args += ["--" + n, p(n)]
         if mode in SINGLE:
             args += ["--" + mode, needles[0]]
@@ -492,7 +503,7 @@ def run_cli(headers, seqs, quals, mode, needles, raw, substr, field, subseq, wri
         r = subprocess.run(args, capture_output=True)
         if r.returncode != 0:
             raise RuntimeError("reference CLI failed: " + r.stderr.decode("latin-1")[-2000:])
-        out = {n: open(p(n), "rb").read() for n in FILES}
+        out = {n: open(p(n), "rb").read() if n in files else None for n in FILES}
         out["log"] = [l for l in open(p("log.txt"), encoding="latin-1").read().splitlines() if "sequences extracted" in l]
         out["warned"] = "Labels longer than 1023" in open(p("log.txt"), encoding="latin-1").read()
         return out

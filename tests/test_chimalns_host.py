@@ -176,3 +176,28 @@ def test_abi_surface_and_refusals(explicit):
     o.select = 0
     assert lib.vsx_chimera_alns(None, C.byref(o), 0, None, 0, None, None, None, C.byref(res)) == _lib.VSX_EINVAL
     lib.vsx_chimalns_out_free(C.byref(res))
+
+
+def test_uchimeout_strips_the_size_annotation_under_xsize(tmp_path):
+    """found by oracle/soak_chimera.py --outputs alns: with --xsize the reference prints all four labels of a --uchimeout line
+    without their ;size= annotation (header_fprint_strip); format_uchimeout and the sessions' uchimeout() took no xsize.  The
+    "no parents" lines are held against the reference CLI's own for the de novo set where its binary is present."""
+    from oracle import refcli
+    from vsearch_amd.chimera import format_uchimeout
+    rec = dict(status="scored", score=1.25, parent_a=0, parent_b=1, closest=1, id_query_model=99.0, id_query_a=95.5, id_query_b=96.0, id_a_b=92.0,
+               id_query_top=96.0, left_yes=5, left_no=0, left_abstain=1, right_yes=4, right_no=1, right_abstain=0, divergence=3.0, flag="Y")
+    names = ["a;size=9", "b;size=7;"]
+    tail = "\t99.0\t95.5\t96.0\t92.0\t96.0\t5\t0\t1\t4\t1\t0\t3.0\tY"
+    assert format_uchimeout(rec, "q;size=3", names) == "1.2500\tq;size=3\ta;size=9\tb;size=7;\tb;size=7;" + tail
+    assert format_uchimeout(rec, "q;size=3", names, xsize=True) == "1.2500\tq\ta\tb\tb" + tail
+    none = dict(rec, status="no_parents")
+    assert format_uchimeout(none, "q;size=3", names, xsize=True).startswith("0.0000\tq\t*\t")
+    if refcli.available():
+        labels, seqs = data.denovo_set()
+        f, out = str(tmp_path / "in.fa"), str(tmp_path / "u.tsv")
+        refcli.write_fasta(f, labels, seqs)
+        refcli.run(["--uchime_denovo", f, "--uchimeout", out, "--xsize", "--threads", "1", "--quiet"])
+        lines = open(out).read().splitlines()
+        assert len(lines) == len(labels) and not any(";size=" in l for l in lines)
+        plain = [l for l in lines if l.split("\t")[2] == "*"]
+        assert len(plain) >= 3 and set(plain) <= {format_uchimeout(none, l, labels, xsize=True) for l in labels}

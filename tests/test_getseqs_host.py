@@ -80,6 +80,21 @@ def test_writers_against_the_recorded_cli(host_results):
         gs.fastq_lines(host_results[s["name"]], s["headers"], s["seqs"], None)
 
 
+def test_sizeout_prints_the_annotation_without_sizein():
+    """found by oracle/soak_commands.py --command getseqs: the three commands hand the writers fastx_get_abundance(), which reads
+    the header's ;size= annotation whether or not --sizein is given; sizes_of() used to give 1 without --sizein.  The expected
+    text is the reference CLI's own for this input, with and without --sizein."""
+    want = dict(fastaout=[">a;size=5", "AC"], notmatched=[">b;size=1", "CGT"])
+    for sizein in (False, True):
+        s = gd._set("annotated", [b"a;size=5", b"b"], "label", b"A;SIZE=5", seq_lengths=[2, 3], sizeout=True, sizein=sizein)
+        assert gd.sizes_of(s) == [5, 1]
+        got = gd.texts(gd.call(None, s), s)
+        assert {k: got[k] for k in want} == want
+        if os.path.exists(gd.ref_binary()):
+            ref = gd.run_reference(s)
+            assert {k: gd.as_lines(ref[k]) for k in want} == want
+
+
 def test_log_line_without_sequences():
     res = gs.getseqs_host([], [], "labels", [b"x"])
     assert gs.log_lines(res) == ["0 of 0 sequences extracted"] and res.n == 0 and res.arrays()[4:] == (0, 0)

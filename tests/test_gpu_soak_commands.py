@@ -1,8 +1,10 @@
 """-m gpu: a short, seeded run of the randomized soaks of the newer commands (oracle/soak_merge.py: --fastq_mergepairs with random
 quality encodings, options, read lengths and windows; oracle/soak_chimera.py: --uchime_ref and the three de novo variants with random
 lengths, masks and parameters, and --chimeras_denovo behind --commands; oracle/soak_commands.py: one leg per command added since --
-filter, eestats, fastq_stats, derep, derep_prefix, search_exact, orient, sintax, otutab, hitout) against the reference CLI, as
-tests/test_gpu_soak.py runs the older ones.
+filter, eestats, fastq_stats, derep, derep_prefix, search_exact, orient, sintax, otutab, hitout, mask, getseqs, cut; and
+oracle/soak_chimera.py --outputs alns: --uchimealns at --alignwidth 0 / 1 / 60 / 80 / 133 with the --chimeras / --nonchimeras /
+--borderline FASTA writers beside every round of the four chimera commands) against the reference CLI, as tests/test_gpu_soak.py
+runs the older ones.
 
 The floors are the reference's own line counts for the seed and the round count (`--reference-only`, no device), rounded down to
 two significant digits.  The round counts keep the reference CLI's share of a case below 5 s (measured: 0.5 s for the 40 merge
@@ -18,6 +20,14 @@ reference refuses none of them.
 Found by oracle/soak_commands.py and kept as ordinary tests beside the command's own:
   - otutab: the reference's search commands count the header's ;size= annotation in the OTU table with or without --sizein;
     tests/otutab_data.inputs() counted 1 per query without it (tests/test_otutab_host.py::test_annotated_abundance_counts_without_sizein)
+  - getseqs: --fastx_getseqs / --fastx_getseq / --fastx_getsubseq print the header's ;size= annotation under --sizeout with or
+    without --sizein; tests/getseqs_data.sizes_of() gave 1 without it -- a wrong expectation of the tests' restatement, the library's
+    writers print what they are handed (tests/test_getseqs_host.py::test_sizeout_prints_the_annotation_without_sizein)
+Found by oracle/soak_chimera.py --outputs alns:
+  - --uchimeout under --xsize: the reference strips the ;size= annotation from the query's, both parents' and the closest parent's
+    label; format_uchimeout() and the sessions' uchimeout() took no xsize and printed the labels whole.  They take it now
+    (tests/test_chimalns_host.py::test_uchimeout_strips_the_size_annotation_under_xsize)
+The mask and cut legs found no mismatch.
 """
 import json
 import os
@@ -41,7 +51,12 @@ MUST = {
     "sintax": ("strand_both", "cutoff", "wl_lt_8", "wl_host"),
     "otutab": ("hash_cut", "biom", "mothur"),
     "hitout": ("hardmask", "minus_strand", "rowlen0", "n_mismatch", "window1"),
+    "mask": ("dust", "soft", "hardmask", "percent_exact", "fastq", "maskfasta", "long_route", "length_edge", "discarded"),
+    "getseqs": ("label", "labels", "label_word", "label_words", "substr", "field", "subseq", "fastq", "hash_cut", "lengths_host", "notmatched"),
+    "cut": ("tile_small", "iupac_pattern", "self_overlap", "site_at_end", "short_sequence", "pattern_host", "discarded"),
 }
+# oracle/soak_chimera.py --outputs alns: the classes of the four extra files, beside those every chimera case holds
+ALNS_MUST = ("alns", "alignwidth0", "alignwidth_other", "fasta_score", "borderline", "alns_host_long", "hardmask", "abskew")
 CHIMERAS_DENOVO_MUST = ("chimeras_denovo@1900-2200", "diff_pct_host", "parts")
 TIME_LIMIT = 600
 
@@ -88,6 +103,9 @@ def test_seeded_soak(gpu_required, tmp_path, script, seed, rounds, floor, must):
     ("sintax", 20261020, 40, 5_800),            # 5 817 lines, 3.3 s, 4.4 s
     ("otutab", 20261020, 40, 7_500),            # 7 564 lines, 0.24 s, 0.7 s
     ("hitout", 20261020, 28, 1_900_000),        # 1 935 410 lines (rowlen 1: a line per column), 4.6 s (30 rounds: 5.4 s), 6.6 s
+    ("mask", 20261020, 40, 23_000),             # 23 532 lines, 0.42 s, 1.6 s
+    ("getseqs", 20261021, 40, 56_000),          # 56 523 lines, 0.21 s, 1.1 s (20261020 holds no lengths_host round)
+    ("cut", 20261020, 40, 760_000),             # 765 445 lines (a pattern of two IUPAC symbols cuts everywhere), 0.41 s, 3.9 s
 ])
 def test_seeded_soak_of_a_command(gpu_required, tmp_path, leg, seed, rounds, floor):
     run_soak(tmp_path, "soak_commands.py", ("--command", leg), seed, rounds, floor, MUST[leg])
@@ -96,3 +114,9 @@ def test_seeded_soak_of_a_command(gpu_required, tmp_path, leg, seed, rounds, flo
 def test_seeded_soak_of_chimeras_denovo(gpu_required, tmp_path):
     """5 rounds: 249 lines (--tabbedout + the labels of --chimeras and --nonchimeras), 4.4 s of the reference (6 rounds: 6.0 s), 4.5 s on the MI355X"""
     run_soak(tmp_path, "soak_chimera.py", ("--commands", "chimeras_denovo"), 20261021, 5, 240, CHIMERAS_DENOVO_MUST)
+
+
+def test_seeded_soak_of_uchimealns_and_the_fasta_writers(gpu_required, tmp_path):
+    """10 rounds of the four chimera commands with --outputs alns: 160 353 lines (--uchimeout, --uchimealns -- one block line per column
+    at --alignwidth 1 --, --chimeras, --nonchimeras, --borderline), 2.9 s of the reference (11 rounds: 5.3 s), 3.6 s on the MI355X"""
+    run_soak(tmp_path, "soak_chimera.py", ("--outputs", "alns"), 20261133, 10, 160_000, ALNS_MUST)

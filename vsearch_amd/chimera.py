@@ -37,13 +37,14 @@ STATUS = {0: "no_parents", 1: "no_alignment", 2: "scored"}
 _SEARCH_KEYS = ("soft_mask", "qmask", "hardmask", "wordlength", "minwordmatches", "threads")
 
 
-def format_uchimeout(rec, qname, tnames):
+def format_uchimeout(rec, qname, tnames, xsize=False):
     """one --uchimeout line (without the newline): a scored query as eval_parents prints it (chimera.cpp:1810-1875), any other as the
-    "no parents" line of :2320-2340"""
+    "no parents" line of :2320-2340.  xsize: --xsize, which strips the ;size= annotation from all four labels (header_fprint_strip)"""
     if rec["status"] != "scored":
-        return "%.4f\t%s\t*\t*\t*\t*\t*\t*\t*\t*\t0\t0\t0\t0\t0\t0\t*\tN" % (0.0, qname)
+        return "%.4f\t%s\t*\t*\t*\t*\t*\t*\t*\t*\t0\t0\t0\t0\t0\t0\t*\tN" % (0.0, _strip(qname, xsize))
     return "%.4f\t%s\t%s\t%s\t%s\t%.1f\t%.1f\t%.1f\t%.1f\t%.1f\t%d\t%d\t%d\t%d\t%d\t%d\t%.1f\t%s" % (
-        rec["score"], qname, tnames[rec["parent_a"]], tnames[rec["parent_b"]], tnames[rec["closest"]],
+        rec["score"], _strip(qname, xsize), _strip(tnames[rec["parent_a"]], xsize), _strip(tnames[rec["parent_b"]], xsize),
+        _strip(tnames[rec["closest"]], xsize),
         rec["id_query_model"], rec["id_query_a"], rec["id_query_b"], rec["id_a_b"], rec["id_query_top"],
         rec["left_yes"], rec["left_no"], rec["left_abstain"], rec["right_yes"], rec["right_no"], rec["right_abstain"],
         rec["divergence"], rec["flag"])
@@ -304,13 +305,13 @@ class ChimeraSession(_Writers):
             recs.append(d)
         return recs
 
-    def uchimeout(self, queries, qnames=None, tnames=None, records=None):
-        """--uchimeout lines in query order (what the reference CLI writes with --threads 1)"""
+    def uchimeout(self, queries, qnames=None, tnames=None, records=None, xsize=False):
+        """--uchimeout lines in query order (what the reference CLI writes with --threads 1); xsize as --xsize"""
         if records is None:
             records = self.uchime_ref(queries)
         qnames = qnames or [f"q{i}" for i in range(len(queries))]
         tnames = tnames or self.labels or [f"t{i}" for i in range(len(self.db))]
-        return [format_uchimeout(r, qn, tnames) for r, qn in zip(records, qnames)]
+        return [format_uchimeout(r, qn, tnames, xsize) for r, qn in zip(records, qnames)]
 
     def _source(self, queries, qnames=None, records=None):
         qnames = qnames or [f"q{i}" for i in range(len(queries))]
@@ -470,11 +471,11 @@ class DenovoChimeraSession(_Writers):
         self._records = _records(out, n)
         return self._records
 
-    def uchimeout(self, records=None):
-        """--uchimeout lines in processing order (what the reference CLI writes)"""
+    def uchimeout(self, records=None, xsize=False):
+        """--uchimeout lines in processing order (what the reference CLI writes); xsize as --xsize"""
         if records is None:
             records = self._records if self._records is not None else self.uchime_denovo()
-        return [format_uchimeout(r, qn, self.labels) for r, qn in zip(records, self.labels)]
+        return [format_uchimeout(r, qn, self.labels, xsize) for r, qn in zip(records, self.labels)]
 
     def nonchimeras(self, records=None):
         """input indices of the sequences whose status is below suspicious (neither 'Y' nor '?'), in processing order"""
