@@ -74,6 +74,10 @@ CUT_SYMBOLS = ["vsx_cut_opts_default", "vsx_cut_pattern_check", "vsx_cut", "vsx_
 CHIMALNS_SYMBOLS = ["vsx_chimalns_opts_default", "vsx_chimera_alns", "vsx_chimalns_out_free", "vsx_chimalns_last_stats",
                     "vsx_internal_chimalns_host", "vsx_internal_chimalns_device"]
 CHIMALNS_Y, CHIMALNS_BORDERLINE, CHIMALNS_N, CHIMALNS_MAX_COLS = 1, 2, 4, 8192      # VSX_CHIMALNS_*
+# include/vsx_sortby.h
+SORTBY_SYMBOLS = ["vsx_sortby_opts_default", "vsx_sortby", "vsx_sortby_out_free", "vsx_sortby_last_stats"]
+SORTBY_SIZE, SORTBY_LENGTH, SORTBY_LENGTH_ASC = 0, 1, 2                                 # VSX_SORTBY_*
+SORTBY_MAX_ROUNDS, SORTBY_STAT_ROUNDS = 32, 8
 CUT_WANT_FWD, CUT_WANT_REV, CUT_WANT_REV_TEXT, CUT_WANT_DISCARDED_REV_TEXT = 1, 2, 4, 8
 CUT_DEVICE_MAX_PATTERN = 64
 MASK_WANT_TEXT, MASK_WANT_BITS = 1, 2                                                    # VSX_MASK_WANT_TEXT / _BITS
@@ -413,6 +417,26 @@ class CutStats(C.Structure):
                                           "seconds_output", "seconds_total")] + \
                [(n, C.c_uint64) for n in ("sequences", "symbols", "blocks", "items", "tile", "pattern_length", "host_no_context",
                                           "host_environment", "host_count", "host_memory", "host_pattern_length")]
+
+
+class SortbyOpts(C.Structure):
+    """vsx_sortby_opts (include/vsx_sortby.h)"""
+    _fields_ = [("order", C.c_int32), ("threads", C.c_int32), ("minsize", C.c_int64), ("maxsize", C.c_int64), ("topn", C.c_int64)]
+
+
+class SortbyOut(C.Structure):
+    """vsx_sortby_out (include/vsx_sortby.h)"""
+    _fields_ = [("n", C.c_uint64), ("n_kept", C.c_uint64), ("n_out", C.c_uint64), ("order", C.c_void_p), ("median", C.c_double)]
+
+
+class SortbyStats(C.Structure):
+    """vsx_sortby_stats (include/vsx_sortby.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_stage", "seconds_h2d", "seconds_numeric", "seconds_refine", "seconds_host_finish",
+                                          "seconds_output", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("items", "kept", "label_bytes", "rounds", "max_rounds", "active_numeric")] + \
+               [("active", C.c_uint64 * SORTBY_STAT_ROUNDS)] + \
+               [(n, C.c_uint64) for n in ("capped_items", "host_no_context", "host_environment", "host_count", "host_memory",
+                                          "host_long_prefix")]
 
 
 class HitoutOpts(C.Structure):
@@ -816,6 +840,13 @@ def load():
                                                C.POINTER(ChimalnsOpts), C.POINTER(ChimalnsOut)]
     lib.vsx_internal_chimalns_device.argtypes = [vp, C.c_uint64] + [C.POINTER(C.c_char_p), vp] * 3 + [C.POINTER(C.c_char_p)] * 2 + \
         [C.POINTER(ChimalnsOpts), C.POINTER(ChimalnsOut)]
+    lib.vsx_sortby_opts_default.argtypes = [C.POINTER(SortbyOpts)]
+    lib.vsx_sortby_opts_default.restype = None
+    lib.vsx_sortby.argtypes = [vp, C.POINTER(SortbyOpts), C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(SortbyOut)]
+    lib.vsx_sortby_out_free.argtypes = [C.POINTER(SortbyOut)]
+    lib.vsx_sortby_out_free.restype = None
+    lib.vsx_sortby_last_stats.argtypes = [C.POINTER(SortbyStats)]
+    lib.vsx_sortby_last_stats.restype = None
     _lib = lib
     return lib
 

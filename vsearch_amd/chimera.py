@@ -26,6 +26,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import sortby as _sortby
 from ._lib import (ChimeraDenovoOpts, ChimeraDenovoStats, ChimeraOpts, ChimeraResult, ChimerasLongOpts, ChimerasLongResult, ChimeraStats,
                    check)
 from .derep import strip_size
@@ -387,6 +388,15 @@ def sort_by_abundance(sizes, labels):
     return sorted(range(len(labels)), key=lambda i: (-sizes[i], keys[i], i))
 
 
+def _abundance_order(aligner, sizes, labels, lengths):
+    """sort_by_abundance's list from the aligner's device (vsx_sortby, vsearch_amd/sortby.py).  What that call refuses -- an abundance
+    the reference's unsigned int cannot hold, a header with a NUL byte -- is sorted here, by the same rule."""
+    keys = [l.encode() if isinstance(l, str) else bytes(l) for l in labels]
+    if any(v > 0xFFFFFFFF for v in sizes) or any(b"\0" in k for k in keys):
+        return sort_by_abundance(sizes, labels)
+    return _sortby.db_order(aligner, keys, lengths, sizes, _lib.SORTBY_SIZE)
+
+
 def denovo_default_opts(variant="uchime"):
     """vsx_chimera_denovo_opts_default as a ChimeraDenovoOpts structure"""
     o = ChimeraDenovoOpts()
@@ -431,7 +441,7 @@ class DenovoChimeraSession(_Writers):
         keep = [i for i, s in enumerate(seqs) if minseqlength <= len(s) <= maxseqlength]
         sizes = {i: header_size(labels[i]) for i in keep}
         kl = [labels[i] for i in keep]
-        self.order = [keep[j] for j in sort_by_abundance([sizes[i] for i in keep], kl)]
+        self.order = [keep[j] for j in _abundance_order(aligner, [sizes[i] for i in keep], kl, [len(seqs[i]) for i in keep])]
         self.seqs = [seqs[i] for i in self.order]
         self.labels = [labels[i] for i in self.order]
         self.sizes = [sizes[i] for i in self.order]
@@ -577,7 +587,7 @@ class ChimerasDenovoSession:
         keep = [i for i, s in enumerate(seqs) if minseqlength <= len(s) <= maxseqlength]
         sizes = {i: header_size(labels[i]) for i in keep}
         kl = [labels[i] for i in keep]
-        self.order = [keep[j] for j in sort_by_abundance([sizes[i] for i in keep], kl)]
+        self.order = [keep[j] for j in _abundance_order(aligner, [sizes[i] for i in keep], kl, [len(seqs[i]) for i in keep])]
         self.seqs = [seqs[i] for i in self.order]
         self.labels = [labels[i] for i in self.order]
         self.sizes = [sizes[i] for i in self.order]
