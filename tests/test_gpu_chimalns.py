@@ -168,6 +168,21 @@ def test_tampered_record_is_refused(ref_session):
         s.alns_raw(qs, bad)
 
 
+def test_a_query_whose_end_wraps_is_refused(ref_session):
+    """the query of a selected record at offset 2^64 - 4 with length 8 "ends" at 4: checked without adding the two, before any
+    device work"""
+    from vsearch_amd import _lib
+    from vsearch_amd.search import _blob
+    s, qn, qs, recs = ref_session
+    k = next(i for i, r in enumerate(recs) if r["flag"] == "Y")
+    blob, off, lens = _blob(qs)
+    off, lens = off.copy(), lens.copy()
+    off[k], lens[k] = (1 << 64) - 4, 8
+    with pytest.raises(_lib.VsxError, match="vsx_chimera_alns: query exceeds the blob") as e:
+        s._alns(len(lens), blob, off, lens, recs, 80, "Y", 0, 0)
+    assert e.value.code == _lib.VSX_EINVAL
+
+
 def test_sentinel_route(aligner):
     """a pair the 16-bit aligner refuses (more than 25 000 000 cells): realigned on the host, the record rendered there"""
     from vsearch_amd import ChimeraSession

@@ -247,3 +247,19 @@ def test_refuses_a_searcher_without_detection_parameters(aligner):
         s.uchime_ref(["ACGT" * 30])
     assert e.value.code == _lib.VSX_EINVAL
     s.close()
+
+
+def test_a_query_whose_end_wraps_is_refused(aligner):
+    """offset 2^64 - 4 with length 8 "ends" at 4: the spans are checked without adding the two, before any device work"""
+    import ctypes as C
+    import numpy as np
+    from vsearch_amd import ChimeraSession, _lib
+    lib = _lib.load()
+    s = ChimeraSession(aligner, ["ACGT" * 50])
+    blob = b"ACGTTGCAACGGTCAT"
+    off, ln = np.array([0, (1 << 64) - 4], np.uint64), np.array([8, 8], np.uint32)
+    out = (_lib.ChimeraResult * 2)()
+    rc = lib.vsx_uchime_ref(s.h, C.byref(s.opts), C.c_uint64(2), C.cast(C.c_char_p(blob), C.c_void_p), C.c_uint64(len(blob)),
+                            off.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p), out)
+    assert (rc, lib.vsx_last_error()) == (_lib.VSX_EINVAL, b"vsx_uchime_ref: query exceeds the blob")
+    s.close()

@@ -693,6 +693,40 @@ def test_dust_masking_refuses_overlapping_sequences(gpu_required):
 
 
 @pytest.mark.gpu
+def test_a_span_whose_end_wraps_is_refused(gpu_required):
+    """offset 2^64 - 4 with length 8 "ends" at 4: the database and the queries are checked without adding the two (before any
+    device work: nothing of the blob is read)"""
+    import ctypes as C
+    import numpy as np
+    from vsearch_amd import Aligner, _lib
+    lib = gpu_required
+    blob = b"ACGTTGCAACGGTCAT"
+    vblob = C.cast(C.c_char_p(blob), C.c_void_p)
+    good_off, good_len = np.array([0, 8], np.uint64), np.array([8, 8], np.uint32)
+    bad_off, bad_len = np.array([0, (1 << 64) - 4], np.uint64), np.array([8, 8], np.uint32)
+    with Aligner() as al:
+        o = _lib.SearchOpts()
+        lib.vsx_search_opts_default(C.byref(o))
+        o.id = 0.9
+        h = C.c_void_p()
+        rc = lib.vsx_searcher_create(al.h, C.byref(h), C.byref(o), 2, vblob, len(blob), bad_off.ctypes.data_as(C.c_void_p), bad_len.ctypes.data_as(C.c_void_p))
+        assert (rc, lib.vsx_last_error()) == (_lib.VSX_EINVAL, b"vsx_searcher_create: sequence exceeds the blob")
+        rc = lib.vsx_searcher_create(al.h, C.byref(h), C.byref(o), 2, vblob, len(blob), good_off.ctypes.data_as(C.c_void_p), good_len.ctypes.data_as(C.c_void_p))
+        assert rc == 0, lib.vsx_last_error()
+        try:
+            hits = _lib.Hits()
+            rc = lib.vsx_search_batch(h, 2, vblob, len(blob), bad_off.ctypes.data_as(C.c_void_p), bad_len.ctypes.data_as(C.c_void_p), C.byref(hits))
+            assert (rc, lib.vsx_last_error()) == (_lib.VSX_EINVAL, b"vsx_search_batch: query exceeds the blob")
+            cands = _lib.Candidates()
+            for device in (1, 0):
+                rc = lib.vsx_search_candidates_batch(h, device, 2, vblob, len(blob), bad_off.ctypes.data_as(C.c_void_p), bad_len.ctypes.data_as(C.c_void_p),
+                                                     C.byref(cands))
+                assert (rc, lib.vsx_last_error()) == (_lib.VSX_EINVAL, b"vsx_search_candidates_batch: query exceeds the blob")
+        finally:
+            lib.vsx_searcher_destroy(h)
+
+
+@pytest.mark.gpu
 def test_allpairs_stream_equals_blocks(gpu_required):
     """r05: vsx_allpairs_stream overlaps pair enumeration, alignment and hit completion of consecutive blocks; the hits it hands to its
     sink, block after block, must be exactly those of one vsx_allpairs_block call -- ranked path and acceptall (every pair kept)"""

@@ -544,7 +544,7 @@ int vsx_chimera_alns(vsx_searcher * S, const vsx_chimalns_opts * O, uint64_t n, 
       const uint32_t bit = r.flag == 'Y' ? VSX_CHIMALNS_Y : r.flag == '?' ? VSX_CHIMALNS_BORDERLINE : VSX_CHIMALNS_N;
       if (!(select & bit)) continue;
       if (r.parent_a >= ndb || r.parent_b >= ndb) return fail(VSX_EINVAL, "%s: record %llu names a parent outside the database", who, (unsigned long long) k);
-      if (qo[k] + ql[k] > qtext_bytes) return fail(VSX_EINVAL, "%s: query exceeds the blob", who);
+      if ((rc = vsxp::check_spans(who, "query", 1, qo + k, ql + k, qtext_bytes)) != VSX_OK) return rc;      // (selected records only)
       if (ql[k] == 0) return fail(VSX_EINVAL, "%s: record %llu: empty query", who, (unsigned long long) k);
       sel.push_back(k);
     }

@@ -29,6 +29,8 @@
 #include "../../include/vsx_chimalns.h"
 
 #include <hip/hip_runtime.h>
+#include "vsx_devutil.h"
+#include "vsx_symbols.h"
 
 #pragma clang fp contract(off)
 
@@ -49,56 +51,11 @@ static_assert(CA_CMAX < (1u << 21) && CA_LMAX < CA_CMAX, "layout");
 // column flags: bits 0-1 diff class (0 ' ', 1 'A', 2 'B', 3 'N' / '?'), 2: class 3 is '?', 3: gap column, 4: gap or ambiguous here
 constexpr u32 F_QMARK = 4u, F_GAP = 8u, F_SELF = 16u;
 
-// chrmap_4bit of 'a' .. 'z' (utils/maps.cpp); every other byte is 0
-__device__ const uint8_t MAP4[26] = { 1, 14, 2, 13, 0, 0, 4, 11, 0, 0, 12, 0, 3, 15, 0, 0, 0, 5, 6, 8, 8, 7, 9, 0, 10, 0 };
-
-DEV u32 map4(u32 c)
-{
-  const u32 u = (c | 0x20u) - 'a';
-  return u < 26u ? MAP4[u] : 0u;
-}
-
-// chrmap_upcase: a letter in upper case, 'N' for every other byte
-DEV u32 upcase(u32 c)
-{
-  const u32 u = (c | 0x20u) - 'a';
-  return u < 26u ? (c & 0xDFu) : (u32) 'N';
-}
-
-DEV bool amb4(u32 c) { return c != 1u && c != 2u && c != 4u && c != 8u; }   // chrmap_ambiguous_4bit
-
-DEV u32 lane_id() { return threadIdx.x & 63u; }
-
-DEV u32 wave_incl_sum(u32 v)
-{
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-    {
-      const u32 o = (u32) __shfl_up((int) v, d, 64);
-      if ((int) lane_id() >= d) v += o;
-    }
-  return v;
-}
-
-// inclusive scan over the workgroup; *total = the sum of all threads' values
-DEV u64 block_scan(u64 v, u64 * s_wsum, u64 * total)
-{
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-    {
-      const u64 o = __shfl_up(v, d, 64);
-      if (lane >= d) v += o;
-    }
-  if (lane == 63) s_wsum[wave] = v;
-  __syncthreads();
-  u64 pre = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < CA_WAVES; ++w) { if (w < wave) pre += s_wsum[w]; tot += s_wsum[w]; }
-  __syncthreads();
-  *total = tot;
-  return v + pre;
-}
+using vsxd::lane_id;
+using vsxd::wave_incl_sum;
+using vsxsym::ambiguous4;
+using vsxsym::map4;
+using vsxsym::upcase;
 
 // maxi[i] from the scanned col[]: col[i] - col[i - 1] = 1 + maxi[i]
 DEV u32 maxi_at(const u32 * col, u32 i) { return i ? col[i] - col[i - 1] - 1u : col[0]; }
@@ -206,7 +163,7 @@ vsx_chimalns_kernel(const VsxChimAlnJob * __restrict__ jobs, const uint8_t * __r
         const u32 i = base + tid;
         const u64 v = i <= L ? (u64) s_col[i] + 1ull : 0ull;
         u64 chunk = 0ull;
-        const u64 incl = block_scan(v, s_wsum, &chunk) + carry;
+        const u64 incl = vsxd::block_scan<CA_WAVES>(v, s_wsum, &chunk) + carry;
         carry += chunk;
         if (i <= L) s_col[i] = (u32) (incl - 1ull);
       }
@@ -234,7 +191,7 @@ vsx_chimalns_kernel(const VsxChimAlnJob * __restrict__ jobs, const uint8_t * __r
       const u32 ab = arow[c], bb = brow[c];
       const u32 qv = map4(qrow[c]), av = map4(ab), bv = map4(bb);
       const bool gap = qv == 0u || av == 0u || bv == 0u;
-      const bool self = gap || amb4(qv) || amb4(av) || amb4(bv);
+      const bool self = gap || ambiguous4(qv) || ambiguous4(av) || ambiguous4(bv);
       if (av != 0u && av != qv) arow[c] = (uint8_t) (ab | 0x20u);
       if (bv != 0u && bv != qv) brow[c] = (uint8_t) (bb | 0x20u);
       u32 cls = 0u, qm = 0u;
@@ -283,8 +240,8 @@ vsx_chimalns_kernel(const VsxChimAlnJob * __restrict__ jobs, const uint8_t * __r
             g = (arow[c] != '-' ? 1ull : 0ull) | (qrow[c] != '-' ? 1ull << 21 : 0ull) | (brow[c] != '-' ? 1ull << 42 : 0ull);
           }
         u64 chunk = 0ull, gchunk = 0ull;
-        const u64 incl = block_scan(v, s_wsum, &chunk) + carry;
-        const u64 gincl = block_scan(g, s_wsum, &gchunk) + gcarry;
+        const u64 incl = vsxd::block_scan<CA_WAVES>(v, s_wsum, &chunk) + carry;
+        const u64 gincl = vsxd::block_scan<CA_WAVES>(g, s_wsum, &gchunk) + gcarry;
         carry += chunk;
         gcarry += gchunk;
         if (c < alnlen && ((c + 1u) % J.width == 0u || c + 1u == alnlen))

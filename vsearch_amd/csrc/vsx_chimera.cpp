@@ -1020,8 +1020,7 @@ int vsx_uchime_ref(vsx_searcher * S, const vsx_chimera_opts * O, uint64_t n, con
     return fail(VSX_EINVAL, "vsx_uchime_ref: the searcher was not created with the detection parameters (vsx_chimera_opts_default: "
                              "id = weak_id = 0.55, maxaccepts 4, maxrejects 16, plus strand)");
   if (O->mindiffs < 0 || !(O->xn > 0.0) || !(O->dn >= 0.0)) return fail(VSX_EINVAL, "vsx_uchime_ref: xn must be > 0, dn >= 0, mindiffs >= 0");
-  for (uint64_t k = 0; k < n; ++k)
-    if (qoff[k] + qlen[k] > qbytes) return fail(VSX_EINVAL, "vsx_uchime_ref: query exceeds the blob");
+  if (const int rc = vsxp::check_spans("vsx_uchime_ref", "query", n, qoff, qlen, qbytes)) return rc;
   const bool host_all = vsxp::env_is_host("VSX_CHIMERA");
   const uint64_t window = O->window > 0 ? (uint64_t) O->window : 16384;
   CallBufs bufs;

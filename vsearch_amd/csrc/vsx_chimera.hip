@@ -28,6 +28,8 @@
 #include "../../include/vsx_search.h"
 
 #include <hip/hip_runtime.h>
+#include "vsx_devutil.h"
+#include "vsx_symbols.h"
 
 #pragma clang fp contract(off)
 
@@ -47,7 +49,7 @@ constexpr int P2_BYTES = 3 * CH_LMAX + (CH_W + 1) * 4;
 constexpr int LDS_BYTES = P1_BYTES > P2_BYTES ? P1_BYTES : P2_BYTES;
 static_assert(CH_LMAX % 32 == 0 && CH_LMAX < (1 << 21), "layout");
 
-__device__ __forceinline__ bool amb4(unsigned c) { return c != 1u && c != 2u && c != 4u && c != 8u; }   // chrmap_ambiguous_4bit
+using vsxsym::ambiguous4;
 
 // the 32-column window sum ending at qpos (qpos >= 31)
 __device__ __forceinline__ int smooth_at(const uint32_t * row, int qpos)
@@ -57,26 +59,6 @@ __device__ __forceinline__ int smooth_at(const uint32_t * row, int qpos)
   uint32_t v = row[w];
   if (o) v = (v >> o) | (row[w + 1] << (32 - o));
   return __popc(v);
-}
-
-// inclusive scan over the workgroup; *total = the sum of all threads' values
-__device__ __forceinline__ unsigned long long block_scan(unsigned long long v, unsigned long long * s_wsum, unsigned long long * total)
-{
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-    {
-      const unsigned long long u = __shfl_up(v, d, 64);
-      if (lane >= d) v += u;
-    }
-  if (lane == 63) s_wsum[wave] = v;
-  __syncthreads();
-  unsigned long long pre = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < CH_WAVES; ++w) { if (w < wave) pre += s_wsum[w]; tot += s_wsum[w]; }
-  __syncthreads();
-  *total = tot;
-  return v + pre;
 }
 
 __device__ void write_unscored(vsx_chimera_result * r, int status, uint32_t pa, uint32_t pb)
@@ -263,7 +245,7 @@ vsx_chimera_eval_kernel(const VsxChimItem * __restrict__ items, const uint8_t * 
     {
       const unsigned qv = q[i], av = ac[i], bv = bc[i];
       const bool zero = qv == 0u || av == 0u || bv == 0u;
-      bool ign = zero || amb4(qv) || amb4(av) || amb4(bv);
+      bool ign = zero || ambiguous4(qv) || ambiguous4(av) || ambiguous4(bv);
       if (((ins[i >> 5] >> (i & 31)) & 1u) || ((ins[(i + 1) >> 5] >> ((i + 1) & 31)) & 1u)) ign = true;   // insertion column beside
       if (i > 0 && (q[i - 1] == 0 || ac[i - 1] == 0 || bc[i - 1] == 0)) ign = true;
       if (i + 1 < L && (q[i + 1] == 0 || ac[i + 1] == 0 || bc[i + 1] == 0)) ign = true;
@@ -296,7 +278,7 @@ vsx_chimera_eval_kernel(const VsxChimItem * __restrict__ items, const uint8_t * 
           if (!(fl & 32u) && (fl & 3u)) v = 1ull << (21 * ((fl & 3u) - 1));
         }
       unsigned long long chunk = 0ull;
-      const unsigned long long incl = block_scan(v, s_wsum, &chunk) + carry;
+      const unsigned long long incl = vsxd::block_scan<CH_WAVES>(v, s_wsum, &chunk) + carry;
       carry += chunk;
       if (v)
         {

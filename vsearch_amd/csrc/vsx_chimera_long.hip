@@ -49,6 +49,7 @@ constexpr int CL_SLOTS = CL_LMAX;                   // scratch ints per candidat
 static_assert(CL_LMAX % 32 == 0, "layout");
 static_assert((CL_LMAX + 1) <= CL_CMAX * CL_STRIDE, "maxi reuses the insertion matrix");
 
+// (kept beside vsx_devutil.h's butterfly: only lane 0 reads the sum, and the downward shuffle is an instruction per step shorter)
 __device__ __forceinline__ int wave_sum(int v)
 {
 #pragma unroll

@@ -134,6 +134,17 @@ void vsx_internal_run_threads(int nth, void (*fn)(int, void *), void * arg) { Wo
 // shared with vsx_search.cpp: one thread-local error slot for the whole library
 void vsx_internal_set_error(const char * msg) { g_err = msg ? msg : ""; }
 const vsx_scoring * vsx_internal_scoring(const vsx_ctx * ctx) { return &ctx->sc; }
+uint64_t vsx_internal_symbols(uint8_t * code, uint8_t * ambiguous, uint8_t * complement, uint8_t * upcase, uint64_t word)
+{
+  for (uint32_t c = 0; c < 256; ++c)
+    {
+      code[c] = (uint8_t) vsxsym::map4(c);
+      ambiguous[c] = vsxsym::ambiguous4(c) ? 1 : 0;
+      complement[c] = (uint8_t) vsxsym::complement(c);
+      upcase[c] = (uint8_t) vsxsym::upcase(c);
+    }
+  return vsxsym::mix64(word);
+}
 int vsx_internal_usable_cpus(void)
 {
   // CPUs this process may really use: affinity mask, capped by a cgroup v2 CPU quota

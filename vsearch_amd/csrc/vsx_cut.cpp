@@ -46,15 +46,6 @@ thread_local vsx_cut_stats g_stats {};
 const char * const PATTERN_MESSAGE[6] = { "", "No forward sequence cut site (^) found in pattern", "No reverse sequence cut site (_) found in pattern",
                                           "Multiple cut sites not supported", "Empty cut pattern string", "Illegal character in cut pattern" };
 
-// chrmap_complement (utils/maps.cpp): case kept for the letters the table has in lower case, unknown -> N
-unsigned char complement(unsigned char c)
-{
-  static const char up[] = "TVGHNNCDNNMNKNNNNYSAABWNRN";
-  if (c >= 'A' && c <= 'Z') return (unsigned char) up[c - 'A'];
-  if (c >= 'a' && c <= 'z') return ((0x17E34CFu >> (c - 'a')) & 1u) ? (unsigned char) (up[c - 'a'] | 0x20) : (unsigned char) 'N';
-  return (unsigned char) 'N';
-}
-
 struct Plan {
   uint64_t n = 0;
   const char * blob = nullptr;
@@ -185,7 +176,7 @@ int host_route(const Plan & P, vsx_cut_out & out)
             if (x < first_disc) { k = out.rev[x].seq; start = out.rev[x].start; length = out.rev[x].length; to = out.rev_off[x]; }
             else { k = out.uncut[x - first_disc]; start = 0; length = P.len[k]; to = out.discarded_off[x - first_disc]; }
             const unsigned char * src = reinterpret_cast<const unsigned char *>(P.blob) + P.off[k] + start;
-            for (uint64_t b = 0; b < length; ++b) out.text[to + b] = (char) complement(src[length - 1 - b]);
+            for (uint64_t b = 0; b < length; ++b) out.text[to + b] = (char) vsxsym::complement(src[length - 1 - b]);
           }
       });
     }
@@ -429,11 +420,11 @@ int run(vsx_ctx * ctx, const vsx_cut_opts * o, uint64_t n, const char * blob, ui
   const uint64_t tile = env_u64("VSX_CUT_TILE", TILE_DEFAULT);
   if (tile < 64 || tile % 64 || tile > ((uint64_t) 1 << 30)) return fail(VSX_EINVAL, "%s: VSX_CUT_TILE must be a multiple of 64 up to 2^30", WHO);
   P.tile_blocks = tile / 64;
+  if (const int rc = vsxp::check_spans(WHO, "a sequence", n, offsets, lengths, blob_bytes)) return rc;
   P.poff.assign(n + 1, 0);
   for (uint64_t k = 0; k < n; ++k)
     {
       if (lengths[k] > (uint32_t) INT32_MAX) return fail(VSX_EINVAL, "%s: a sequence is longer than INT32_MAX", WHO);
-      if (offsets[k] > blob_bytes || lengths[k] > blob_bytes - offsets[k]) return fail(VSX_EINVAL, "%s: a sequence exceeds the blob", WHO);
       P.poff[k + 1] = P.poff[k] + lengths[k];
     }
   out->n = n;

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include "vsx_cut_internal.h"
+#include "vsx_symbols.h"
 
 namespace {
 
@@ -29,35 +30,13 @@ typedef uint32_t u32;
 #define CUT_WAVES   4
 #define CUT_THREADS (64 * CUT_WAVES)
 
-// chrmap_4bit (utils/maps.cpp): IUPAC in either case, U = T, everything else 0
-__device__ __forceinline__ u32 cut_code4(u32 c)
-{
-  //                 a  b   c  d   e  f  g  h   i  j  k   l  m  n   o  p  q  r  s  t  u  v  w  x  y   z
-  const uint8_t t[26] = { 1, 14, 2, 13, 0, 0, 4, 11, 0, 0, 12, 0, 3, 15, 0, 0, 0, 5, 6, 8, 8, 7, 9, 0, 10, 0 };
-  const u32 l = (c | 0x20u) - 'a';
-  return ((c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z')) ? t[l] : 0u;
-}
-
-// chrmap_complement (utils/maps.cpp), as vsx_orient.hip states it: case kept for the letters the table has in lower case, unknown -> N
-__device__ __forceinline__ unsigned char cut_complement(u32 c)
-{
-  const char up[] = "TVGHNNCDNNMNKNNNNYSAABWNRN";
-  if (c >= 'A' && c <= 'Z') return (unsigned char) up[c - 'A'];
-  if (c >= 'a' && c <= 'z')
-    {
-      const u32 kept = 0x17E34CFu;                                      // bit (c - 'a') of: a b c d g h k m n r s t u v w y
-      return ((kept >> (c - 'a')) & 1u) ? (unsigned char) (up[c - 'a'] | 0x20) : (unsigned char) 'N';
-    }
-  return (unsigned char) 'N';
-}
-
 __global__ __launch_bounds__(CUT_THREADS)
 void vsx_cut_match_kernel(const uint8_t * __restrict__ text, const u64 * __restrict__ off, const u32 * __restrict__ len,
                           const u32 * __restrict__ bstart, const VsxCutItem * __restrict__ items, u32 n_items, u32 tile_blocks,
                           VsxCutPattern pat, u64 * __restrict__ bits, u32 * __restrict__ count)
 {
   __shared__ uint8_t code4[256];
-  code4[threadIdx.x] = (uint8_t) cut_code4(threadIdx.x);
+  code4[threadIdx.x] = (uint8_t) vsxsym::map4(threadIdx.x);      // chrmap_4bit as a 256-entry table
   __syncthreads();
   const u32 item = __builtin_amdgcn_readfirstlane(blockIdx.x * CUT_WAVES + (threadIdx.x >> 6));
   if (item >= n_items) return;
@@ -182,7 +161,7 @@ void vsx_cut_emit_kernel(const uint8_t * __restrict__ text, const u64 * __restri
                          const u64 * __restrict__ poff, u64 n_pieces, u64 total, uint8_t * __restrict__ out)
 {
   __shared__ unsigned char comp[256];
-  comp[threadIdx.x] = cut_complement(threadIdx.x);
+  comp[threadIdx.x] = (unsigned char) vsxsym::complement(threadIdx.x);      // chrmap_complement as a 256-entry table
   __syncthreads();
   const u64 o0 = ((u64) blockIdx.x * CUT_WAVES + (threadIdx.x >> 6)) * 64u;        // wave-uniform
   if (o0 >= total) return;

@@ -22,25 +22,18 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "vsx_derep_internal.h"
+#include "vsx_symbols.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 typedef unsigned long long u64;
+using vsxsym::mix64;
 
 #define DEREP_WAVES   4
 #define DEREP_THREADS (64 * DEREP_WAVES)
 #define DEREP_AHEAD   8                      // members whose symbols the quality kernel loads ahead of the chain
-
-// splitmix64's finaliser (as vsx_exact.hip)
-__device__ inline u64 mix64(u64 x)
-{
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
 
 __device__ inline uint32_t words_in(uint32_t len) { return (len + VSX_EXACT_CHUNK - 1) / VSX_EXACT_CHUNK; }
 
@@ -69,7 +62,7 @@ void vsx_derep_key_kernel(VsxDerepReads R, u64 hash_mask, u64 * __restrict__ kha
         }
       if (minus) { h = hm; w = wm; }
     }
-  if (R.label) h = mix64(h ^ ((u64) (R.label[k] + 1u) * 0x9E3779B97F4A7C15ull)) & hash_mask;
+  if (R.label) h = mix64(h ^ ((u64) (R.label[k] + 1u) * vsxsym::kGolden)) & hash_mask;
   khash[k] = h; kwoff[k] = w; flag[k] = (uint8_t) minus;
 }
 

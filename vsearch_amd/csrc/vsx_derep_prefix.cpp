@@ -127,14 +127,6 @@ struct Groups {
 };
 
 // ---- the host restatement ------------------------------------------------------------------------------------------------------
-inline uint64_t mix_host(uint64_t x)
-{
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
 constexpr uint64_t FNV_BASIS = 14695981039346656037ull, FNV_PRIME = 1099511628211ull;
 
 inline void atomic_min(uint64_t * p, uint64_t v)
@@ -170,7 +162,7 @@ void host_links(const Input & in, std::vector<uint64_t> & node, std::vector<uint
   for (uint64_t r = 0; r < K; ++r)
     {
       const uint32_t L = in.len(r);
-      uint64_t j = mix_host(hash[r]) & mask;
+      uint64_t j = vsxsym::mix64(hash[r]) & mask;
       for (;; j = (j + 1) & mask)
         {
           const uint64_t o = table[j];
@@ -195,7 +187,7 @@ void host_links(const Input & in, std::vector<uint64_t> & node, std::vector<uint
         for (uint32_t l = 0; l < L; h = (h ^ c[l]) * FNV_PRIME, ++l)
           {
             if (!occurs[l]) continue;
-            for (uint64_t j = mix_host(h) & mask;; j = (j + 1) & mask)
+            for (uint64_t j = vsxsym::mix64(h) & mask;; j = (j + 1) & mask)
               {
                 const uint64_t o = table[j];
                 ++np;

@@ -24,42 +24,23 @@
 // Integer code only; no kernel waits for another workgroup.
 #include <hip/hip_runtime.h>
 #include "vsx_derep_prefix_internal.h"
+#include "vsx_devutil.h"
+#include "vsx_symbols.h"
 
 namespace {
 
 typedef unsigned long long u64;
+using vsxd::shfl64;
+using vsxd::shfl_up64;
+using vsxd::shfl_xor64;
+using vsxsym::kGolden;
+using vsxsym::kLengthMul;
+using vsxsym::mix64;
 
 #define PREFIX_WAVES   4
 #define PREFIX_THREADS (64 * PREFIX_WAVES)
 
-constexpr u64 kGolden = 0x9E3779B97F4A7C15ull, kPartialTag = 0xD6E8FEB86659FD93ull, kLengthMul = 0xC2B2AE3D27D4EB4Full;
-
-// splitmix64's finaliser (as vsx_exact.hip)
-__device__ inline u64 mix64(u64 x)
-{
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
-__device__ inline u64 shfl64(u64 v, int lane)
-{
-  const int lo = __shfl((int) (uint32_t) v, lane), hi = __shfl((int) (uint32_t) (v >> 32), lane);
-  return ((u64) (uint32_t) hi << 32) | (uint32_t) lo;
-}
-
-__device__ inline u64 shfl_up64(u64 v, int d)
-{
-  const int lo = __shfl_up((int) (uint32_t) v, d), hi = __shfl_up((int) (uint32_t) (v >> 32), d);
-  return ((u64) (uint32_t) hi << 32) | (uint32_t) lo;
-}
-
-__device__ inline u64 shfl_xor64(u64 v, int m)
-{
-  const int lo = __shfl_xor((int) (uint32_t) v, m), hi = __shfl_xor((int) (uint32_t) (v >> 32), m);
-  return ((u64) (uint32_t) hi << 32) | (uint32_t) lo;
-}
+constexpr u64 kPartialTag = 0xD6E8FEB86659FD93ull;
 
 // H(l) from the sum of the mixed full words below word j = l / 16 and word j cut to l mod 16 codes
 __device__ inline u64 prefix_hash(u64 sum, u64 partial, uint32_t j, uint32_t l, u64 hash_mask)

@@ -352,9 +352,7 @@ int check_queries(uint64_t nq, const char * qblob, uint64_t qbytes, const uint64
   if (!out || (nq && (!qblob || !qoff || !qlen))) return fail(VSX_EINVAL, "%s: null argument", WHO);
   std::memset(out, 0, sizeof *out);
   if (nq > (uint64_t) UINT32_MAX) return fail(VSX_EINVAL, "%s: more than UINT32_MAX queries", WHO);
-  for (uint64_t i = 0; i < nq; ++i)
-    if (qoff[i] > qbytes || qlen[i] > qbytes - qoff[i]) return fail(VSX_EINVAL, "%s: query exceeds the blob", WHO);
-  return VSX_OK;
+  return vsxp::check_spans(WHO, "query", nq, qoff, qlen, qbytes);
 }
 
 }  // namespace
@@ -398,8 +396,7 @@ int vsx_internal_search_exact_host(const vsx_scoring * scoring, const vsx_search
   if (rc_q != VSX_OK) return rc_q;
   if (opts->soft_mask < 0 || opts->soft_mask > 2 || opts->qmask < 0 || opts->qmask > 3 || opts->hardmask < 0 || opts->hardmask > 3)
     return fail(VSX_EINVAL, "%s: masking option out of range", WHO);
-  for (uint64_t i = 0; i < n; ++i)
-    if (offsets[i] > blob_bytes || lengths[i] > blob_bytes - offsets[i]) return fail(VSX_EINVAL, "%s: sequence exceeds the blob", WHO);
+  if (const int rc = vsxp::check_spans(WHO, "sequence", n, offsets, lengths, blob_bytes)) return rc;
   // a searcher without a context: the text, the options and the annotations are all the host restatement reads
   vsx_searcher S;
   S.scoring = *scoring;

@@ -23,10 +23,14 @@
 // Integer code only; no kernel waits for another workgroup.
 #include <hip/hip_runtime.h>
 #include "vsx_exact_internal.h"
+#include "vsx_devutil.h"
+#include "vsx_symbols.h"
 
 namespace {
 
 typedef unsigned long long u64;
+using vsxd::shfl_xor64;
+using vsxsym::mix64;
 
 // chrmap_4bit for 'a' .. 'p' and 'q' .. 'z', one nibble per letter
 constexpr u64 table_of(const char * codes, int first)
@@ -45,21 +49,6 @@ __device__ inline uint32_t code_of(uint32_t byte)
   const u64 t = idx < 16u ? kTableLo : kTableHi;
   const uint32_t c = (uint32_t) (t >> ((idx & 15u) * 4u)) & 15u;
   return idx < 26u ? c : 0u;
-}
-
-// splitmix64's finaliser
-__device__ inline u64 mix64(u64 x)
-{
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
-__device__ inline u64 shfl_xor64(u64 v, int m)
-{
-  const int lo = __shfl_xor((int) (uint32_t) v, m), hi = __shfl_xor((int) (uint32_t) (v >> 32), m);
-  return ((u64) (uint32_t) hi << 32) | (uint32_t) lo;
 }
 
 // the codes of eight text bytes, byte i in nibble i; `zero_as`: the code a symbol outside the alphabet gets
@@ -120,12 +109,12 @@ void vsx_exact_hash_kernel(const VsxExactItem * __restrict__ items, uint32_t n_i
       word &= keep;
       if (it.reverse) word = __brevll(word);
       out[c] = word;
-      acc += mix64(word ^ ((u64) (c + 1) * 0x9E3779B97F4A7C15ull));
+      acc += mix64(word ^ ((u64) (c + 1) * vsxsym::kGolden));
     }
   if ((nwords & 1) && lane == 0) out[nwords] = 0;            // the pad word: the compare loop reads pairs
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) acc += shfl_xor64(acc, m);
-  if (lane == 0) hash[item] = mix64(acc ^ ((u64) len * 0xC2B2AE3D27D4EB4Full)) & hash_mask;
+  if (lane == 0) hash[item] = mix64(acc ^ ((u64) len * vsxsym::kLengthMul)) & hash_mask;
 }
 
 __global__ __launch_bounds__(256)

@@ -18,8 +18,11 @@
 // -ffp-contract=off and without fast-math: ee += pe and the comparisons are the IEEE double operations of the reference.
 #include <hip/hip_runtime.h>
 #include "vsx_fastq_stats_internal.h"
+#include "vsx_devutil.h"
 
 namespace {
+
+using vsxd::wave_sum;
 
 constexpr int ROW_BYTES = VSX_FQS_ROW_WORDS * 4;
 
@@ -118,12 +121,6 @@ void vsx_fastq_stats_walk_kernel(const VsxEestatsItem * __restrict__ items, uint
   if (have) minmax[read] = full ? (uint32_t) low | (uint32_t) high << 8 : VSX_FQS_NO_SYMBOL;
 }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
 __global__ __launch_bounds__(VSX_FQS_THREADS)
 void vsx_fastq_chars_kernel(const VsxEestatsItem * __restrict__ items, uint32_t n_items, const uint8_t * __restrict__ seq,
                             const uint8_t * __restrict__ qual, uint32_t tail, VsxFastqCharsAcc * __restrict__ acc, uint32_t * __restrict__ err)
@@ -205,7 +202,8 @@ void vsx_fastq_chars_kernel(const VsxEestatsItem * __restrict__ items, uint32_t 
   if (run > 0) atomicMax(&s_maxrun[run_char - 'A'], run);
   if ((uint32_t) full >= tail && tail_run >= tail && (unsigned) (tail_char - VSX_FQS_FIRST) < (unsigned) VSX_FQS_SYMS)
     atomicAdd(&s_tail[tail_char - VSX_FQS_FIRST], 1u);
-  const unsigned long long w_a = wave_sum(n_a), w_c = wave_sum(n_c), w_g = wave_sum(n_g), w_t = wave_sum(n_t), w_n = wave_sum(n_n);
+  typedef unsigned long long u64;                                 // (the sums are taken in 64 bits)
+  const u64 w_a = wave_sum<u64>(n_a), w_c = wave_sum<u64>(n_c), w_g = wave_sum<u64>(n_g), w_t = wave_sum<u64>(n_t), w_n = wave_sum<u64>(n_n);
   if (lane == 0)
     {
       if (w_a) atomicAdd(&acc->seq['A'], w_a);

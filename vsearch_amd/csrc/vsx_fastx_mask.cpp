@@ -396,11 +396,11 @@ int vsx_fastx_mask(vsx_ctx * ctx, const vsx_fastx_mask_opts * opts, uint64_t n, 
   if (!(o.max_unmasked_pct >= 0.0 && o.max_unmasked_pct <= 100.0)) return fail(VSX_EINVAL, "%s: max_unmasked_pct must be between 0.0 and 100.0", WHO);
   if (o.min_unmasked_pct > o.max_unmasked_pct) return fail(VSX_EINVAL, "%s: min_unmasked_pct cannot be larger than max_unmasked_pct", WHO);
   Input in { n, blob, offsets, lengths, {} };
+  if (const int rc = vsxp::check_spans(WHO, "a sequence", n, offsets, lengths, blob_bytes)) return rc;
   in.poff.assign(n + 1, 0);
   for (uint64_t k = 0; k < n; ++k)
     {
       if (lengths[k] > (uint32_t) INT32_MAX) return fail(VSX_EINVAL, "%s: a sequence is longer than INT32_MAX", WHO);
-      if (offsets[k] > blob_bytes || lengths[k] > blob_bytes - offsets[k]) return fail(VSX_EINVAL, "%s: a sequence exceeds the blob", WHO);
       in.poff[k + 1] = in.poff[k] + lengths[k];
     }
   if (!disjoint(n, offsets, lengths)) return fail(VSX_EINVAL, "%s: masking needs sequences that do not overlap in the blob", WHO);

@@ -21,35 +21,17 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include "vsx_getseqs_internal.h"
+#include "vsx_devutil.h"
 
 namespace {
 
 typedef unsigned long long u64;
+using vsxd::shfl64;
+using vsxd::shfl_up64;
+using vsxd::wave_sum;
 
 #define GS_WAVES   4
 #define GS_THREADS (64 * GS_WAVES)
-
-__device__ inline u64 shfl_xor64(u64 v, int m)
-{
-  const int lo = __shfl_xor((int) (uint32_t) v, m), hi = __shfl_xor((int) (uint32_t) (v >> 32), m);
-  return ((u64) (uint32_t) hi << 32) | (uint32_t) lo;
-}
-__device__ inline u64 shfl_up64(u64 v, int d)
-{
-  const int lo = __shfl_up((int) (uint32_t) v, d), hi = __shfl_up((int) (uint32_t) (v >> 32), d);
-  return ((u64) (uint32_t) hi << 32) | (uint32_t) lo;
-}
-__device__ inline u64 shfl64(u64 v, int src)
-{
-  const int lo = __shfl((int) (uint32_t) v, src), hi = __shfl((int) (uint32_t) (v >> 32), src);
-  return ((u64) (uint32_t) hi << 32) | (uint32_t) lo;
-}
-__device__ inline u64 wave_sum64(u64 v)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += shfl_xor64(v, m);
-  return v;
-}
 
 // P(s) over the whole wave: every lane returns the sum
 __device__ inline u64 wave_poly(const uint8_t * s, uint32_t L, uint32_t lane, uint32_t fold)
@@ -57,7 +39,7 @@ __device__ inline u64 wave_poly(const uint8_t * s, uint32_t L, uint32_t lane, ui
   const u64 step = vsx_gs_pow(VSX_GS_BASE, 64);
   u64 pw = vsx_gs_pow(VSX_GS_BASE, lane), acc = 0;
   for (uint32_t j = lane; j < L; j += 64, pw *= step) acc += (u64) (vsx_gs_fold(s[j], fold) + 1u) * pw;
-  return wave_sum64(acc);
+  return wave_sum(acc);
 }
 
 __global__ __launch_bounds__(GS_THREADS)
@@ -198,7 +180,7 @@ void vsx_getseqs_match_kernel(VsxGetseqsMatch M)
             }
         }
     }
-  probes = wave_sum64(probes); checks = wave_sum64(checks);
+  probes = wave_sum(probes); checks = wave_sum(checks);
   if (lane == 0)
     {
       M.verdict[i] = found ? 1u : 0u;

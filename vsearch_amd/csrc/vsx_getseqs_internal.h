@@ -8,6 +8,7 @@
 
 #include <stdint.h>
 #include <hip/hip_runtime_api.h>
+#include "vsx_symbols.h"
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define VSX_GS_HD __host__ __device__
@@ -15,23 +16,16 @@
 #define VSX_GS_HD
 #endif
 
-#define VSX_GS_BASE       0x9E3779B97F4A7C15ull        // odd
-#define VSX_GS_LENGTH_MUL 0xC2B2AE3D27D4EB4Full
+#define VSX_GS_BASE       vsxsym::kGolden              // odd
+#define VSX_GS_LENGTH_MUL vsxsym::kLengthMul
 
 #define VSX_GS_BOUND_NONE  0u                          // LABEL / LABELS
 #define VSX_GS_BOUND_ALNUM 1u                          // WORD / WORDS
 #define VSX_GS_BOUND_SEMI  2u                          // WORD / WORDS with a field
 
-VSX_GS_HD inline uint64_t vsx_gs_mix64(uint64_t x)   // splitmix64's finaliser (as vsx_exact.hip)
-{
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
 VSX_GS_HD inline uint64_t vsx_gs_key(uint64_t poly, uint32_t len, uint64_t hash_mask)
 {
-  return vsx_gs_mix64(poly ^ ((uint64_t) len * VSX_GS_LENGTH_MUL)) & hash_mask;
+  return vsxsym::mix64(poly ^ ((uint64_t) len * VSX_GS_LENGTH_MUL)) & hash_mask;
 }
 VSX_GS_HD inline uint64_t vsx_gs_pow(uint64_t b, uint64_t e)
 {

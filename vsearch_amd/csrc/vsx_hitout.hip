@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include "vsx_hitout_internal.h"
+#include "vsx_devutil.h"
+#include "vsx_symbols.h"
 
 namespace {
 
@@ -30,25 +32,10 @@ typedef unsigned long long u64;
 
 constexpr int WAVES_PER_BLOCK = 4;
 
-// chrmap_4bit of 'a' .. 'z' (utils/maps.cpp); every other byte is 0
-__device__ const uint8_t MAP4[26] = { 1, 14, 2, 13, 0, 0, 4, 11, 0, 0, 12, 0, 3, 15, 0, 0, 0, 5, 6, 8, 8, 7, 9, 0, 10, 0 };
-// chrmap_complement of 'A' .. 'Z'; a lower-case letter keeps its case where the table has one, everything else is 'N'
-__device__ const uint8_t COMP[26] = { 'T', 'V', 'G', 'H', 'N', 'N', 'C', 'D', 'N', 'N', 'M', 'N', 'K', 'N', 'N', 'N', 'N', 'Y', 'S', 'A', 'A', 'B', 'W', 'N', 'R', 'N' };
-// bit k: the letter 'a' + k has a lower-case complement (a b c d g h k m n r s t u v w y)
-constexpr u32 COMP_LOWER = 0x017E34CFu;
-
-DEV u32 map4(u32 c)
-{
-  const u32 u = (c | 0x20u) - 'a';
-  return u < 26u ? MAP4[u] : 0u;
-}
-
-DEV u32 complement(u32 c)
-{
-  if (c - 'A' < 26u) return COMP[c - 'A'];
-  if (c - 'a' < 26u) return ((COMP_LOWER >> (c - 'a')) & 1u) ? (COMP[c - 'a'] | 0x20u) : (u32) 'N';
-  return 'N';
-}
+using vsxd::lane_id;
+using vsxd::wave_incl_sum;
+using vsxsym::complement;
+using vsxsym::map4;
 
 // get_aligment_symbol (showalign.cpp:122-137)
 DEV u32 symbol(u32 qc, u32 tc, bool n_mismatch)
@@ -58,19 +45,6 @@ DEV u32 symbol(u32 qc, u32 tc, bool n_mismatch)
   if (q == t && (q == 1u || q == 2u || q == 4u || q == 8u)) return '|';
   if ((q & t) != 0u) return '+';
   return ' ';
-}
-
-DEV u32 lane_id() { return threadIdx.x & 63u; }
-
-DEV u32 wave_incl_sum(u32 v)
-{
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-    {
-      const u32 o = (u32) __shfl_up((int) v, d, 64);
-      if ((int) lane_id() >= d) v += o;
-    }
-  return v;
 }
 
 DEV u32 ndigits(u32 v)

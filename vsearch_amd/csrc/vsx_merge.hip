@@ -18,22 +18,15 @@
 // Output: vector stores only.
 #include <hip/hip_runtime.h>
 #include "vsx_merge_internal.h"
+#include "vsx_devutil.h"
 
 namespace {
 
 constexpr int MG_L = VSX_MERGE_MAX_LEN;
 constexpr int MG_T = VSX_MERGE_THREADS;
 
-__device__ inline int wave_min(int v)
-{
-  for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(v, m, 64); v = o < v ? o : v; }
-  return v;
-}
-__device__ inline int wave_sum(int v)
-{
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+using vsxd::wave_min;
+using vsxd::wave_sum;
 
 // first position p < len whose quality is out of range or at / below truncqual (len if none), as the reference's loop meets it
 __device__ inline int first_stop(const uint8_t * q, int len, const VsxMergeParams & P, int lane)

@@ -375,8 +375,7 @@ int check_call(const vsx_orient_opts * o, const Queries & Q, vsx_orient_result *
   std::memset(out, 0, sizeof *out);
   if (o->qmask < 0 || o->qmask > 2) return fail(VSX_EINVAL, "%s: qmask must be 0 (none), 1 (soft) or 2 (dust)", WHO);
   if (Q.n > (uint64_t) UINT32_MAX) return fail(VSX_EINVAL, "%s: too many queries in one call", WHO);
-  for (uint64_t i = 0; i < Q.n; ++i)
-    if (Q.off[i] > Q.bytes || Q.len[i] > Q.bytes - Q.off[i]) return fail(VSX_EINVAL, "%s: query exceeds the blob", WHO);
+  if (const int rc = vsxp::check_spans(WHO, "query", Q.n, Q.off, Q.len, Q.bytes)) return rc;
   if (o->want_text && !sequences_disjoint(Q.n, [&](uint64_t k) { return Q.off[k]; }, [&](uint64_t k) { return (uint64_t) Q.len[k]; }))
     return fail(VSX_EINVAL, "%s: want_text needs queries that do not overlap in the blob", WHO);
   return VSX_OK;
@@ -478,8 +477,7 @@ int vsx_internal_orient_host(const vsx_search_opts * search, const vsx_orient_op
   if (search->wordlength < 3 || search->wordlength > 15) return fail(VSX_EINVAL, "%s: wordlength must be 3..15", WHO);
   if (search->soft_mask < 0 || search->soft_mask > 2 || search->hardmask < 0 || search->hardmask > 3)
     return fail(VSX_EINVAL, "%s: masking option out of range", WHO);
-  for (uint64_t i = 0; i < n; ++i)
-    if (offsets[i] > blob_bytes || lengths[i] > blob_bytes - offsets[i]) return fail(VSX_EINVAL, "%s: sequence exceeds the blob", WHO);
+  if (const int rc = vsxp::check_spans(WHO, "sequence", n, offsets, lengths, blob_bytes)) return rc;
   // a searcher without a context: the masked text and the word length are all the restatement reads
   vsx_searcher S;
   S.o = *search;

@@ -19,9 +19,12 @@
 #include <algorithm>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "vsx_orient_internal.h"
+#include "vsx_devutil.h"
+#include "vsx_symbols.h"
 
 typedef unsigned int u32;
 typedef unsigned long long u64;
+using vsxd::wave_sum;
 
 // ---- build -------------------------------------------------------------------------------------------------------------------
 // the word of w symbols at s[p ..]; false where a symbol is ambiguous or (lower != NULL) masked.  i = the blob byte of s[p].
@@ -89,13 +92,6 @@ __device__ __forceinline__ u32 or_rc(u32 word, int w)
   u32 x = __brev(~word);                                              // symbols reversed and complemented, the bits of each pair swapped
   x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
   return x >> (32 - 2 * w);
-}
-
-__device__ __forceinline__ u32 wave_sum(u32 v)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += (u32) __shfl_xor((int) v, m, 64);
-  return v;
 }
 
 // TPQ threads per query (64: a wave of the block per query; else the whole block), SLOTS per set
@@ -180,25 +176,12 @@ vsx_orient_count_kernel(u32 nq, const u32 * __restrict__ list, const char * __re
 }
 
 // ---- emit --------------------------------------------------------------------------------------------------------------------
-// chrmap_complement (utils/maps.cpp): the complement of A .. Z, case kept for the letters the reference's table has in lower case
-__device__ __forceinline__ unsigned char or_complement(u32 c)
-{
-  const char up[] = "TVGHNNCDNNMNKNNNNYSAABWNRN";
-  if (c >= 'A' && c <= 'Z') return (unsigned char) up[c - 'A'];
-  if (c >= 'a' && c <= 'z')
-    {
-      const u32 kept = 0x17E34CFu;                                      // bit (c - 'a') of: a b c d g h k m n r s t u v w y
-      return ((kept >> (c - 'a')) & 1u) ? (unsigned char) (up[c - 'a'] | 0x20) : (unsigned char) 'N';
-    }
-  return (unsigned char) 'N';
-}
-
 __global__ void __launch_bounds__(256)
 vsx_orient_emit_kernel(u32 nq, const char * __restrict__ text, const char * __restrict__ qual, const u64 * __restrict__ qoff,
                        const u32 * __restrict__ qlen, const OrRec * __restrict__ rec, char * __restrict__ out_text, char * __restrict__ out_qual)
 {
   __shared__ unsigned char comp[256];
-  comp[threadIdx.x] = or_complement(threadIdx.x);
+  comp[threadIdx.x] = (unsigned char) vsxsym::complement(threadIdx.x);      // chrmap_complement as a 256-entry table
   __syncthreads();
   const u32 q = blockIdx.x * 4u + (threadIdx.x >> 6);
   const u32 lane = threadIdx.x & 63u;

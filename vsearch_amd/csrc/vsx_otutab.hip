@@ -26,30 +26,19 @@
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include "vsx_otutab_internal.h"
+#include "vsx_devutil.h"
+#include "vsx_symbols.h"
 
 namespace {
 
 typedef unsigned long long u64;
+using vsxd::shfl_xor64;
+using vsxsym::kGolden;
+using vsxsym::kLengthMul;
+using vsxsym::mix64;
 
 #define OTUTAB_WAVES   4
 #define OTUTAB_THREADS (64 * OTUTAB_WAVES)
-
-constexpr u64 kGolden = 0x9E3779B97F4A7C15ull, kLengthMul = 0xC2B2AE3D27D4EB4Full;
-
-// splitmix64's finaliser (as vsx_exact.hip)
-__device__ inline u64 mix64(u64 x)
-{
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
-__device__ inline u64 shfl_xor64(u64 v, int m)
-{
-  const int lo = __shfl_xor((int) (uint32_t) v, m), hi = __shfl_xor((int) (uint32_t) (v >> 32), m);
-  return ((u64) (uint32_t) hi << 32) | (uint32_t) lo;
-}
 
 // bit p: the keyword stands at byte p of the step (it may run into the next step's bytes)
 template <int N>

@@ -5,6 +5,7 @@
 #define VSX_PRIVATE_H
 
 #include "../../include/vsx_search.h"
+#include "vsx_symbols.h"
 
 #include <hip/hip_runtime_api.h>
 #include <algorithm>
@@ -30,6 +31,9 @@ hipStream_t vsx_internal_stream(const vsx_ctx * ctx);
 // real size, which put() wants again
 hipError_t vsx_internal_scratch_get(vsx_ctx * ctx, size_t bytes, void ** out, size_t * got);
 void vsx_internal_scratch_put(vsx_ctx * ctx, void * p, size_t got);
+// vsx_symbols.h as the host compiles it (tests/test_symbols_host.py): four 256-entry tables by byte value -- map4, ambiguous4 (of the
+// byte taken as a code), complement, upcase -- and the return value mix64(word)
+uint64_t vsx_internal_symbols(uint8_t * code, uint8_t * ambiguous, uint8_t * complement, uint8_t * upcase, uint64_t word);
 // CPUs this process may really use: affinity mask, capped by a cgroup v2 CPU quota
 int vsx_internal_usable_cpus(void);
 // the library's host worker pool: fn(0) runs on the caller, which also helps with queued jobs while it waits
@@ -367,19 +371,18 @@ void run_pool(int nth, F && f)
   vsx_internal_run_threads(nth, [](int t, void * a) { (*static_cast<Fn *>(a))(t); }, (void *) &f);
 }
 
-// chrmap_4bit (utils/maps.cpp): the codes the device encoder writes into a sequence set
-inline uint8_t map4(unsigned char c)
+// chrmap_4bit (the codes the device encoder writes into a sequence set) and chrmap_ambiguous_4bit, as vsx_symbols.h states them
+inline uint8_t map4(unsigned char c) { return (uint8_t) vsxsym::map4(c); }
+using vsxsym::ambiguous4;
+
+// do the n spans (offsets[k], lengths[k]) lie inside a blob of blob_bytes?  (offset + length may wrap: never added.)  `what` names
+// a span in the error text: "query", "a sequence", ...
+inline int check_spans(const char * who, const char * what, uint64_t n, const uint64_t * offsets, const uint32_t * lengths, uint64_t blob_bytes)
 {
-  switch (c | 0x20)
-    {
-    case 'a': return 1;  case 'b': return 14; case 'c': return 2;  case 'd': return 13;
-    case 'g': return 4;  case 'h': return 11; case 'k': return 12; case 'm': return 3;
-    case 'n': return 15; case 'r': return 5;  case 's': return 6;  case 't': return 8;
-    case 'u': return 8;  case 'v': return 7;  case 'w': return 9;  case 'y': return 10;
-    default: return 0;
-    }
+  for (uint64_t k = 0; k < n; ++k)
+    if (offsets[k] > blob_bytes || lengths[k] > blob_bytes - offsets[k]) return fail(VSX_EINVAL, "%s: %s exceeds the blob", who, what);
+  return VSX_OK;
 }
-inline bool ambiguous4(uint8_t c) { return c != 1 && c != 2 && c != 4 && c != 8; }     // chrmap_ambiguous_4bit
 
 }  // namespace vsxp
 

@@ -548,8 +548,7 @@ int vsx_searcher_create(vsx_ctx * ctx, vsx_searcher ** out, const vsx_search_opt
   S->blob.push_back(0);
   S->off.assign(offsets, offsets + n);
   S->len.assign(lengths, lengths + n);
-  for (uint64_t i = 0; i < n; ++i)
-    if (offsets[i] + lengths[i] > blob_bytes) return fail(VSX_EINVAL, "vsx_searcher_create: sequence exceeds the blob");
+  if (const int rc = vsxp::check_spans("vsx_searcher_create", "sequence", n, offsets, lengths, blob_bytes)) return rc;
   // clamp to the database size; 0 means "all" (usearch_global.cpp:598-611)
   const int64_t sc = (int64_t) n;
   S->mr = (opts->maxrejects == 0 || opts->maxrejects > sc) ? sc : opts->maxrejects;
@@ -674,8 +673,7 @@ int vsx_search_candidates_batch(vsx_searcher * S, int32_t device, uint64_t nq, c
 {
   if (!S || !out || (nq && (!qblob || !qoff || !qlen))) return fail(VSX_EINVAL, "vsx_search_candidates_batch: null argument");
   std::memset(out, 0, sizeof *out);
-  for (uint64_t i = 0; i < nq; ++i)
-    if (qoff[i] + qlen[i] > qbytes) return fail(VSX_EINVAL, "vsx_search_candidates_batch: query exceeds the blob");
+  if (const int rc = vsxp::check_spans("vsx_search_candidates_batch", "query", nq, qoff, qlen, qbytes)) return rc;
   if (device && !device_kmer_ok(*S))
     return fail(VSX_EINVAL, "vsx_search_candidates_batch: the device path needs wordlength 3..15 and a non-empty database");
   const double t0 = now_s();
@@ -1202,8 +1200,7 @@ static int search_batch_impl(vsx_searcher * S, uint64_t nq, const char * qblob, 
 {
   if (!S || !out || (nq && (!qblob || !qoff || !qlen))) return fail(VSX_EINVAL, "vsx_search_batch: null argument");
   std::memset(out, 0, sizeof *out);
-  for (uint64_t i = 0; i < nq; ++i)
-    if (qoff[i] + qlen[i] > qbytes) return fail(VSX_EINVAL, "vsx_search_batch: query exceeds the blob");
+  if (const int rc = vsxp::check_spans("vsx_search_batch", "query", nq, qoff, qlen, qbytes)) return rc;
   const double t_begin = now_s();
   static const bool timeline = std::getenv("VSX_DEBUG_TIMELINE") != nullptr;
   // lazy first batches (advance()): VSX_SEARCH_LAZY=0 aligns the reference's batches of eight from the start (A/B, tests)

@@ -69,19 +69,8 @@ using vsxp::fail;
 using vsxp::now_s;
 using vsxp::run_pool;
 
-// chrmap_complement, utils/maps.cpp:121-150: IUPAC complement, case kept for the letters that have one, everything else 'N'
-inline char complement(unsigned char c)
-{
-  static const char up[] = "TVGHNNCDNNMNKNNNNYSAABWNRN";    // complement of 'A' .. 'Z'
-  if (c >= 'A' && c <= 'Z') return up[c - 'A'];
-  if (c >= 'a' && c <= 'z')
-    {
-      const char u = up[c - 'a'];
-      const bool kept = std::strchr("abcdghkmnrstuvwy", (int) c) != nullptr;       // letters whose row entry is lower case
-      return kept ? (char) (u | 0x20) : 'N';
-    }
-  return 'N';
-}
+// chrmap_complement, utils/maps.cpp:121-150, as vsx_symbols.h states it
+inline char complement(unsigned char c) { return (char) vsxsym::complement(c); }
 
 struct Cand { uint32_t target, count, length; };
 

@@ -17,7 +17,7 @@ static int seqset_common(vsx_ctx * ctx, vsx_seqset ** out, uint64_t n, const voi
     return fail(VSX_EINVAL, "vsx_seqset_create: null argument");
   *out = nullptr;
   for (uint64_t i = 0; i < n; ++i)
-    if (offsets[i] + lengths[i] > blob_bytes)
+    if (offsets[i] > blob_bytes || lengths[i] > blob_bytes - offsets[i])
       return fail(VSX_EINVAL, "vsx_seqset_create: sequence %" PRIu64 " exceeds the blob", i);
   VSX_HIP(hipSetDevice(ctx->device));
   auto * s = new vsx_seqset;

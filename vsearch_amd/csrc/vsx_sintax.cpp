@@ -409,9 +409,7 @@ int check_call(const vsx_sintax_opts * o, uint64_t nq, const char * qblob, uint6
   std::memset(out, 0, sizeof *out);
   if (o->randseed == 0) return fail(VSX_EINVAL, "%s: randseed 0 seeds from the operating system: nothing could be compared; give a seed", WHO);
   if (nq > (uint64_t) UINT32_MAX / 2) return fail(VSX_EINVAL, "%s: too many queries in one call", WHO);
-  for (uint64_t i = 0; i < nq; ++i)
-    if (qoff[i] > qbytes || qlen[i] > qbytes - qoff[i]) return fail(VSX_EINVAL, "%s: query exceeds the blob", WHO);
-  return VSX_OK;
+  return vsxp::check_spans(WHO, "query", nq, qoff, qlen, qbytes);
 }
 
 uint32_t max_dblen()
@@ -509,8 +507,7 @@ int vsx_internal_sintax_host(const vsx_search_opts * search, const vsx_sintax_op
   if (search->wordlength < 3 || search->wordlength > 15) return fail(VSX_EINVAL, "%s: wordlength must be 3..15", WHO);
   if (search->soft_mask < 0 || search->soft_mask > 2 || search->hardmask < 0 || search->hardmask > 3)
     return fail(VSX_EINVAL, "%s: masking option out of range", WHO);
-  for (uint64_t i = 0; i < n; ++i)
-    if (offsets[i] > blob_bytes || lengths[i] > blob_bytes - offsets[i]) return fail(VSX_EINVAL, "%s: sequence exceeds the blob", WHO);
+  if (const int rc = vsxp::check_spans(WHO, "sequence", n, offsets, lengths, blob_bytes)) return rc;
   // a searcher without a context: the masked text, the word length and the labels are all the restatement reads
   vsx_searcher S;
   S.o = *search;

@@ -23,9 +23,11 @@
 #define SX_DEVICE_MULHI 1
 #include "vsx_sintax_internal.h"
 #include "vsx_kmer_pack.h"
+#include "vsx_devutil.h"
 
 typedef unsigned int u32;
 typedef unsigned long long u64;
+using vsxd::wave_max;
 
 #define SX_THREADS 512
 #define SX_WAVES 8
@@ -68,28 +70,6 @@ vsx_sintax_sample_kernel(u32 nq, const u64 * __restrict__ wstart, const u32 * __
           nout[r] = (uint8_t) n;
         }
     }
-}
-
-__device__ __forceinline__ u64 wave_max_u64(u64 v)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1)
-    {
-      const u32 lo = (u32) __shfl_xor((int) (u32) v, m, 64), hi = (u32) __shfl_xor((int) (u32) (v >> 32), m, 64);
-      const u64 o = ((u64) hi << 32) | lo;
-      v = o > v ? o : v;
-    }
-  return v;
-}
-__device__ __forceinline__ u32 wave_max_u32(u32 v)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1)
-    {
-      const u32 o = (u32) __shfl_xor((int) v, m, 64);
-      v = o > v ? o : v;
-    }
-  return v;
 }
 
 __global__ void __launch_bounds__(SX_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
@@ -216,7 +196,7 @@ vsx_sintax_count_kernel(const uint4 * __restrict__ postings, const u64 * __restr
                 }
             }
         }
-      const u32 top = wave_max_u32(mytop);
+      const u32 top = wave_max(mytop);
       if (lane == 0) wave_top[wave] = top;
       __syncthreads();
       u32 cmax = 0;
@@ -253,7 +233,7 @@ vsx_sintax_count_kernel(const uint4 * __restrict__ postings, const u64 * __restr
       for (int g4 = 0; g4 < SX_DW_PER_THREAD / 4; ++g4) c4[g4 * SX_THREADS + tid] = make_uint4(0, 0, 0, 0);
       if (cmax > 1u)
         {
-          best = wave_max_u64(best);
+          best = wave_max(best);
           if (lane == 0) wave_key[wave] = best;
         }
       __syncthreads();
@@ -297,7 +277,7 @@ vsx_sintax_vote_kernel(u32 nq, u32 ntiles, const u64 * __restrict__ keys, const 
           const u64 ballot = __ballot(kept);
           if (kept) cand[s][n + (u32) __popcll(ballot & below)] = sx_key_seq(key);
           n += (u32) __popcll(ballot);
-          const u32 m = wave_max_u32(kept ? c : 0u);
+          const u32 m = wave_max(kept ? c : 0u);
           bc = m > bc ? m : bc;
         }
       boot[s] = n;
@@ -351,7 +331,7 @@ vsx_sintax_vote_kernel(u32 nq, u32 ntiles, const u64 * __restrict__ keys, const 
                 vote = v > vote ? v : vote;
               }
           }
-      vote = wave_max_u32(vote);
+      vote = wave_max(vote);
       const u32 winner = vote ? 127u - (vote & 127u) : 0u;           // (candidate 0's group always votes)
       const u32 wid = ids[winner];
       __syncthreads();

@@ -309,11 +309,11 @@ int run(vsx_ctx * ctx, const vsx_sortby_opts * o, uint64_t n, const char * blob,
   P.minsize = o->minsize; P.maxsize = o->maxsize; P.topn = (uint64_t) o->topn; P.max_rounds = (uint32_t) max_rounds;
   P.nth = std::max(1, std::min(o->threads > 0 ? o->threads : vsxp::usable_cpus(), HOST_THREADS));
   // the span of the blob the headers use: only that goes up
+  if (const int rc = vsxp::check_spans(WHO, "a header", n, offsets, lengths, blob_bytes)) return rc;
   uint64_t first = blob_bytes, last = 0, label_bytes = 0;
   for (uint64_t i = 0; i < n; ++i)
     {
       if (sizes[i] == 0) return fail(VSX_EINVAL, "%s: record %llu has abundance 0", WHO, (unsigned long long) i);
-      if (offsets[i] > blob_bytes || lengths[i] > blob_bytes - offsets[i]) return fail(VSX_EINVAL, "%s: a header exceeds the blob", WHO);
       if (!lengths[i]) continue;
       if (std::memchr(blob + offsets[i], 0, lengths[i])) return fail(VSX_EINVAL, "%s: the header of record %llu holds a NUL byte", WHO, (unsigned long long) i);
       first = std::min(first, offsets[i]); last = std::max(last, offsets[i] + lengths[i]);
