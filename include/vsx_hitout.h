@@ -5,7 +5,7 @@
  *
  * Callers: the results of vsx_search_batch(_meta), vsx_search_exact and vsx_multi_search_batch (render with replica 0).  NOT covered:
  * the hits of vsx_allpairs_* and vsx_cluster_fast -- their queries are database sequences, which this call does not take.  The
- * chimera commands' --uchimealns block is a call of its own: vsx_chimera_alns (vsx_chimalns.h).
+ * chimera commands' --uchimealns block is a call of its own: vsx_chimera_alns (vsx_chimalns.h); so is --lcaout: vsx_lca (vsx_lca.h).
  *
  * Query text.  The call masks the queries itself with the code the search uses -- the plus strand and, under strand_both, the
  * reverse complement, each on its own (core/search.cpp:294-303): --qmask dust leaves the DUST intervals in lower case, --hardmask

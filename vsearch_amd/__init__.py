@@ -23,6 +23,8 @@ from .getseqs import getseqs, getseq, getsubseq, getseqs_host, read_labels, Gets
 from .cut import cut, cut_host, parse_pattern, CutResult  # noqa: F401
 # (vsearch_amd.sortby stays the module: its sortby() is not exported under the same name)
 from .sortby import sortbysize, sortbylength, sortby_host, SortbyResult  # noqa: F401
+# (vsearch_amd.lca stays the module too: call vsearch_amd.lca.lca())
+from .lca import LcaIndex, LcaResult, lca_host, lcaout_lines  # noqa: F401
 from ._lib import SENTINEL, VsxError, load as load_library  # noqa: F401
 
 __all__ = ["Aligner", "SequenceSet", "Plan", "AlignmentResults", "RawResults", "cigar_from_runs", "DEFAULT_SCORING", "scoring_from_tuple",
@@ -30,3 +32,4 @@ __all__ = ["Aligner", "SequenceSet", "Plan", "AlignmentResults", "RawResults", "
 __all__ += ["getseqs", "getseq", "getsubseq", "getseqs_host", "read_labels", "GetseqsResult"]
 __all__ += ["cut", "cut_host", "parse_pattern", "CutResult"]
 __all__ += ["sortbysize", "sortbylength", "sortby_host", "SortbyResult"]
+__all__ += ["LcaIndex", "LcaResult", "lca_host", "lcaout_lines"]

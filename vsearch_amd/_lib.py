@@ -78,6 +78,10 @@ CHIMALNS_Y, CHIMALNS_BORDERLINE, CHIMALNS_N, CHIMALNS_MAX_COLS = 1, 2, 4, 8192  
 SORTBY_SYMBOLS = ["vsx_sortby_opts_default", "vsx_sortby", "vsx_sortby_out_free", "vsx_sortby_last_stats"]
 SORTBY_SIZE, SORTBY_LENGTH, SORTBY_LENGTH_ASC = 0, 1, 2                                 # VSX_SORTBY_*
 SORTBY_MAX_ROUNDS, SORTBY_STAT_ROUNDS = 32, 8
+# include/vsx_lca.h
+LCA_SYMBOLS = ["vsx_lca_opts_default", "vsx_lca_index_create", "vsx_lca_index_destroy", "vsx_lca", "vsx_lca_result_free", "vsx_lca_last_stats",
+               "vsx_internal_lca_host", "vsx_internal_lca_index_split"]
+LCA_LEVELS, LCA_NONE = 9, 0xFFFFFFFF                                                     # VSX_LCA_LEVELS / _NONE
 CUT_WANT_FWD, CUT_WANT_REV, CUT_WANT_REV_TEXT, CUT_WANT_DISCARDED_REV_TEXT = 1, 2, 4, 8
 CUT_DEVICE_MAX_PATTERN = 64
 MASK_WANT_TEXT, MASK_WANT_BITS = 1, 2                                                    # VSX_MASK_WANT_TEXT / _BITS
@@ -437,6 +441,24 @@ class SortbyStats(C.Structure):
                [("active", C.c_uint64 * SORTBY_STAT_ROUNDS)] + \
                [(n, C.c_uint64) for n in ("capped_items", "host_no_context", "host_environment", "host_count", "host_memory",
                                           "host_long_prefix")]
+
+
+class LcaOpts(C.Structure):
+    """vsx_lca_opts (include/vsx_lca.h)"""
+    _fields_ = [("lca_cutoff", C.c_double), ("maxhits", C.c_int64), ("top_hits_only", C.c_int32), ("threads", C.c_int32), ("window", C.c_uint64)]
+
+
+class LcaResult(C.Structure):
+    """vsx_lca_result (include/vsx_lca.h)"""
+    _fields_ = [("n_queries", C.c_uint64)] + [(n, C.POINTER(C.c_uint32)) for n in ("n_top", "depth", "matches", "target", "start", "len")]
+
+
+class LcaStats(C.Structure):
+    """vsx_lca_stats (include/vsx_lca.h)"""
+    _fields_ = [(n, C.c_double) for n in ("seconds_index_stage", "seconds_index_split", "seconds_index_number", "seconds_index_total",
+                                          "seconds_stage", "seconds_h2d", "seconds_vote", "seconds_d2h", "seconds_output", "seconds_total")] + \
+               [(n, C.c_uint64) for n in ("labels", "labels_device", "labels_host", "windows", "queries_device", "queries_host", "hits_device",
+                                          "hits_host", "host_no_context", "host_environment", "host_count", "host_memory", "host_collision")]
 
 
 class HitoutOpts(C.Structure):
@@ -847,6 +869,18 @@ def load():
     lib.vsx_sortby_out_free.restype = None
     lib.vsx_sortby_last_stats.argtypes = [C.POINTER(SortbyStats)]
     lib.vsx_sortby_last_stats.restype = None
+    lib.vsx_lca_opts_default.argtypes = [C.POINTER(LcaOpts)]
+    lib.vsx_lca_opts_default.restype = None
+    lib.vsx_lca_index_create.argtypes = [vp, C.POINTER(Labels), C.POINTER(vp)]
+    lib.vsx_lca_index_destroy.argtypes = [vp]
+    lib.vsx_lca_index_destroy.restype = None
+    lib.vsx_lca.argtypes = [vp, C.POINTER(LcaOpts), C.POINTER(Hits), C.POINTER(LcaResult)]
+    lib.vsx_lca_result_free.argtypes = [C.POINTER(LcaResult)]
+    lib.vsx_lca_result_free.restype = None
+    lib.vsx_lca_last_stats.argtypes = [C.POINTER(LcaStats)]
+    lib.vsx_lca_last_stats.restype = None
+    lib.vsx_internal_lca_host.argtypes = [C.POINTER(LcaOpts), C.POINTER(Labels), C.POINTER(Hits), C.POINTER(LcaResult)]
+    lib.vsx_internal_lca_index_split.argtypes = [vp, C.c_uint64, vp, vp]
     _lib = lib
     return lib
 

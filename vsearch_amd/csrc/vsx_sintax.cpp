@@ -12,8 +12,8 @@
 // place that knows --sintax_random (a reservoir draw per database sequence in scan order).
 #include "vsx_search_internal.h"
 #include "vsx_sintax_internal.h"
+#include "vsx_tax_split.h"
 
-#include <cctype>
 #include <unordered_map>
 #include <unordered_set>
 
@@ -46,46 +46,7 @@ namespace {
 
 thread_local vsx_sintax_stats g_stats;
 
-const char kRanks[] = "dkpcofgst";
-
-// tax_parse + tax_split (core/tax.cpp:70-186).  start/len stay 0 for a rank the header does not name.
-void tax_split(const char * h, int hlen, int * start, int * len)
-{
-  for (int k = 0; k < SX_RANKS; ++k) start[k] = len[k] = 0;
-  int tax_start = 0, tax_end = 0;
-  bool found = false;
-  int offset = 0;
-  while (offset < hlen - 4)
-    {
-      const char * p = std::strstr(h + offset, "tax=");
-      if (!p) break;
-      offset = (int) (p - h);
-      if (offset > 0 && h[offset - 1] != ';') { offset += 5; continue; }
-      tax_start = offset;
-      const char * e = std::strchr(h + offset + 4, ';');
-      tax_end = e ? (int) (e - h) : hlen;
-      found = true;
-      break;
-    }
-  if (!found) return;
-  offset = tax_start + 4;
-  while (offset < tax_end)
-    {
-      const char * r = std::strchr(kRanks, std::tolower((unsigned char) h[offset]));
-      if (r && *r)                                                   // (strchr also finds the terminator for a NUL)
-        {
-          const int level = (int) (r - kRanks);
-          if (h[offset + 1] == ':')
-            {
-              start[level] = offset + 2;
-              const char * comma = std::strchr(h + offset + 2, ',');    // not bounded by the end of the field
-              len[level] = comma ? (int) (comma - h) - offset - 2 : tax_end - offset - 2;
-            }
-        }
-      const char * comma = std::strchr(h + offset, ',');
-      offset = comma ? (int) (comma - h) + 1 : tax_end;
-    }
-}
+using vsxtax::tax_split;                                          // tax_parse + tax_split (core/tax.cpp:70-186), vsx_tax_split.h
 
 // ids[9 i + k]: 0 = the empty name; equal iff (length, bytes) are equal
 void intern_labels(uint64_t n, const char * const * labels, uint32_t * ids, int32_t * start_out, int32_t * len_out)
